@@ -3,7 +3,7 @@
 32-mer nodes, 21 844 labels), 150 bp synthetic reads, 160 M reads per GPU by default (10 steps x 16 M-read batches; a
 launch over 16 M reads classifies a read 10-12 % faster than one over 4 M: profiles/r03/batch_sizes.txt, DESIGN_APPENDIX.md section 0.12).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One process per GPU.  A "step" is one pass of the hot path (reverse-complement staging off, k-mer roller,
@@ -40,6 +40,8 @@ N_SIMD = 256 * 4               # 256 CUs x 4 SIMD16
 DEFAULT_BATCH_READS = 16_000_000   # reads per step of the default workload (hit_dense keeps 4 M: its kept profile is of that size)
 CONFIG_READS = 40_000_000          # BASELINE.json configs[1]: reads of the file -> file leg
 RANDOM_LINE_GBS = 48.6 * 128   # random 128-byte lines/s this chip serves (tools/membench.hip, profiles/r02/membench_random_lines.txt) x 128 B
+DUMP_MAX_READS = 1_000_000     # --dump-outputs: 1 M reads x 7 float64 = 56 MB, under the 64 MB the dump may take
+DUMP_SEED = 20241015
 
 
 def contract_bytes_per_read(n_nodes: int, W: int, I: int, read_len: int):
@@ -105,6 +107,10 @@ def main():
     ap.add_argument("--e2e-reads-per-rank", type=int, default=8_000_000, help="N>1: reads of each rank's shard in the file -> file leg")
     ap.add_argument("--no-cli-leg", action="store_true", help="N>1: skip the command-line leg (one process, all GPUs, one input, one output)")
     ap.add_argument("--make-files", default="", help="(internal) write the bench database as DIR/db.ctr and --e2e-reads reads as DIR/reads.fa, then exit")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write rank 0's results of the last timed step as DIR/results.npy (float64, one row of 6 result "
+                         "words per read, converted exactly) and DIR/read_index.npy (the reads' positions in the batch); batches of more than "
+                         "%d reads are sampled at a fixed seed" % DUMP_MAX_READS)
     args = resolve_defaults(ap.parse_args())
     if args.gpus <= 0:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
@@ -283,6 +289,8 @@ def main():
     if dist_on:
         elapsed = udist.max_over_ranks(elapsed, dev)
     k_ms, k_launches = tree.kernel_time(reset=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % nb])
 
     line = None
     if rank == 0:
@@ -356,6 +364,23 @@ def main():
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, res):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- DeviceTree.classify's (reads, 6) int32 result
+    words -- as float64 (which holds every int32 exactly), with the reads' positions in the batch.  A batch of more than DUMP_MAX_READS
+    reads is sampled at a fixed seed, so two builds run with the same arguments write the same rows."""
+    import numpy as np
+    import torch
+    n = res.shape[0]
+    if n > DUMP_MAX_READS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_READS, replace=False))
+    else:
+        idx = np.arange(n)
+    rows = res.index_select(0, torch.from_numpy(idx).to(res.device)).cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "results.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "read_index.npy"), idx.astype(np.float64))
 
 
 def e2e_leg_dist(args, sdb, tree, rank, world, dev, udist):

@@ -18,6 +18,9 @@ Fixture sets:
   k64     F4  PACKSIZE=64 build of a smaller toy + reads (+RC)
   ix32    F4  IXTYPE=uint32_t build of a smaller toy + reads
   k64ix32 F4  PACKSIZE=64 and IXTYPE=uint32_t together (+RC)
+
+`python tests/golden/make_golden.py reference_runs` writes reference_runs.json: hashes of the reference's results on the
+inputs tests/util.py generates (adversarial labels, byte and framing fuzz, hostile BUILD inputs, irregular PACKSIZE=16 tables).
 """
 import gzip
 import hashlib
@@ -727,9 +730,71 @@ def gen_build(manifest, seed=2025):
     manifest["build_outputs"] = out
 
 
+def gen_reference_runs():
+    """reference_runs.json: what the genuine binaries did on the inputs tests/util.py generates for the oracle-vs-reference tests
+    (tests/test_oracle_golden.py) -- SHA-256 of every input, exit code, SHA-256 of every output file (None where none was written) --
+    so that those tests hold the oracle to the reference without the reference at hand."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import util
+
+    def ref_run(exe, inputs, args, outputs):
+        for f in outputs.values():
+            if os.path.exists(f):
+                os.remove(f)
+        code, _, _ = run([os.path.join(REF, exe)] + args)
+        return {"inputs": {k: util.sha256_of(v) for k, v in inputs.items()}, "exit": code,
+                "outputs": {k: util.sha256_of(f) for k, f in outputs.items()}}
+
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        fa, want = os.path.join(td, "r.fa"), os.path.join(td, "ref.txt")
+        for seed, max_depth in [(1, 8), (2, 8), (3, 8), (4, 7), (5, 7), (6, 5)]:
+            ctr, data, _ = util.adversarial_vote_case(seed, td, max_depth)
+            open(fa, "wb").write(data)
+            out["vote_adversarial_%d_%d" % (seed, max_depth)] = ref_run("xtree-searchGG", {"ctr": ctr, "fa": data}, [ctr, fa, want, "1"], {"out": want})
+        ctr, data, _ = util.adversarial_vote_case(2, td)
+        open(fa, "wb").write(data)
+        out["rank_adversarial_2"] = ref_run("xtree-search", {"ctr": ctr, "fa": data}, [ctr, fa, want, "1"], {"out": want})
+        for name, with_gt in [("toy", False), ("toy", True), ("k64", False), ("ix32", False), ("k64ix32", False), ("vote", False), ("k16", False)]:
+            data = util.byte_fuzz_reads(name, 21, with_gt)
+            open(fa, "wb").write(data)
+            exe = "xtree-searchGG" + {"k64": "-k64", "ix32": "-ix32", "k64ix32": "-k64-ix32", "k16": "-k16"}.get(name, "")
+            for rc in (0, 1):
+                ctr = util.fixture_ctr(name)
+                out["byte_fuzz_%s_%d_rc%d" % (name, with_gt, rc)] = ref_run(exe, {"ctr": ctr, "fa": data}, [ctr, fa, want, "1"] + (["RC"] if rc else []),
+                                                                            {"out": want})
+        mp, ubt = os.path.join(td, "i.map"), os.path.join(td, "r.ubt")
+        for exe, gg in [("utree-buildGG", 1), ("utree-build", 0), ("utree-buildGG-k64", 1)]:
+            for seed in (1, 2):
+                fa_b, mp_b = util.hostile_build_case(seed)
+                open(fa, "wb").write(fa_b)
+                open(mp, "wb").write(mp_b)
+                for cl in (0, 1, 2):
+                    out["build_hostile_%s_%d_c%d" % (exe, seed, cl)] = ref_run(exe, {"fa": fa_b, "map": mp_b}, [fa, mp, ubt, "1", str(cl)],
+                                                                               {"ubt": ubt, "log": ubt + (".gg.log" if gg else ".log")})
+        for seed in range(16):
+            data = util.framing_fuzz_case(seed)
+            open(fa, "wb").write(data)
+            for rc in (0, 1):
+                ctr = util.fixture_ctr("toy")
+                out["framing_fuzz_%d_rc%d" % (seed, rc)] = ref_run("xtree-searchGG", {"ctr": ctr, "fa": data}, [ctr, fa, want, "1"] + (["RC"] if rc else []),
+                                                                   {"out": want})
+        k16 = util.k16_table_cases(td)
+        for case in ("quirk", "dups", "generic"):
+            ctr, data = k16[case]
+            open(fa, "wb").write(data)
+            for rc in (0, 1):
+                out["k16_table_%s_rc%d" % (case, rc)] = ref_run("xtree-searchGG-k16", {"ctr": ctr, "fa": data}, [ctr, fa, want, "1"] + (["RC"] if rc else []),
+                                                                {"out": want})
+    json.dump(out, open(os.path.join(HERE, "reference_runs.json"), "w"), indent=1, sort_keys=True)
+
+
 def main():
     if not os.path.exists(os.path.join(REF, "xtree-searchGG")):
         sys.exit("build the reference first: make -C oracle ref")
+    if len(sys.argv) > 1 and sys.argv[1] == "reference_runs":  # add reference_runs.json (the oracle-vs-reference tests' expected results)
+        gen_reference_runs()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "compress":       # add the COMPRESS fixtures to an existing golden set
         manifest = json.load(open(os.path.join(HERE, "manifest.json")))
         gen_compress(manifest)

@@ -122,6 +122,26 @@ def test_bench_launch_size_defaults():
     assert (a.batch_reads, a.e2e_reads) == (4_000_000, 1_000_000)
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last step's (reads, 6) int32 result words as float64, exactly; a batch larger than the cap is sampled at a
+    fixed seed (the same rows every run), and the files stay under 64 MB."""
+    import bench
+    g = torch.Generator().manual_seed(3)
+    small = torch.randint(-2**31, 2**31 - 1, (1000, 6), dtype=torch.int32, generator=g)
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    assert np.array_equal(np.load(tmp_path / "a" / "results.npy"), small.numpy().astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "read_index.npy"), np.arange(1000, dtype=np.float64))
+    n = bench.DUMP_MAX_READS + 12345
+    big = torch.arange(n * 6, dtype=torch.int32).reshape(n, 6)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    res, idx = np.load(tmp_path / "b" / "results.npy"), np.load(tmp_path / "b" / "read_index.npy")
+    assert res.dtype == idx.dtype == np.float64 and res.shape == (bench.DUMP_MAX_READS, 6)
+    assert np.array_equal(res, big.numpy()[idx.astype(np.int64)].astype(np.float64)) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "read_index.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 64 << 20
+
+
 def test_bench_gpus_flag_cold_start_reaches_every_rank(tmp_path):
     """The real thing from a cold start, on this GPU-less box: two ranks come up under torch.distributed.run and each one refuses
     to run without an MI355X (there is no CPU fallback); the launcher's exit code comes back."""

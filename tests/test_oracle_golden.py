@@ -178,120 +178,99 @@ def test_build_matches_reference(tag, tmpdir_mod):
         assert ("Total nodes in tree: %d [%d labels]" % (nn, nl)) in v["stdout_tail"]
 
 
-@pytest.mark.skipif(not util.have_ref(), reason="needs oracle/_ref (the genuine reference, built from /root/reference by `make -C oracle ref`)")
 @pytest.mark.parametrize("seed,max_depth", [(1, 8), (2, 8), (3, 8), (4, 7), (5, 7), (6, 5)])
 def test_vote_adversarial_cases_oracle_vs_reference(seed, max_depth, tmp_path):
     """The label sets the GPU vote is stressed with (util.adversarial_vote_case) go beyond the committed vote fixture, so
-    the oracle is first held against the genuine reference binary on them, where that binary exists."""
-    import subprocess
+    the oracle is first held against what the genuine reference binary wrote on them (golden/reference_runs.json)."""
     ctr_path, data, n_reads = util.adversarial_vote_case(seed, str(tmp_path), max_depth)
+    want = util.reference_run("vote_adversarial_%d_%d" % (seed, max_depth), ctr=ctr_path, fa=data)
+    assert want["exit"] == 0
     fa = tmp_path / "r.fa"
     fa.write_bytes(data)
-    want = tmp_path / "ref.txt"
-    r = subprocess.run([os.path.join(util.REF_DIR, "xtree-searchGG"), ctr_path, str(fa), str(want), "1"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()
     o = orc.OracleDB.load(ctr_path)
     got = tmp_path / "orc.txt"
     code, nr, good, err = o.search_file(str(fa), str(got), threads=4, rc=False)
     assert code == 0 and nr == n_reads
-    assert got.read_bytes() == want.read_bytes() and good > 1000
+    assert util.sha256_of(str(got)) == want["outputs"]["out"] and good > 1000
 
 
-@pytest.mark.skipif(not util.have_ref(), reason="needs oracle/_ref (the genuine reference, built from /root/reference by `make -C oracle ref`)")
 def test_rank_search_adversarial_case_oracle_vs_reference(tmp_path):
     """Same hostile label set through the rank-specific search (`xtree-search`): whole output files identical."""
-    import subprocess
     ctr_path, data, n_reads = util.adversarial_vote_case(2, str(tmp_path))
+    want = util.reference_run("rank_adversarial_2", ctr=ctr_path, fa=data)
+    assert want["exit"] == 0
     fa = tmp_path / "r.fa"
     fa.write_bytes(data)
-    want = tmp_path / "ref.txt"
-    r = subprocess.run([os.path.join(util.REF_DIR, "xtree-search"), ctr_path, str(fa), str(want), "1"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0, r.stderr.decode()
     got = tmp_path / "orc.txt"
     code, nr, good, err = orc.rank_search_file(orc.OracleDB.load(ctr_path), str(fa), str(got))
     assert code == 0 and nr == n_reads and good > 100
-    assert got.read_bytes() == want.read_bytes()
+    assert util.sha256_of(str(got)) == want["outputs"]["out"]
 
 
-@pytest.mark.skipif(not util.have_ref(), reason="needs oracle/_ref (the genuine reference, built from /root/reference by `make -C oracle ref`)")
 @pytest.mark.parametrize("name,with_gt", [("toy", False), ("toy", True), ("k64", False), ("ix32", False), ("k64ix32", False), ("vote", False), ("k16", False)])
 def test_byte_fuzz_oracle_vs_reference(name, with_gt, tmp_path):
     """Sequence lines with arbitrary 7-bit bytes, both strands: output file AND exit code of the oracle equal the genuine
     reference's (with '>' allowed, both stop at the same record with the format error)."""
-    import subprocess
     data = util.byte_fuzz_reads(name, 21, with_gt)
     fa = tmp_path / "f.fa"
     fa.write_bytes(data)
-    exe = "xtree-searchGG" + {"k64": "-k64", "ix32": "-ix32", "k64ix32": "-k64-ix32", "k16": "-k16"}.get(name, "")
     o = orc.OracleDB.load(util.fixture_ctr(name))
     for rc in (False, True):
-        want, got = tmp_path / "ref.txt", tmp_path / "orc.txt"
-        r = subprocess.run([os.path.join(util.REF_DIR, exe), util.fixture_ctr(name), str(fa), str(want), "1"] + (["RC"] if rc else []),
-                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        want = util.reference_run("byte_fuzz_%s_%d_rc%d" % (name, with_gt, rc), ctr=util.fixture_ctr(name), fa=data)
+        got = tmp_path / "orc.txt"
         code, nr, good, err = o.search_file(str(fa), str(got), threads=4, rc=rc)
-        assert code == r.returncode and (code == 2) == with_gt
-        assert got.read_bytes() == want.read_bytes() and good > 10
+        assert code == want["exit"] and (code == 2) == with_gt
+        assert util.sha256_of(str(got)) == want["outputs"]["out"] and good > 10
 
 
-@pytest.mark.skipif(not util.have_ref(), reason="needs oracle/_ref (the genuine reference, built from /root/reference by `make -C oracle ref`)")
 @pytest.mark.parametrize("exe,W,gg", [("utree-buildGG", 8, 1), ("utree-build", 8, 0), ("utree-buildGG-k64", 16, 1)])
 def test_build_hostile_labels_oracle_vs_reference(exe, W, gg, tmp_path):
     """BUILD / BUILD_GG with hostile labels (util.hostile_build_case): `.ubt` and log of the oracle equal the genuine reference's
-    at every compression level."""
-    import subprocess
+    (built by `exe`) at every compression level."""
     for seed in (1, 2):
         fa_b, mp_b = util.hostile_build_case(seed)
         fa = tmp_path / "i.fa"; mp = tmp_path / "i.map"
         fa.write_bytes(fa_b); mp.write_bytes(mp_b)
         for cl in (0, 1, 2):
-            want, got = str(tmp_path / "r.ubt"), str(tmp_path / "o.ubt")
-            r = subprocess.run([os.path.join(util.REF_DIR, exe), str(fa), str(mp), want, "1", str(cl)], stdout=subprocess.PIPE,
-                               stderr=subprocess.PIPE, timeout=600)
-            assert r.returncode == 0
+            want = util.reference_run("build_hostile_%s_%d_c%d" % (exe, seed, cl), fa=fa_b, map=mp_b)
+            assert want["exit"] == 0
+            got = str(tmp_path / "o.ubt")
             code, ns, nn, nl, err = orc.build_file(str(fa), str(mp), got, W=W, I=2, complevel=cl, gg=bool(gg))
             assert code == 0, err
             ext = ".gg.log" if gg else ".log"
-            assert open(got, "rb").read() == open(want, "rb").read()
-            assert open(got + ext, "rb").read() == open(want + ext, "rb").read()
+            assert util.sha256_of(got) == want["outputs"]["ubt"]
+            assert util.sha256_of(got + ext) == want["outputs"]["log"]
 
 
-@pytest.mark.skipif(not util.have_ref(), reason="needs oracle/_ref (the genuine reference, built from /root/reference by `make -C oracle ref`)")
 def test_framing_fuzz_oracle_vs_reference(tmp_path):
     """Sixteen random files from the grammar of framing corner cases (util.framing_fuzz_case; 150 were run once while writing
     this test), both strands: the oracle's exit code and output file equal the genuine reference's."""
-    import subprocess
     o = orc.OracleDB.load(util.fixture_ctr("toy"))
     for seed in range(16):
+        data = util.framing_fuzz_case(seed)
         fa = tmp_path / "f.fa"
-        fa.write_bytes(util.framing_fuzz_case(seed))
+        fa.write_bytes(data)
         for rc in (False, True):
-            want, got = tmp_path / "ref.txt", tmp_path / "orc.txt"
-            for f in (want, got):
-                if f.exists():
-                    f.unlink()
-            r = subprocess.run([os.path.join(util.REF_DIR, "xtree-searchGG"), util.fixture_ctr("toy"), str(fa), str(want), "1"] + (["RC"] if rc else []),
-                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+            want = util.reference_run("framing_fuzz_%d_rc%d" % (seed, rc), ctr=util.fixture_ctr("toy"), fa=data)
+            got = tmp_path / "orc.txt"
+            if got.exists():
+                got.unlink()
             code, nr, good, err = o.search_file(str(fa), str(got), threads=2, rc=rc)
-            assert code == r.returncode, seed
-            assert (got.read_bytes() if got.exists() else None) == (want.read_bytes() if want.exists() else None), seed
+            assert code == want["exit"], seed
+            assert util.sha256_of(str(got)) == want["outputs"]["out"], seed
 
 
-@pytest.mark.skipif(not util.have_ref(), reason="needs oracle/_ref (the genuine reference, built from /root/reference by `make -C oracle ref`)")
 @pytest.mark.parametrize("case", ["quirk", "dups", "generic"])
 def test_packsize16_irregular_tables_oracle_vs_reference(case, tmp_path):
     """PACKSIZE=16 trees off the regular shape (util.k16_table_cases): the oracle equals the genuine reference built with -D PACKSIZE=16,
     both strand modes -- which pins the oracle the GPU's direct-address table is held to in tests/test_gpu_parity.py."""
-    import subprocess
     ctr, data = util.k16_table_cases(str(tmp_path))[case]
     fa = tmp_path / "r.fa"
     fa.write_bytes(data)
     o = orc.OracleDB.load(ctr)
     for rc in (False, True):
-        want, got = tmp_path / "ref.txt", tmp_path / "orc.txt"
-        r = subprocess.run([os.path.join(util.REF_DIR, "xtree-searchGG-k16"), ctr, str(fa), str(want), "1"] + (["RC"] if rc else []),
-                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        want = util.reference_run("k16_table_%s_rc%d" % (case, rc), ctr=ctr, fa=data)
+        got = tmp_path / "orc.txt"
         code, nr, good, err = o.search_file(str(fa), str(got), threads=4, rc=rc)
-        assert r.returncode == 0 and code == 0
-        assert got.read_bytes() == want.read_bytes() and good > 100
+        assert want["exit"] == 0 and code == 0
+        assert util.sha256_of(str(got)) == want["outputs"]["out"] and good > 100
