@@ -15,7 +15,7 @@
  *   - `.ctr` files are consumed unchanged (layout: itree.c:1301-1313 writer, 736-775 reader);
  *   - PACKSIZE / IXTYPE are compile-time in the reference (itree.c:35-70) and run-time here: W in {4,8,16}
  *     (k = 16, 32, 64: every PACKSIZE the reference compiles with, README.md:87-88) and I in {2,4} are dispatched from the file
- *     header; PACKSIZE=16 trees are searched (GG) and compressed, not built or searched rank-specifically;
+ *     header; PACKSIZE=16 trees are built (utree_build_file with W = 4), compressed and searched both ways (GG and rank-specific);
  *   - there is no CPU fallback: every compute entry point needs a gfx950 device and fails with
  *     UTREE_E_HIP otherwise.
  */

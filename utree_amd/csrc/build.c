@@ -116,7 +116,7 @@ static int write_all(int fd, const void *p, size_t n) {
 
 int utree_build_file(const char *fasta_path, const char *map_path, const char *ubt_path, uint32_t W, uint32_t I, int complevel,
                      int gg, int device, utree_build_stats *stats) {
-    if (!fasta_path || !map_path || !ubt_path || (W != 8 && W != 16) || (I != 2 && I != 4) || complevel < 0 || complevel > 4)
+    if (!fasta_path || !map_path || !ubt_path || (W != 4 && W != 8 && W != 16) || (I != 2 && I != 4) || complevel < 0 || complevel > 4)
         return UTREE_E_ARG;
     utree_build_stats st; memset(&st, 0, sizeof st);
     st.W = W; st.I = I;

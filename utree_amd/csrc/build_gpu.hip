@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
+#include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -85,14 +86,15 @@ __device__ __forceinline__ bool eval_pos(const dev_in &in, uint64_t g, uint64_t 
         acc[q >> 3] = (acc[q >> 3] << 8) | byte;
     }
     if (bad) return false;                                                  // 609-612
-    if (W == 8) { hi = 0; lo = acc[0]; } else { hi = acc[0]; lo = acc[1]; }
+    if (W == 16) { hi = acc[0]; lo = acc[1]; } else { hi = 0; lo = acc[0]; }           // W = 4: the 16-mer in the low 32 bits
     return true;
 }
 
 // k-mers are handled in passes over ranges of their top 12 bits ("buckets"): each pass sorts fewer than 2^31 items and
-// its buffers fit what is left of the HBM; the ranges are contiguous in the final order.
+// its buffers fit what is left of the HBM; the ranges are contiguous in the final order.  (W = 4: a 32-bit word, bits 31..20.)
 constexpr uint32_t BUCKET_BITS = 12, N_BUCKETS = 1u << BUCKET_BITS;
 template <int W> __device__ __forceinline__ uint32_t bucket_of(uint64_t hi, uint64_t lo) {
+    if constexpr (W == 4) return (uint32_t)(lo >> (32 - BUCKET_BITS)) & (N_BUCKETS - 1u);
     return (uint32_t)((W == 16 ? hi : lo) >> (64 - BUCKET_BITS));
 }
 
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(BLOCK) void fold_k(const uint64_t *__restrict__ key
                                                 unsigned long long *__restrict__ n_distinct) {
     const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     const uint64_t lo = j < n ? key_lo[j] : 0, hi = (W == 16 && j < n) ? key_hi[j] : 0;
-    const bool head = j < n && !(j && key_lo[j - 1] == lo && (W == 8 || key_hi[j - 1] == hi));
+    const bool head = j < n && !(j && key_lo[j - 1] == lo && (W != 16 || key_hi[j - 1] == hi));
     {   // distinct k-mers of the pass (the reference's NumsInserted, itree.c:448,466): one atomic per wavefront
         const uint64_t hm = __ballot(head);
         if (hm && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(hm)) atomicAdd(n_distinct, (unsigned long long)__popcll(hm));
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(BLOCK) void fold_k(const uint64_t *__restrict__ key
     if (j >= n) return;
     if (!head) { state_out[j] = ST_SKIP; return; }
     uint32_t st = (uint32_t)(val[j] & 0xFFFFFFu);                           // first occurrence: its reference's label
-    for (uint64_t t = j + 1; t < n && key_lo[t] == lo && (W == 8 || key_hi[t] == hi); ++t) {
+    for (uint64_t t = j + 1; t < n && key_lo[t] == lo && (W != 16 || key_hi[t] == hi); ++t) {
         const uint64_t v = val[t];
         const uint32_t nu = (uint32_t)(v & 0xFFFFFFu);
         if (nu == st) continue;                                             // same label: nothing happens (262, 280)
@@ -217,7 +219,7 @@ __global__ __launch_bounds__(BLOCK) void pack_k(const uint64_t *__restrict__ lo,
     uint8_t *o = out + i * (uint64_t)(W + I);
     const uint64_t l = lo[first + i];
 #pragma unroll
-    for (int b = 0; b < 8; ++b) o[b] = (uint8_t)(l >> (8 * b));            // fwrite(&word) of a little-endian WTYPE (402-404)
+    for (int b = 0; b < (W == 4 ? 4 : 8); ++b) o[b] = (uint8_t)(l >> (8 * b));   // fwrite(&word) of a little-endian WTYPE (402-404)
     if (W == 16) {
         const uint64_t h = hi[first + i];
 #pragma unroll
@@ -226,6 +228,15 @@ __global__ __launch_bounds__(BLOCK) void pack_k(const uint64_t *__restrict__ lo,
 #pragma unroll
     for (int b = 0; b < I; ++b) o[W + b] = (uint8_t)(ix >> (8 * b));
     atomicAdd(&per_label[ix], 1ull);                                        // ++cnts[tree->ix] (412)
+}
+
+// one instantiation per W (k = 16, 32, 64); any other W is refused before a kernel is launched
+template <typename Fn> bool dispatch_w(int W, Fn &&fn) {
+    if (W == 4) fn(std::integral_constant<int, 4>{});
+    else if (W == 8) fn(std::integral_constant<int, 8>{});
+    else if (W == 16) fn(std::integral_constant<int, 16>{});
+    else return false;
+    return true;
 }
 
 #define HK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[utree_amd] build: %s: %s\n", #x, hipGetErrorString(e_)); rc = UTREE_E_HIP; goto fail; } } while (0)
@@ -268,8 +279,7 @@ static int build_pass(const utk_build_job *job, const dev_in &in, const universe
     size_t tb = 0;
     uint64_t n = 0;
     memset(seg, 0, sizeof *seg);
-    if (W == 8) count_k<8><<<dim3((unsigned)n_blocks), dim3(BLOCK)>>>(in, b_lo, b_hi, d_counts);
-    else count_k<16><<<dim3((unsigned)n_blocks), dim3(BLOCK)>>>(in, b_lo, b_hi, d_counts);
+    dispatch_w(W, [&](auto w) { count_k<decltype(w)::value><<<dim3((unsigned)n_blocks), dim3(BLOCK)>>>(in, b_lo, b_hi, d_counts); });
     HK(hipGetLastError());
     HK(rocprim::exclusive_scan(nullptr, tb, d_counts, d_block_off, (uint64_t)0, n_blocks + 1, rocprim::plus<uint64_t>()));
     HK(hipMalloc(&tmp, tb ? tb : 8));
@@ -281,15 +291,15 @@ static int build_pass(const utk_build_job *job, const dev_in &in, const universe
     {
         const unsigned gb = (unsigned)((n + BLOCK - 1) / BLOCK);
         if (dmalloc(&k_lo, n) || dmalloc(&k_val, n) || (W == 16 && dmalloc(&k_hi, n))) { rc = UTREE_E_NOMEM; goto fail; }
-        if (W == 8) emit_k<8><<<dim3((unsigned)n_blocks), dim3(BLOCK)>>>(in, b_lo, b_hi, d_block_off, k_lo, k_hi, k_val);
-        else emit_k<16><<<dim3((unsigned)n_blocks), dim3(BLOCK)>>>(in, b_lo, b_hi, d_block_off, k_lo, k_hi, k_val);
+        dispatch_w(W, [&](auto w) { emit_k<decltype(w)::value><<<dim3((unsigned)n_blocks), dim3(BLOCK)>>>(in, b_lo, b_hi, d_block_off, k_lo, k_hi, k_val); });
         HK(hipGetLastError());
-        // ---- stable sort by k-mer ----
-        if (W == 8) {
+        // ---- stable sort by k-mer (W = 4: only the low 32 bits carry the 16-mer, so half the digit passes) ----
+        if (W != 16) {
+            const unsigned end_bit = W == 4 ? 32u : 64u;
             if (dmalloc(&a_lo, n) || dmalloc(&a_val, n)) { rc = UTREE_E_NOMEM; goto fail; }
-            HK(rocprim::radix_sort_pairs(nullptr, tb, k_lo, a_lo, k_val, a_val, n, 0, 64));
+            HK(rocprim::radix_sort_pairs(nullptr, tb, k_lo, a_lo, k_val, a_val, n, 0, end_bit));
             HK(hipMalloc(&tmp, tb ? tb : 8));
-            HK(rocprim::radix_sort_pairs(tmp, tb, k_lo, a_lo, k_val, a_val, n, 0, 64));
+            HK(rocprim::radix_sort_pairs(tmp, tb, k_lo, a_lo, k_val, a_val, n, 0, end_bit));
             HK(hipDeviceSynchronize());
             HK(hipFree(tmp)); tmp = nullptr;
             HK(hipFree(k_lo)); HK(hipFree(k_val));
@@ -313,10 +323,11 @@ static int build_pass(const utk_build_job *job, const dev_in &in, const universe
         }
         // ---- replay each k-mer's occurrences ----
         if (dmalloc(&d_state, n)) { rc = UTREE_E_NOMEM; goto fail; }
-        if (W == 8 && job->gg) fold_k<8, true><<<dim3(gb), dim3(BLOCK)>>>(k_lo, k_hi, k_val, n, U, d_first, d_state, d_distinct);
-        else if (W == 8) fold_k<8, false><<<dim3(gb), dim3(BLOCK)>>>(k_lo, k_hi, k_val, n, U, d_first, d_state, d_distinct);
-        else if (job->gg) fold_k<16, true><<<dim3(gb), dim3(BLOCK)>>>(k_lo, k_hi, k_val, n, U, d_first, d_state, d_distinct);
-        else fold_k<16, false><<<dim3(gb), dim3(BLOCK)>>>(k_lo, k_hi, k_val, n, U, d_first, d_state, d_distinct);
+        dispatch_w(W, [&](auto w) {
+            constexpr int WV = decltype(w)::value;
+            if (job->gg) fold_k<WV, true><<<dim3(gb), dim3(BLOCK)>>>(k_lo, k_hi, k_val, n, U, d_first, d_state, d_distinct);
+            else fold_k<WV, false><<<dim3(gb), dim3(BLOCK)>>>(k_lo, k_hi, k_val, n, U, d_first, d_state, d_distinct);
+        });
         HK(hipGetLastError());
         HK(hipFree(k_val)); k_val = nullptr;
         // ---- keep what is not BAD, ascending ----
@@ -368,6 +379,7 @@ int utk_build_phase1(const utk_build_job *job, utk_build_result *res, utk_build_
     unsigned long long *d_first = nullptr, *d_hist = nullptr;
     uint64_t *h_prefix = nullptr;
     unsigned long long *h_hist = nullptr;
+    if (!dispatch_w(W, [](auto) {}) || (job->I != 2 && job->I != 4)) return UTREE_E_ARG;   /* k = 16, 32, 64 only */
     utk_build_state *S = (utk_build_state *)calloc(1, sizeof *S);
     if (!S) return UTREE_E_NOMEM;
     S->device = job->device; S->W = W; S->I = (int)job->I;
@@ -416,7 +428,7 @@ int utk_build_phase1(const utk_build_job *job, utk_build_result *res, utk_build_
         HK(hipMemset(d_counts, 0, 4 * (n_blocks + 1)));
         {
             const unsigned hb = n_blocks > 8192 ? 8192u : (unsigned)n_blocks;
-            if (W == 8) hist_k<8><<<dim3(hb), dim3(BLOCK)>>>(in, d_hist); else hist_k<16><<<dim3(hb), dim3(BLOCK)>>>(in, d_hist);
+            dispatch_w(W, [&](auto w) { hist_k<decltype(w)::value><<<dim3(hb), dim3(BLOCK)>>>(in, d_hist); });
             HK(hipGetLastError());
             HK(hipMemcpy(h_hist, d_hist, 8ull * N_BUCKETS, hipMemcpyDeviceToHost));
         }
@@ -427,7 +439,7 @@ int utk_build_phase1(const utk_build_job *job, utk_build_result *res, utk_build_
         HK(hipMemset(d_hist, 0, 8));                                     /* the histogram is on the host now: word 0 counts distinct k-mers */
         // passes: contiguous bucket ranges of at most `limit` occurrences
         HK(hipMemGetInfo(&free_b, &total_b));
-        uint64_t limit = (free_b > ((uint64_t)2 << 30) ? free_b - ((uint64_t)2 << 30) : 0) / (W == 16 ? 72ull : 44ull);
+        uint64_t limit = (free_b > ((uint64_t)2 << 30) ? free_b - ((uint64_t)2 << 30) : 0) / (W == 16 ? 72ull : 44ull);   /* W = 4: 64-bit keys as W = 8, no k_hi */
         if (limit > (1ull << 31) - 1) limit = (1ull << 31) - 1;
         { const char *e = getenv("UTREE_BUILD_PASS_KMERS"); if (e && atoll(e) > 0 && (uint64_t)atoll(e) < limit) limit = (uint64_t)atoll(e); }
         S->seg = (build_seg *)calloc(N_BUCKETS, sizeof(build_seg));
@@ -478,7 +490,8 @@ fail:
 int utk_build_phase2(utk_build_state *S, const uint32_t *h_ix_of_u, uint32_t n_u, uint32_t n_labels, int fd, uint64_t *h_per_label) {
     int rc = UTREE_OK;
     uint32_t *d_ix = nullptr; unsigned long long *d_cnt = nullptr; uint8_t *d_out = nullptr; uint8_t *h_out = nullptr;
-    const uint64_t CH = 32ull << 20, rec = (uint64_t)(S->W + S->I);
+    const uint64_t CH = 32ull << 20, rec = (uint64_t)(S->W + S->I);   /* W = 4: a 4-byte uint32_t word + I bytes */
+    if (!dispatch_w(S->W, [](auto) {}) || (S->I != 2 && S->I != 4)) return UTREE_E_ARG;
     HK(hipSetDevice(S->device));
     if (dmalloc(&d_ix, n_u) || dmalloc(&d_cnt, n_labels) || dmalloc(&d_out, CH * rec)) { rc = UTREE_E_NOMEM; goto fail; }
     HK(hipHostMalloc((void **)&h_out, CH * rec, hipHostMallocDefault));
@@ -489,10 +502,11 @@ int utk_build_phase2(utk_build_state *S, const uint32_t *h_ix_of_u, uint32_t n_u
         for (uint64_t first = 0; first < G.n; first += CH) {
             const uint64_t cnt = G.n - first < CH ? G.n - first : CH;
             const unsigned gb = (unsigned)((cnt + BLOCK - 1) / BLOCK);
-            if (S->W == 8 && S->I == 2) pack_k<8, 2><<<dim3(gb), dim3(BLOCK)>>>(G.lo, G.hi, G.st, d_ix, first, cnt, d_out, d_cnt);
-            else if (S->W == 8) pack_k<8, 4><<<dim3(gb), dim3(BLOCK)>>>(G.lo, G.hi, G.st, d_ix, first, cnt, d_out, d_cnt);
-            else if (S->I == 2) pack_k<16, 2><<<dim3(gb), dim3(BLOCK)>>>(G.lo, G.hi, G.st, d_ix, first, cnt, d_out, d_cnt);
-            else pack_k<16, 4><<<dim3(gb), dim3(BLOCK)>>>(G.lo, G.hi, G.st, d_ix, first, cnt, d_out, d_cnt);
+            dispatch_w(S->W, [&](auto w) {
+                constexpr int WV = decltype(w)::value;
+                if (S->I == 2) pack_k<WV, 2><<<dim3(gb), dim3(BLOCK)>>>(G.lo, G.hi, G.st, d_ix, first, cnt, d_out, d_cnt);
+                else pack_k<WV, 4><<<dim3(gb), dim3(BLOCK)>>>(G.lo, G.hi, G.st, d_ix, first, cnt, d_out, d_cnt);
+            });
             HK(hipGetLastError());
             HK(hipMemcpy(h_out, d_out, cnt * rec, hipMemcpyDeviceToHost));
             uint64_t done = 0;

@@ -5,7 +5,7 @@
  * Same positional arguments, same files written (`output.ubt`, `output.ubt[.gg].log`), same exit codes (1 files, 2 malformed
  * map / FASTA / no k-mers, 3 out of memory, 4 name not in the map).  `threads` is accepted and ignored (the reference's
  * parse loop is sequential too, itree.c:575).  The reference's compile-time -D PACKSIZE / -D IXTYPE come from the
- * environment: UTREE_PACKSIZE=32|64 (default 32), UTREE_IXTYPE=16|32 (default 16); UTREE_DEVICE picks the GPU.
+ * environment: UTREE_PACKSIZE=16|32|64 (default 32; any other value is 32), UTREE_IXTYPE=16|32 (default 16); UTREE_DEVICE picks the GPU.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -43,6 +43,7 @@ int main(int argc, char *argv[]) {
     printf("Setting compression level to %u\n", cl);
     uint32_t W = 8, I = 2;
     if (getenv("UTREE_PACKSIZE") && atoi(getenv("UTREE_PACKSIZE")) == 64) W = 16;
+    if (getenv("UTREE_PACKSIZE") && atoi(getenv("UTREE_PACKSIZE")) == 16) W = 4;
     if (getenv("UTREE_IXTYPE") && atoi(getenv("UTREE_IXTYPE")) == 32) I = 4;
     int device = getenv("UTREE_DEVICE") ? atoi(getenv("UTREE_DEVICE")) : 0;
     utree_build_stats st;

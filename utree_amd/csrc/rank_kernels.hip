@@ -16,7 +16,8 @@
 //  * output: label with the most votes, 1 - secondMost/most, most; only if most >= TOLERANCE_THRESHOLD and
 //    most >= SLACK * secondMost (1000-1002).
 //
-//   rank_hits_k    one wavefront per read, any length (staged through LDS in 960-window segments)
+//   rank_hits_k    one wavefront per read, any length (staged through LDS in 960-window segments); k = 16, 32, 64
+//                  (PACKSIZE=16: each examined window is one load from the direct-address table, wave_common.hpp: direct_rank)
 //   block_max_k    max tree over the hit counts (three launches)
 //   rank_vote_k    one wavefront per read: carried entry, tally, most / secondMost
 //   rank_state_k   folds the batch into the carried array
@@ -53,11 +54,15 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
 }
 
 // The word the reference looks up d bases after a hit on w0 (S <= d < K), given the query's real k-mer there.
+// The register is a WTYPE: for W = 4 (PACKSIZE=16) a uint32_t, so the shifted word wraps in 32 bits (sh <= 60 here).
 template <int W>
 __device__ __forceinline__ void register_word(uint64_t w0hi, uint64_t w0lo, uint64_t th, uint64_t tl, uint32_t d, uint32_t S,
                                               uint64_t &eh, uint64_t &el) {
     const uint32_t sh = 2u * (d + S - 1u);
-    if constexpr (W == 8) {
+    if constexpr (W == 4) {
+        eh = 0;
+        el = ((w0lo << sh) | (tl & ((1ull << (2u * d)) - 1ull))) & 0xFFFFFFFFull;
+    } else if constexpr (W == 8) {
         eh = 0;
         el = (sh >= 64u ? 0ull : (w0lo << sh)) | (tl & ((1ull << (2u * d)) - 1ull));
     } else {
@@ -151,7 +156,7 @@ __global__ __launch_bounds__(256) void rank_hits_k(utk_image im, const uint8_t *
                     const uint32_t ch = il >> 6, bit = il & 63u;
                     const uint64_t b0 = sbad[ch], b1 = sbad[ch + 1];
                     const uint64_t x = (b0 >> bit) | (bit ? (b1 << (64 - bit)) : 0ull);
-                    valid = (K == 64) ? (x == 0) : ((uint32_t)x == 0);
+                    valid = (K == 64) ? (x == 0) : (K == 32) ? ((uint32_t)x == 0) : ((x & 0xFFFFull) == 0);   // bad bases i .. i+K-1
                 }
                 uint64_t th = 0, tl = 0;
                 if (valid) window_word<W>(sw, il, th, tl);
@@ -359,7 +364,7 @@ int utk_rank_hits(const utk_image *im, const uint8_t *d_bases, const uint64_t *d
     uint32_t blocks = (n_reads + RK_WAVES - 1) / RK_WAVES;
     const uint32_t cap = (uint32_t)n_cu * 8u;                            // 32 wavefronts per CU: dev_image's hit-list bound assumes it
     if (blocks > cap) blocks = cap;
-    return dispatch_img(im, [&](auto w, auto i, auto exc, auto offt) {
+    return dispatch_img_all(im, [&](auto w, auto i, auto exc, auto offt) {   // W = 4: the direct-address table, one load per window
         rank_hits_k<decltype(w)::value, decltype(i)::value, decltype(exc)::value, decltype(offt)>
             <<<dim3(blocks), dim3(256), 0, (hipStream_t)stream>>>(*im, d_bases, d_off, d_len, n_reads, do_rc, *ws);
     });

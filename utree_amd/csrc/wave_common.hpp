@@ -215,9 +215,11 @@ __device__ __forceinline__ void base_code(uint32_t b, uint32_t &code, bool &bad)
 
 // k-mer word of the window that starts at base i, from the big-endian packed 2-bit stream in LDS
 // (word j holds bases 16j..16j+15, base 16j in the top two bits).  itree.c:924: first base most significant.
+// W = 4 (PACKSIZE=16): the 16 bases of x0 alone, in the low 32 bits of klo.
 template <int W> __device__ __forceinline__ void window_word(const uint32_t *sw, uint32_t i, uint64_t &khi, uint64_t &klo) {
     uint32_t j = i >> 4, sh = 32u - ((i & 15u) << 1);          // sh in [2,32]
     uint64_t a = ((uint64_t)sw[j] << 32) | sw[j + 1];
+    if constexpr (W == 4) { khi = 0; klo = (uint32_t)(a >> sh); return; }
     uint64_t b = ((uint64_t)sw[j + 1] << 32) | sw[j + 2];
     uint32_t x0 = (uint32_t)(a >> sh), x1 = (uint32_t)(b >> sh);
     if constexpr (W == 16) {
