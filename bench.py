@@ -3,7 +3,7 @@
 32-mer nodes, 21 844 labels), 150 bp synthetic reads, 160 M reads per GPU by default (10 steps x 16 M-read batches; a
 launch over 16 M reads classifies a read 10-12 % faster than one over 4 M: profiles/r03/batch_sizes.txt, DESIGN_APPENDIX.md section 0.12).
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One process per GPU.  A "step" is one pass of the hot path (reverse-complement staging off, k-mer roller,
@@ -12,7 +12,9 @@ HBM; the database image is resident too.  Reads shard across ranks (each rank ha
 scaling, no data-path collective); the only collective is the one-off RCCL broadcast of the database image
 from rank 0 before the timed region, issued from C (utree_dev_replicate_rank).  Rank 0 prints ONE JSON line.
 
-Extra objects on that line (DESIGN.md sections 6 and 9):
+A plain run does only what that line's headline figure needs: it builds the database and the batches, warms up, times the
+steps, writes --dump-outputs and prints the line.  Everything else it can measure or check runs only with --full, which adds
+these objects to the line (DESIGN.md sections 6 and 9); --no-cpu-baseline, --no-e2e and --no-cli-leg leave single legs out of it:
   roofline      dominant kernel (classify_lanes_k, or classify_short_k / classify_long_k for images it does not take): bytes the kernel must move per launch by the byte model of the image AS
                 BUILT (distinct 128-byte buckets per read, counted on the device) / average launch duration measured with
                 HIP events on the launch stream, against 8 TB/s; next to it the PMC-measured HBM fraction and the VALU / SALU
@@ -22,7 +24,9 @@ Extra objects on that line (DESIGN.md sections 6 and 9):
   cpu_baseline  (N=1 only) the genuine reference binary (and the CPU oracle port) timed on this box's host cores on a
                 bounded sample of the same batches, and a parity check of the GPU results on that sample.
   e2e           (N=1 only) SURVEY section 8(d)'s metric as defined there: database resident -> output file closed, on a FASTA
-                file of the same 40 M reads through utree_search_file (C-ABI), with stage times and parity flags.
+                file of the same 40 M reads through utree_search_file (C-ABI), with stage times and parity flags; at N>1 the
+                per-rank file -> file leg.
+  cli           (N>1, or UTREE_BENCH_CLI_LEG=1) the command line over all the GPUs of the run, timed by rank 0 as a child process.
 """
 import argparse
 import json
@@ -106,6 +110,8 @@ def main():
     ap.add_argument("--share-gpu0", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo --replicate torch)")
     ap.add_argument("--e2e-reads-per-rank", type=int, default=8_000_000, help="N>1: reads of each rank's shard in the file -> file leg")
     ap.add_argument("--no-cli-leg", action="store_true", help="N>1: skip the command-line leg (one process, all GPUs, one input, one output)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: roofline, cpu_baseline, e2e and (N>1) cli")
     ap.add_argument("--make-files", default="", help="(internal) write the bench database as DIR/db.ctr and --e2e-reads reads as DIR/reads.fa, then exit")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write rank 0's results of the last timed step as DIR/results.npy (float64, one row of 6 result "
@@ -124,7 +130,7 @@ def main():
     # rendezvous meanwhile, holding nothing).  UTREE_BENCH_CLI_LEG=1 rehearses it at N = 1.
     cli_leg_result = None
     if ((int(os.environ.get("WORLD_SIZE", "1")) > 1 and int(os.environ.get("RANK", "0")) == 0 and not args.no_cli_leg) or os.environ.get("UTREE_BENCH_CLI_LEG")) \
-            and args.workload == "config" and args.len_dist == "fixed":
+            and args.full and args.workload == "config" and args.len_dist == "fixed":
         import torch as _t
         if _t.cuda.device_count() < 1:                             # (counting devices does not initialise one)
             raise SystemExit("bench.py needs an MI355X (no CPU fallback)")
@@ -172,9 +178,9 @@ def main():
     hit_dense = args.workload == "hit_dense"
     if hit_dense and (world > 1 or var_len or args.kmer != 32):
         raise SystemExit("bench.py --workload hit_dense: one GPU, fixed read length, k = 32")
-    want_cpu = (world == 1 and not args.no_cpu_baseline and not var_len and not hit_dense)
-    want_e2e = (world == 1 and not args.no_e2e and not var_len and not hit_dense)
-    want_e2e_dist = (world > 1 and not args.no_e2e and not var_len)
+    want_cpu = (args.full and world == 1 and not args.no_cpu_baseline and not var_len and not hit_dense)
+    want_e2e = (args.full and world == 1 and not args.no_e2e and not var_len and not hit_dense)
+    want_e2e_dist = (args.full and world > 1 and not args.no_e2e and not var_len)
 
     # ---- database: rank 0 builds the image in HBM, the others receive it by ONE broadcast (RCCL / xGMI) ----
     t0 = time.time()
@@ -273,7 +279,7 @@ def main():
     for i in range(args.warmup):
         step(nb - 1 - (i % nb))
     torch.cuda.synchronize()
-    tree.kernel_time(reset=True)                 # switches the HIP-event bracket of the dominant kernel on
+    tree.kernel_time(reset=True)                 # switches the HIP-event bracket of the dominant kernel on (the roofline's launch time: on with or without --full, so the timed steps are the same)
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
@@ -296,10 +302,6 @@ def main():
     if rank == 0:
         reads_total = world * args.batch_reads * args.steps
         value = reads_total / elapsed
-        avg_launch_s = (k_ms / 1e3) / max(1, k_launches)
-        kernel_sig = tree.kernel_name()
-        roof = roofline(args, tree, batches[0], outs[0], W, avg_launch_s, k_launches, kernel_sig, ulib,
-                        mean_len=(sum(totals) / (len(totals) * args.batch_reads)) if var_len else None)
         nfound = int((outs[(args.steps - 1) % nb][:, 2] > 0).sum().item())
         line = {
             "metric": "reads classified/sec, 8 GB L2 CTR, 150 bp reads",
@@ -316,10 +318,13 @@ def main():
                                       args.steps, args.batch_reads, nb, args.rc),
                        "parallelism": "reads sharded over %d GPU(s), CTR image replicated%s; batches alternate over %d HIP stream(s) per GPU" %
                                       (world, " by %s (%.2f s)" % (bcast_how, bcast_s) if dist_on else "", ns)},
-            "roofline": roof,
             "batch_reads": args.batch_reads, "reads_per_gpu": args.batch_reads * args.steps,
             "db_build_seconds": db_s, "classified_fraction_last_batch": nfound / args.batch_reads,
         }
+        if args.full:
+            # the byte model is counted on the device by a pass of its own over batch 0
+            line["roofline"] = roofline(args, tree, batches[0], outs[0], W, (k_ms / 1e3) / max(1, k_launches), k_launches, tree.kernel_name(), ulib,
+                                        mean_len=(sum(totals) / (len(totals) * args.batch_reads)) if var_len else None)
         if cli_leg_result is not None:
             line["cli"] = cli_leg_result
         if dist_on:

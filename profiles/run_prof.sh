@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 python3 -c "import sys; sys.path.insert(0, '$R'); from utree_amd import lib; print(lib.kernel_source_sha256())" > $OUT/kernel_source_sha256.txt || exit 9
 echo "$*" > $OUT/bench_args.txt
-LEGS="--no-cpu-baseline --no-e2e"
+LEGS="--full --no-cpu-baseline --no-e2e"
 # pass 1: the default bench command (10 steps, 2 warm-up) minus the CPU / file legs, kernel trace + stats
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py $LEGS $* > $OUT/trace.json 2> $OUT/trace.err || exit 1
 # counter passes (each on its own, never together with a trace domain): fewer steps are enough

@@ -9,6 +9,6 @@ for n in "$@"; do
     unset UTREE_AMD_SO
     D=$R
     if [ "$n" = r03 ]; then D=$R/old_r03; elif [ "$n" != main ]; then export UTREE_AMD_SO=$R/utree_amd/libexp_$n.so; fi
-    python3 $D/bench.py --no-cpu-baseline --no-e2e $ARGS 2>/dev/null | python3 -c "$pick" $n "$ARGS"
+    python3 $D/bench.py --full --no-cpu-baseline --no-e2e $ARGS 2>/dev/null | python3 -c "$pick" $n "$ARGS"
 done
 done

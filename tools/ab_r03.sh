@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 pick='import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j["roofline"]; m=r["model"]; print("%-4s %-60s %.4g reads/s  %.3f ms/step  kernel %.3f ms  ovf/read %.3f  %s" % (sys.argv[1], sys.argv[2], j["value"], j["ms_per_step"], r["avg_launch_ms"], m["overflow_buckets_per_read"], j["config"]["workload"].split("image")[1].split(",")[0]))'
 run() { # tag dir args
-    python3 $2/bench.py --no-cpu-baseline --no-e2e $3 2>/dev/null | python3 -c "$pick" $1 "$3"
+    python3 $2/bench.py --full --no-cpu-baseline --no-e2e $3 2>/dev/null | python3 -c "$pick" $1 "$3"
 }
 if [ "$1" = quick ]; then SETS=("--steps 5" "--rc 1 --steps 5");
 elif [ "$1" = rc ]; then SETS=("--rc 1 --steps 5" "--nodes 72000000 --read-len 10000 --rc 1 --batch-reads 400000 --steps 4 --len-dist lognormal --model-reads 1000");

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/bq.sh [bench args]: one bench.py run without the CPU / file legs, the essentials on one line
 R=${GRAFT_REPO_ROOT:-/root/repo}
-python3 $R/bench.py --no-cpu-baseline --no-e2e "$@" 2>/tmp/bq_err.txt | python3 -c '
+python3 $R/bench.py --full --no-cpu-baseline --no-e2e "$@" 2>/tmp/bq_err.txt | python3 -c '
 import json,sys
 t=sys.stdin.read().strip().splitlines()
 if not t: print("NO OUTPUT"); print(open("/tmp/bq_err.txt").read()[-3000:]); sys.exit(1)

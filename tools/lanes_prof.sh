@@ -6,7 +6,7 @@ TAG=$1; shift
 OUT=$R/gpurun_out/lanesprof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-A="--steps 3 --warmup 1 --no-cpu-baseline --no-e2e $*"
+A="--steps 3 --warmup 1 --full --no-cpu-baseline --no-e2e $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -- python3 $R/bench.py $A > $OUT/bt.json 2> $OUT/et.txt || exit 1
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_WAIT_INST_ANY --output-format csv -d $OUT/p1 -- python3 $R/bench.py $A > $OUT/b1.json 2> $OUT/e1.txt || exit 2
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_ANY --output-format csv -d $OUT/p2 -- python3 $R/bench.py $A > $OUT/b2.json 2> $OUT/e2.txt || exit 3
