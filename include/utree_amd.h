@@ -41,12 +41,14 @@ enum {
     UTREE_E_FASTA = 8,       /* malformed read: details in utree_fasta_error (872, 880, 886, 888 -> exit 2)     */
     UTREE_E_RCCL = 9,
     UTREE_E_BUILD = 10,      /* BUILD input rejected: details in utree_build_stats.error_kind                   */
-    UTREE_E_DEVICE = 11      /* a batch's kernels found the workspace too small for it (utree_classify_poll)    */
+    UTREE_E_DEVICE = 11,     /* a batch's kernels found the workspace too small for it (utree_classify_poll)    */
+    UTREE_E_PROFILE = 12     /* the search itself succeeded, its profile was not written: utree_last_hip_error
+                                says why (utree_search_file_profile)                                            */
 };
 
 const char *utree_strerror(int code);
 /* what the calling thread's last UTREE_E_HIP / UTREE_E_DEVICE was: the failing HIP call and the runtime's message for it (no
- * counterpart in the reference, which has no device; "" when there was none) */
+ * counterpart in the reference, which has no device; "" when there was none); after UTREE_E_PROFILE, why the profile was not written */
 const char *utree_last_hip_error(void);
 int utree_abi_version(void);
 
@@ -317,6 +319,52 @@ int utree_rank_search_file(const utree_ctr *ctr, utree_dev *dev, const char *fas
 int utree_rank_search_file_opts(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path,
                                 int do_rc, const utree_rank_params *params, int host_threads, int input_format,
                                 utree_search_stats *stats);
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-taxon read-count profiles (no counterpart in the reference, which writes only the per-read lines).  A read's taxon is the
+ * second column of its output line -- the interpolated taxonomy of the GG search (itree.c:1032, 1040, 1087-1096; it may be empty),
+ * the printed label of the rank-specific one (982, 1002) -- and a read without a line is unclassified.  The counters live on ONE
+ * device; a batch's utree_result records are added by one kernel pass that counts in LDS first.  Entries are
+ * keyed as the records are, (label, cut): cut -2 whole label, -1 empty taxon, >= 0 the label's first `cut` bytes; different keys
+ * that print the same text are merged by utree_profile_write, which also takes entries of several devices.  File layout:
+ *     # reads\t<N>\tclassified\t<G>\tunclassified\t<N-G>\n
+ *     # taxon\tassigned\tclade\n
+ *     <s>\t<assigned>\t<clade>\n   for every assigned taxon and every ';'-prefix of one, in unsigned bytewise order (shorter first)
+ * where `assigned` counts the lines that print exactly s and `clade` the lines whose taxon is s or begins with s + ";".
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct utree_profile utree_profile;
+/* Counters on dev's device for dev's labels.  `truncated_capacity`: slots of the table of truncated taxa (rounded up to a power of
+ * two; 16 B of HBM each) -- keep it at twice the distinct (label, cut >= 0) keys a search can produce.  Whole labels, the empty
+ * taxon and unclassified reads need no slot. */
+int utree_profile_create(utree_dev *dev, uint32_t truncated_capacity, utree_profile **out);
+/* Adds n_reads records (GG or rank-specific) on `stream` (a hipStream_t, NULL = default stream), asynchronously; any number of
+ * streams may add to one profile at the same time. */
+int utree_profile_add(utree_profile *p, const utree_result *d_res, uint32_t n_reads, void *stream);
+/* Zeroes the counters (synchronous: waits for the device first). */
+int utree_profile_reset(utree_profile *p);
+typedef struct { uint32_t label; int32_t cut; uint64_t reads; } utree_profile_entry;
+/* the most entries utree_profile_read can return for p: n_labels + table slots + 1 */
+size_t utree_profile_max_entries(const utree_profile *p);
+/* Synchronous (waits for the device).  Writes up to `cap` entries with reads > 0 into h and their number into *n (UTREE_E_ARG if
+ * that exceeds cap); *n_reads = records added, *n_classified = records that print a line (either may be NULL).  UTREE_E_DEVICE
+ * when the table of truncated taxa was too small for a batch, or a record named a label the database does not have: the counts
+ * are then incomplete. */
+int utree_profile_read(utree_profile *p, utree_profile_entry *h, size_t cap, size_t *n, uint64_t *n_reads, uint64_t *n_classified);
+void utree_profile_free(utree_profile *p);
+/* Host: entries from any number of devices (label indices of ctr) -> merged by text, rolled up, written to `path` in the layout
+ * above; classified = the sum of the entries' reads. */
+int utree_profile_write(const utree_ctr *ctr, const utree_profile_entry *e, size_t n, uint64_t n_reads, const char *path);
+/* utree_search_file_opts / utree_rank_search_file_opts that also write the profile of the search to `profile_path` (NULL: no
+ * profile, no extra launch).  The per-read output and the stats are those of the plain call, and so is the return code of a search
+ * that fails (the profile file is then left as it was).  When the search succeeds but its profile cannot be written -- the file
+ * cannot be created or written, the table of truncated taxa was too small, the devices did not count every read once -- the call
+ * returns UTREE_E_PROFILE and utree_last_hip_error says which.  Each device handle counts its own reads (truncated-taxon slots:
+ * UTREE_PROFILE_CAPACITY, default 2^20). */
+int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
+                              int do_rc, int host_threads, int input_format, const char *profile_path, utree_search_stats *stats);
+int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
+                                   const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
+                                   utree_search_stats *stats);
 
 /* ------------------------------------------------------------------------------------------------
  * `.ubt` -> `.ctr` = XT_cmp32(filename, outfile) (itree.c:1234-1315; `xtree-compress`), SURVEY.md §8(f) rank 2.

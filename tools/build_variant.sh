@@ -15,7 +15,7 @@ for P in 8_2_1_0 8_2_1_1 8_2_2_0 8_4_1_0 8_4_1_1 8_4_2_0 16_2_1_0 16_2_1_1 16_2_
     PARTS="$PARTS /tmp/lanes_part_${P}_$N.o"
 done
 gcc -std=gnu11 -O2 -g -fPIC -fopenmp -I/opt/rocm/include "$@" -c dev_image.c -o /tmp/dev_image_$N.o
-OBJS=$(echo text_kernels.o build_gpu.o ctr_host.o fasta.o search.o search_dev.o rccl_replicate.o compress.o rank.o build.o)
+OBJS=$(echo text_kernels.o profile_kernels.o build_gpu.o ctr_host.o fasta.o search.o search_dev.o rccl_replicate.o compress.o rank.o build.o profile.o)
 if [ -n "$ALL" ]; then
     /opt/rocm/bin/hipcc $HF "$@" -c image_build.hip -o /tmp/image_build_$N.o &
     /opt/rocm/bin/hipcc $HF "$@" -c rank_kernels.hip -o /tmp/rank_kernels_$N.o &

@@ -26,6 +26,7 @@ const char *utree_strerror(int code) {
         case UTREE_E_RCCL: return "RCCL error";
         case UTREE_E_BUILD: return "BUILD input rejected";
         case UTREE_E_DEVICE: return "a kernel found the batch's workspace too small";
+        case UTREE_E_PROFILE: return "the search succeeded but its profile was not written";
         default: return "unknown error";
     }
 }

@@ -32,6 +32,7 @@ void utree_dev_set_hip_error(int err, const char *what) {
     if (getenv("UTREE_DEBUG")) fprintf(stderr, "[utree_amd] HIP error: %s\n", g_hip_msg);
 }
 const char *utree_last_hip_error(void) { return g_hip_msg; }
+void utree_set_error_text(const char *msg) { snprintf(g_hip_msg, sizeof g_hip_msg, "%s", msg); }
 
 #include <time.h>
 static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }

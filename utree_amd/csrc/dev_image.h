@@ -39,6 +39,7 @@ struct utree_dev {
 
 void utree_dev_set_hip_error(int err, const char *what);
 const char *utree_last_hip_error(void);
+void utree_set_error_text(const char *msg);   /* what utree_last_hip_error returns next, for errors that are not HIP's */
 int utree_pick_fine_bits(const utree_ctr *ctr, int fine_bits);
 void utree_search_ctx_free(void *ctx);
 

@@ -15,14 +15,23 @@
  *                           two-lines-per-read framing, bit-compatible)
  *     UTREE_OUTPUT_PARTS=<P> opt-in: the output as P files output.txt.part000 ... (their concatenation is output.txt as the reference writes
  *                           it with one thread); ONE new file fills at ~6 GB/s on a Linux host whatever writes it, P files P times that
+ *     UTREE_PROFILE=<path>  opt-in: also write the sample's per-taxon read counts to <path> (include/utree_amd.h: utree_profile_write;
+ *                           the taxon of a read is the second column of its output line), counted on the GPU while it searches; stdout
+ *                           and the output are those of a run without it.  A path that cannot be opened: a message on stderr, exit 1,
+ *                           before the search (nothing is created there).  A profile that cannot be written after the search (the file,
+ *                           a table too small: UTREE_PROFILE_CAPACITY): the usual stdout, a message on stderr, exit 1.  A search that fails
+ *                           leaves the path as it was.  Unset: no profile, no extra work
  * `threads` sizes the host formatting team (the GPU does the search).  `SPEED` is parsed and ignored, as
  * in the reference (itree.c:858, 907-918).
  */
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
+#include <errno.h>
+#include <fcntl.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 #ifdef _OPENMP
 #include <omp.h>
 #endif
@@ -55,6 +64,18 @@ int main(int argc, char *argv[]) {
     threads = argc >= 5 ? atoi(argv[4]) : 1;
 #endif
     printf("Using up to %d threads.\n", threads);
+
+    const char *profile = getenv("UTREE_PROFILE");
+    if (profile && *profile) {
+        /* can it be opened for writing?  Nothing is created or changed here: a search that fails leaves the path as it was (the file is written
+         * after a successful search) */
+        int pf = open(profile, O_WRONLY | O_CREAT | O_EXCL, 0644);
+        const int created = pf >= 0;
+        if (pf < 0 && errno == EEXIST) pf = open(profile, O_WRONLY);
+        if (pf < 0) { fprintf(stderr, "ERROR: cannot open the profile file %s: %s\n", profile, strerror(errno)); exit(1); }
+        close(pf);
+        if (created) unlink(profile);
+    } else profile = NULL;
 
     utree_ctr *ctr = NULL;
     int rc = utree_ctr_open(argv[1], &ctr);
@@ -123,9 +144,11 @@ int main(int argc, char *argv[]) {
     if (getenv("UTREE_SLACK")) prm.slack = (uint32_t)atoi(getenv("UTREE_SLACK"));
     if (getenv("UTREE_SPARSITY")) prm.sparsity = (uint32_t)atoi(getenv("UTREE_SPARSITY"));
     if (getenv("UTREE_TOLERANCE")) prm.tolerance = (uint32_t)atoi(getenv("UTREE_TOLERANCE"));
-    rc = utree_rank_search_file_opts(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, &st);
+    rc = profile ? utree_rank_search_file_profile(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, &st)
+                 : utree_rank_search_file_opts(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, &st);
 #else
-    rc = utree_search_file_opts(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, &st);
+    rc = profile ? utree_search_file_profile(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, &st)
+                 : utree_search_file_opts(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, &st);
 #endif
     if (rc == UTREE_E_IO) { puts("Invalid input files"); exit(1); }                      /* itree.c:835 */
     if (rc == UTREE_E_FASTA) {
@@ -138,14 +161,15 @@ int main(int argc, char *argv[]) {
         }
         exit(2);
     }
-    if (rc) { fprintf(stderr, "ERROR: %s\n", utree_strerror(rc)); exit(3); }
+    if (rc && rc != UTREE_E_PROFILE) { fprintf(stderr, "ERROR: %s\n", utree_strerror(rc)); exit(3); }
     printf("Good finds: %llu\n", (unsigned long long)st.good_finds);                      /* itree.c:1106 */
     printf("Searched %llu queries\n", (unsigned long long)st.n_reads);                    /* itree.c:1375 */
     fprintf(stderr, "[utree_amd] search %.3f s (%.0f reads/s), GPU batches %.3f s%s\n", st.seconds_total,
             st.seconds_total > 0 ? (double)st.n_reads / st.seconds_total : 0.0, st.seconds_kernels,
             st.pipeline ? " (lane-seconds; framing and formatting on the GPU)" : "");
+    if (rc == UTREE_E_PROFILE) fprintf(stderr, "ERROR: %s\n", utree_last_hip_error());    /* the search and its output are complete; the profile is not */
     for (int i = n_dev - 1; i >= 0; --i) utree_dev_free(devs[i]);
     if (devs[0] != built) utree_dev_free(built);                                          /* UTREE_RCCL_FORCE: devs[0] was a replica */
     utree_ctr_close(ctr);
-    exit(0);
+    exit(rc == UTREE_E_PROFILE ? 1 : 0);
 }

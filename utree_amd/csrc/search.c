@@ -27,6 +27,7 @@
 #include "ctr_host.h"
 #include "dev_image.h"
 #include "search_dev.h"
+#include "profile.h"
 
 #define CHUNK_BYTES ((size_t)96 << 20)        /* must hold two maximal (16 MiB) lines                    */
 #define MAX_READS_PER_BATCH ((size_t)2 << 20)  /* more reads in a chunk (tiny reads) simply take another batch */
@@ -72,6 +73,7 @@ static int slot_alloc(slot_t *s) {
 
 typedef struct {
     utree_dev *dev;
+    utree_profile *prof;                        /* non-NULL: the search writes a profile; this device's reads are counted here */
     hipStream_t stream;
     uint8_t *d_buf; uint64_t *d_off; uint32_t *d_len; utree_result *d_out; void *d_ws; size_t ws_bytes;
 } gpu_ctx;
@@ -227,6 +229,7 @@ static void *gpu_main(void *arg) {
                             : utree_classify_batch(c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
                                                    c->d_out, c->d_ws, c->ws_bytes, c->stream);
             if (e) { set_error(P, e); return NULL; }
+            if (c->prof && (e = utree_profile_add(c->prof, c->d_out, (uint32_t)count, c->stream))) { set_error(P, e); return NULL; }
             HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
         }
         for (size_t g = 0; g < n_dev && nr; ++g) {
@@ -335,7 +338,8 @@ static void free_ctx(gpu_ctx *g) {
 #define HIPM(x) do { if ((x) != hipSuccess) { rc = UTREE_E_HIP; goto done; } } while (0)
 
 static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
-                       int do_rc, const utree_rank_params *rank, int host_threads, int input_format, utree_search_stats *stats) {
+                       int do_rc, const utree_rank_params *rank, int host_threads, int input_format, utree_profile **profs,
+                       utree_search_stats *stats) {
     if (!ctr || !devs || n_dev < 1 || !fasta_path || !out_path || input_format < 0 || input_format > UTREE_INPUT_AUTO) return UTREE_E_ARG;
     int rc = UTREE_OK;
     uint64_t dev_printed = 0;
@@ -345,9 +349,12 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
      * does not take -- malformed records, NUL bytes, lines fgets would split -- and the host framing below then reproduces
      * the reference on it case by case.  UTREE_HOST_TEXT=1 forces the host pipeline (tests, A/B). */
     if (!rank && input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
-        rc = utree_search_file_device(ctr, devs, n_dev, fasta_path, out_path, do_rc, host_threads, stats, &dev_printed, &resume);
+        rc = utree_search_file_device(ctr, devs, n_dev, fasta_path, out_path, do_rc, host_threads, profs, stats, &dev_printed, &resume);
         if (rc != UTREE_RETRY_HOST) return rc;
         rc = UTREE_OK;
+        /* a profile carries the chunks the device pipeline has written when this pipeline continues behind them (resume.fo >= 0), as the
+         * counts do; when it starts the file over, so does the profile */
+        if (profs && resume.fo < 0 && (rc = utree_profiles_reset(profs, n_dev))) return rc;
     }
     double t_start = now_s();
     pipe_t *P = (pipe_t *)calloc(1, sizeof *P);
@@ -396,6 +403,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     for (int g = 0; g < n_dev; ++g) {
         gpu_ctx *c = &P->G[g];
         c->dev = devs[g];
+        c->prof = profs ? profs[g] : NULL;
         HIPM(hipSetDevice(devs[g]->device));
         HIPM(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         HIPM(hipMalloc((void **)&c->d_buf, CHUNK_BYTES + 64));
@@ -452,11 +460,35 @@ done:
 
 int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
                       int do_rc, int host_threads, utree_search_stats *stats) {
-    return search_file(ctr, devs, n_dev, fasta_path, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, stats);
+    return search_file(ctr, devs, n_dev, fasta_path, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, stats);
 }
 int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
                            int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
-    return search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, stats);
+    return search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, NULL, stats);
+}
+
+/* the search with one profile per device handle; the devices' counts are merged into one file when the search has succeeded */
+static int search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
+                               const utree_rank_params *rank, int host_threads, int input_format, const char *profile_path,
+                               utree_search_stats *stats) {
+    if (!profile_path) return search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, rank, host_threads, input_format, NULL, stats);
+    if (!ctr || !devs || n_dev < 1) return UTREE_E_ARG;
+    utree_profile **profs = (utree_profile **)calloc((size_t)n_dev, sizeof *profs);
+    if (!profs) return UTREE_E_NOMEM;
+    utree_search_stats st;
+    memset(&st, 0, sizeof st);
+    int rc = utree_profiles_create(devs, n_dev, profs);
+    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, rank, host_threads, input_format, profs, &st);
+    if (!rc && utree_profiles_write(ctr, profs, n_dev, st.n_reads, profile_path)) rc = UTREE_E_PROFILE;   /* (the search's own codes stay its own) */
+    utree_profiles_free(profs, n_dev);
+    free(profs);
+    if (stats) *stats = st;
+    return rc;
+}
+
+int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
+                              int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
+    return search_file_profile(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, profile_path, stats);
 }
 
 /* XT_doSearch32(utree, in, out, 0, speed, doRC) (itree.c:1376 without DO_GG): the same three-stage pipeline; the
@@ -470,5 +502,13 @@ int utree_rank_search_file_opts(const utree_ctr *ctr, utree_dev *dev, const char
     if (!dev || !params) return UTREE_E_ARG;
     int rc = utree_rank_reset(dev);
     if (rc) return rc;
-    return search_file(ctr, &dev, 1, reads_path, out_path, do_rc, params, host_threads, input_format, stats);
+    return search_file(ctr, &dev, 1, reads_path, out_path, do_rc, params, host_threads, input_format, NULL, stats);
+}
+int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
+                                   const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
+                                   utree_search_stats *stats) {
+    if (!dev || !params) return UTREE_E_ARG;
+    int rc = utree_rank_reset(dev);
+    if (rc) return rc;
+    return search_file_profile(ctr, &dev, 1, reads_path, out_path, do_rc, params, host_threads, input_format, profile_path, stats);
 }

@@ -17,7 +17,7 @@ BUILD_GG_CLI_PATH = os.path.join(_HERE, "utree-buildGG")
 BUILD_CLI_PATH = os.path.join(_HERE, "utree-build")
 _LIB = None
 
-OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE = range(12)
+OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE = range(13)
 BUILD_E_MAP_EMPTY, BUILD_E_MAP, BUILD_E_FASTA, BUILD_E_NO_KMERS, BUILD_E_NAME = range(1, 6)
 FINE_AUTO = -1
 FANOUT_NONE, FANOUT_BROADCAST, FANOUT_UPLOAD = range(3)
@@ -66,6 +66,11 @@ class BuildStats(C.Structure):
 class RankParams(C.Structure):
     """SLACK, SPARSITY, TOLERANCE_THRESHOLD of the rank-specific search (itree.c:952-960)."""
     _fields_ = [("slack", C.c_uint32), ("sparsity", C.c_uint32), ("tolerance", C.c_uint32)]
+
+
+class ProfileEntry(C.Structure):
+    """utree_profile_entry: reads whose line prints (label, cut) -- cut -2 whole label, -1 empty taxon, >= 0 the first cut bytes."""
+    _fields_ = [("label", C.c_uint32), ("cut", C.c_int32), ("reads", C.c_uint64)]
 
 
 class Result(C.Structure):
@@ -135,6 +140,18 @@ SYMBOLS = {
     "utree_search_prepare": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "utree_search_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                     C.POINTER(SearchStats)]),
+    "utree_profile_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "utree_profile_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "utree_profile_reset": (C.c_int, [C.c_void_p]),
+    "utree_profile_max_entries": (C.c_size_t, [C.c_void_p]),
+    "utree_profile_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)]),
+    "utree_profile_free": (None, [C.c_void_p]),
+    "utree_profile_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p]),
+    "utree_search_file_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                            C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
+    "utree_rank_search_file_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RankParams),
+                                                 C.c_int, C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
 }
 
 
@@ -153,7 +170,7 @@ class UtreeError(RuntimeError):
     def __init__(self, code, what=""):
         self.code = code
         msg = load().utree_strerror(code).decode() if _LIB is not None else str(code)
-        if _LIB is not None and code in (4, 5, 11):        # UTREE_E_NOMEM, UTREE_E_HIP, UTREE_E_DEVICE: which call, and what the runtime said
+        if _LIB is not None and code in (4, 5, 11, 12):    # UTREE_E_NOMEM, UTREE_E_HIP, UTREE_E_DEVICE: which call, and what the runtime said; UTREE_E_PROFILE: why
             hip = (_LIB.utree_last_hip_error() or b"").decode(errors="replace")
             if hip:
                 msg += " [" + hip + "]"

@@ -5,6 +5,7 @@
     tree.get_ix(words)               ~ IXTYPE XT_getIX32(UTree*, WTYPE word)             itree.c:720
     tree.classify(bases, off, len)   ~ the per-read body of XT_doSearch32, GG branch     itree.c:891-1088
     search_gg(db, trees, in, out)    ~ size_t XT_doSearch32(utree, in, out, 8, 0, doRC)  itree.c:833
+    tree.profile(capacity)           per-taxon read counts of classified batches (no counterpart in the reference)
 
 torch is used only for device memory and streams (plumbing); every computation happens in the HIP kernels
 behind libutree_amd.so.  Nothing here falls back to the CPU.
@@ -21,6 +22,7 @@ from . import lib as _lib
 RESULT_FIELDS = ("label", "cut", "found", "uix", "sl", "ol")
 RESULT_DTYPE = np.dtype([("label", "<u4"), ("cut", "<i4"), ("found", "<u4"), ("uix", "<u4"), ("sl", "<u4"),
                          ("ol", "<u4")])
+PROFILE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("cut", "<i4"), ("reads", "<u8")])
 
 
 class CtrDB:
@@ -320,6 +322,10 @@ class DeviceTree:
                    "utree_classify_kernel_time")
         return ms.value, n.value
 
+    def profile(self, capacity: int = 1 << 20) -> "Profile":
+        """Per-taxon read counts on this device (utree_profile_create); `capacity` = slots for truncated taxa."""
+        return Profile(self, capacity)
+
     def close(self):
         if self._h:
             _lib.load().utree_dev_free(self._h)
@@ -334,25 +340,94 @@ class DeviceTree:
             pass
 
 
+class Profile:
+    """Per-taxon read counts on one device (utree_profile_*): add() batches of classify / rank_search results, entries() reads
+    them back, write() merges entries by their text and writes the profile file."""
+
+    def __init__(self, tree: DeviceTree, capacity: int = 1 << 20):
+        self.tree = tree
+        h = C.c_void_p()
+        _lib.check(_lib.load().utree_profile_create(tree._h, capacity, C.byref(h)), "utree_profile_create")
+        self._h = h
+
+    def add(self, results, n: Optional[int] = None):
+        """results: the int32 [n, 6] CUDA tensor of classify() / rank_search(); asynchronous on torch's current stream."""
+        import torch
+        if not (isinstance(results, torch.Tensor) and results.dtype == torch.int32 and results.dim() == 2 and results.shape[1] == 6
+                and results.is_contiguous() and results.is_cuda and results.device.index == self.tree.info.device):
+            raise ValueError("Profile.add: results must be a contiguous int32 [n, 6] tensor on cuda:%d" % self.tree.info.device)
+        n = results.shape[0] if n is None else n
+        if not 0 <= n <= results.shape[0]:
+            raise ValueError("Profile.add: n = %d outside the %d records given" % (n, results.shape[0]))
+        stream = torch.cuda.current_stream(results.device).cuda_stream
+        _lib.check(_lib.load().utree_profile_add(self._h, results.data_ptr(), n, stream), "utree_profile_add")
+
+    def reset(self):
+        _lib.check(_lib.load().utree_profile_reset(self._h), "utree_profile_reset")
+
+    def entries(self):
+        """(entries, n_reads, n_classified): entries a numpy array of PROFILE_ENTRY_DTYPE (label, cut, reads).  Raises
+        UtreeError(E_DEVICE) when the table of truncated taxa was too small."""
+        L = _lib.load()
+        cap = L.utree_profile_max_entries(self._h)
+        buf = np.zeros(cap, dtype=PROFILE_ENTRY_DTYPE)
+        n = C.c_size_t(0)
+        nr = C.c_uint64(0)
+        nc = C.c_uint64(0)
+        _lib.check(L.utree_profile_read(self._h, buf.ctypes.data, cap, C.byref(n), C.byref(nr), C.byref(nc)), "utree_profile_read")
+        return buf[:n.value].copy(), nr.value, nc.value
+
+    def write(self, path: str):
+        e, nr, _ = self.entries()
+        write_profile(self.tree.db, e, nr, path)
+
+    def close(self):
+        if self._h:
+            _lib.load().utree_profile_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_profile(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
+    """utree_profile_write: entries (PROFILE_ENTRY_DTYPE, from any number of devices) merged by text, rolled up, written."""
+    e = np.ascontiguousarray(entries, dtype=PROFILE_ENTRY_DTYPE)
+    _lib.check(_lib.load().utree_profile_write(db._h, e.ctypes.data if len(e) else None, len(e), n_reads, path.encode()),
+               "utree_profile_write")
+
+
 def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: bool = False, threads: int = 0,
-              input_format: int = _lib.INPUT_REFERENCE):
+              input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
-    FASTA / gzip input."""
+    FASTA / gzip input.  profile: also write the per-taxon read counts there (utree_search_file_profile)."""
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     st = _lib.SearchStats()
-    code = _lib.load().utree_search_file_opts(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads,
-                                              input_format, C.byref(st))
+    if profile is not None:
+        code = _lib.load().utree_search_file_profile(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads,
+                                                     input_format, profile.encode(), C.byref(st))
+    else:
+        code = _lib.load().utree_search_file_opts(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads,
+                                                  input_format, C.byref(st))
     return code, st
 
 
 def search_rank(db: CtrDB, tree: DeviceTree, fasta: str, out: str, rc: bool = False, slack: int = 2, sparsity: int = 4,
-                tolerance: int = 2, threads: int = 0, input_format: int = _lib.INPUT_REFERENCE):
-    """XT_doSearch32(utree, in, out, 0, speed, doRC): the `xtree-search` binary (itree.c:1376 without DO_GG)."""
+                tolerance: int = 2, threads: int = 0, input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None):
+    """XT_doSearch32(utree, in, out, 0, speed, doRC): the `xtree-search` binary (itree.c:1376 without DO_GG).  profile: as
+    search_gg's."""
     st = _lib.SearchStats()
     prm = _lib.RankParams(slack, sparsity, tolerance)
-    code = _lib.load().utree_rank_search_file_opts(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm),
-                                                   threads, input_format, C.byref(st))
+    if profile is not None:
+        code = _lib.load().utree_rank_search_file_profile(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm),
+                                                          threads, input_format, profile.encode(), C.byref(st))
+    else:
+        code = _lib.load().utree_rank_search_file_opts(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm),
+                                                       threads, input_format, C.byref(st))
     return code, st
 
 
