@@ -4,7 +4,7 @@
 # their runs end in a SEGV under ASan's allocator (hostile labels through xtree-search; PACKSIZE=16 tables with duplicate / non-monotone bins):
 # undefined behaviour in the reference, whose unsanitised answers the goldens hold -- not findings in this tree.
 set -e
-R=/root/repo
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 mkdir -p /tmp/asan
 cd $R/utree_amd/csrc
 SF="-fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g -std=gnu11 -fPIC -fopenmp -I/opt/rocm/include"

@@ -75,7 +75,7 @@ static double pois_tail_nodes(double lam, uint32_t cap) {
     s = 1.0 - s / lam;
     return s < 0 ? 0 : s;
 }
-/* UTREE_CANON_MODE 1: only every other hash value is some canonical 16-mer's, so a pair of `v` = 2^24 / nb hash values holds Binomial(v, 1/2)
+/* Only every other hash value is some canonical 16-mer's (device_common.hpp: canon_of), so a pair of `v` = 2^24 / nb hash values holds Binomial(v, 1/2)
  * occupied ones, each with Poisson(lam1) nodes per bucket -- lumps: the share of the region's nodes in overflowing buckets */
 static double lumpy_overflow(double nb, double expect, uint32_t cap) {
     const double v = 16777216.0 / nb, lam1 = expect / 16777216.0;
@@ -107,7 +107,7 @@ static int sub_slices_on(uint32_t W, uint32_t F) {
 static uint64_t compute_regions_sub(uint64_t n_nodes, uint32_t W, uint32_t I, uint32_t bucket_words, uint32_t F, int sub_on, uint64_t regions[256]) {
     /* (image version 11: the region table counts PAIRS of buckets -- the two orientations of a canonical 16-mer --, a pair is sized for
      * 2 TARGET nodes) */
-    const double m = (UTREE_CANON_MODE == 2 ? 2.0 : 1.0) * (4.0 * W - 15.0 - 2.0 * UTREE_MIN_MARGIN(W));   /* mode 2: the smallest of 2 (K - 15) hashes */
+    const double m = 4.0 * W - 15.0 - 2.0 * UTREE_MIN_MARGIN(W);     /* the hash is the smallest of this many (a window's candidate 16-mers) */
     const uint32_t cap_entries = bucket_words / utree_rec_words(W, I);
     const char *te = getenv("UTREE_BUCKET_TARGET");                     /* nodes per bucket; experiments only */
     const double target = te && atof(te) > 0 ? atof(te) : (bucket_words == 16 ? 0.5625 : 0.375) * cap_entries;
@@ -122,14 +122,14 @@ static uint64_t compute_regions_sub(uint64_t n_nodes, uint32_t W, uint32_t I, ui
         uint64_t nb = want >= (double)nb_max ? nb_max : (uint64_t)want, sub = 1;
         if (nb < nb_min) nb = nb_min;
         if (nb > nb_max) nb = nb_max;
-        /* mode 1: more pairs where a pair holds so few hash values that the occupied ones make lumps: up to the overflow share the design
-         * load has without them (times `slack`), at most one pair per value */
-        if (UTREE_CANON_MODE != 2 && slack > 0)
+        /* more pairs where a pair holds so few hash values that the occupied ones make lumps: up to the overflow share the design load has
+         * without them (times `slack`), at most one pair per value */
+        if (slack > 0)
             while (nb < nb_max && lumpy_overflow((double)nb, expect, cap_entries) > slack * p0 + 1e-4) { nb += nb / 20 + 1; if (nb > nb_max) nb = nb_max; }
-        /* ... and beyond one slot per value (k = 64): an occupied value -- every other one in mode 1 -- has expect / 2^23 nodes, half of them per
+        /* ... and beyond one slot per value (k = 64): an occupied value -- every other one -- has expect / 2^23 nodes, half of them per
          * orientation, spread over the slot's pairs by the 256 combinations of four bases; the fullest pair gets ceil(256 / sub) of them */
         if (sub_on && nb == (1ull << 24)) {
-            const double per_value = expect / 16777216.0 * (UTREE_CANON_MODE == 2 ? 0.5 : 1.0);   /* nodes per occupied value and orientation */
+            const double per_value = expect / 16777216.0;                   /* nodes per occupied value and orientation */
             while (sub < 256 && pois_tail_nodes(per_value * ceil(256.0 / (double)sub) / 256.0, cap_entries) > slack * p0 + 1e-4) ++sub;
         }
         /* test hook: that many pairs per slot in every region (the addressing does not need a slot to be one hash value) */

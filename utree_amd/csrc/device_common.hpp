@@ -143,17 +143,15 @@ __host__ __device__ __forceinline__ uint32_t rc16(uint32_t m) {
     const uint32_t y = __builtin_bitreverse32(m);
     return ~(((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1));
 }
-// The strand-independent hash of a 16-mer m with reverse complement r (UTREE_CANON_MODE, utree_internal.h) and its orientation bit: 1 when the
-// hash is the reverse complement's.  of: as view f has it (0 for a 16-mer that is its own reverse complement), og: as view g has it (1).
+// The strand-independent hash of a 16-mer m with reverse complement r and its orientation bit: 1 when the hash is the reverse complement's.
+// It is the hash of the canonical form, the smaller of m and r: three vector instructions per base of a read on top of the forward walk, but
+// only every other hash value is some canonical 16-mer's -- where the table has a pair of buckets per hash value (the dense end of the range)
+// every other pair stays empty, and regions of a few values per pair are sized for the lumps (dev_image.c: lumpy_overflow).  (The smaller of
+// the two 16-mers' hashes, every value in use, costs a second hash per base and measured 3-6 % slower: DESIGN.md section 3.)
+// of: as view f has it (0 for a 16-mer that is its own reverse complement), og: as view g has it (1).
 __host__ __device__ __forceinline__ uint32_t canon_of(uint32_t m, uint32_t r, uint32_t &of, uint32_t &og) {
-#if UTREE_CANON_MODE == 2
-    const uint32_t hf = mix32(m), hr = mix32(r);
-    of = hr < hf ? 1u : 0u; og = hr <= hf ? 1u : 0u;
-    return hr < hf ? hr : hf;
-#else
     of = m > r ? 1u : 0u; og = m >= r ? 1u : 0u;
     return mix32(m > r ? r : m);
-#endif
 }
 __host__ __device__ __forceinline__ uint32_t canon_hash(uint32_t m, uint32_t &o) {
     uint32_t og;
@@ -161,12 +159,7 @@ __host__ __device__ __forceinline__ uint32_t canon_hash(uint32_t m, uint32_t &o)
 }
 // the hash alone (the search kernels' walk has m and r rolling)
 __host__ __device__ __forceinline__ uint32_t canon_key(uint32_t m, uint32_t r) {
-#if UTREE_CANON_MODE == 2
-    const uint32_t hf = mix32(m), hr = mix32(r);
-    return hr < hf ? hr : hf;
-#else
     return mix32(m > r ? r : m);
-#endif
 }
 // 16-mers are ordered by their hash WITHOUT its MIN_LOW_BITS low bits (leftmost on ties): the search kernels then fit
 // { hash bits | position in the tile } into 32 bits and slide the minimum with one v_min_u32 per step.  The bucket is still

@@ -131,9 +131,10 @@ struct RegionLds { const uint64_t *reg; uint64_t table; uint32_t bshift; };   //
 // One wave looks up the windows [w0, w0+n) of a staged buffer (lb / sw = packed bases, sbad = bad-base bit words, both
 // indexed from the buffer's first base; w0 a multiple of 64) and hands every lane's result to on_rank(rank) -- called by all
 // lanes, INVALID for lanes without a hit -- once per 64 windows.  One bucket (64 bytes) is in flight per lane: its records
-// arrive in one round trip, and two buckets in flight would not fit the registers.  CHECKBAD = false: the caller knows the
-// windows hold no bad base (most reads), and the per-window test disappears.
-template <int W, int I, bool EXC, typename OFF, uint32_t TILE, bool CHECKBAD, bool PAIRS, typename HitFn>
+// arrive in one round trip.  (Two rounds' buckets in flight, one memory wait per 128 windows, took 16 more registers -- 7
+// instead of 8 waves per SIMD -- and measured 5 % slower, same-box.)  CHECKBAD = false: the caller knows the windows hold no
+// bad base (most reads), and the per-window test disappears.
+template <int W, int I, bool EXC, typename OFF, uint32_t TILE, bool CHECKBAD, typename HitFn>
 __device__ __forceinline__ void wave_scan_windows(const utk_image &im, const LaneBits &lb, const uint64_t *sbad, uint64_t *Kk,
                                                   uint32_t w0, uint32_t n, const RegionLds &rg, uint32_t lane, HitFn &&on_rank PH_ARG) {
     constexpr uint32_t K = 4 * W;
@@ -165,9 +166,6 @@ __device__ __forceinline__ void wave_scan_windows(const utk_image &im, const Lan
         const uint32_t *st = lb.swl + ((w0 + wb) >> 4);                      // the tile's first word, per lane
         build_minkeys<W, TILE>(st, lb.sh, Kl, Hl, Ob, tn + K - 16, lane);   // 16-mers of windows w0+wb .. w0+wb+tn-1
         TICK(2);
-#if defined(UTREE_ABLATE) && UTREE_ABLATE == 2
-        continue;
-#endif
         // A round = 64 windows, lane l taking window it*64 + l of the tile.  locate(): the bucket (and the key bits that go with
         // it) of the lane's window in round `it`; resolve(): the rank its bucket holds for the window.
         auto locate = [&](uint32_t it, uint64_t &baddr, uint32_t &tag) {
@@ -188,11 +186,7 @@ __device__ __forceinline__ void wave_scan_windows(const utk_image &im, const Lan
                 const uint32_t sub = (uint32_t)(re >> UTREE_REGION_NB_BITS) & ((1u << UTREE_REGION_SUB_BITS) - 1u);
                 bl = bl * sub + ((ext_canon((uint32_t)((v >> 32) & 0xF0u) | (uint32_t)(v & 0xFu), o) * sub) >> 8);
             }
-#ifdef UTREE_ABLATE_L2
-            baddr = rg.table + ((uint64_t)(bl & 0x1FFFu) << rg.bshift);     // timing experiment: every bucket inside 1 MB (L2 hits), answers wrong
-#else
             baddr = rg.table + ((2u * ((re >> UTREE_REGION_BASE_SHIFT) + bl) + o) << rg.bshift);
-#endif
             tag = ((h & 0xFFu) << 6) | pos;                                 // hash bits the bucket does not imply | position (< 64)
         };
         auto resolve = [&](uint32_t it, const Bucket<W, I> &bk, uint64_t baddr, uint32_t tag) -> uint32_t {
@@ -223,39 +217,19 @@ __device__ __forceinline__ void wave_scan_windows(const utk_image &im, const Lan
             }
             return ok;
         };
-        // PAIRS: two rounds' buckets are requested together -- one memory wait per 128 windows instead of two -- at the price of
-        // 16 more registers (7 instead of 8 waves per SIMD).  Otherwise one bucket is in flight per lane.
-        constexpr uint32_t STEP = PAIRS ? 2 : 1;
-        for (uint32_t it = 0; it * 64 < tn; it += STEP) {
-            const uint32_t left0 = tn - it * 64, left1 = left0 > 64 ? left0 - 64 : 0;
-            const bool ok0 = window_ok(it, left0);
-            uint64_t a0 = 0; uint32_t t0 = 0;
-            Bucket<W, I> bk0;
-            if (ok0) { locate(it, a0, t0); bk0 = load_bucket_at<W, I>(a0); }
+        for (uint32_t it = 0; it * 64 < tn; ++it) {
+            const bool ok = window_ok(it, tn - it * 64);
+            uint64_t baddr = 0; uint32_t tag = 0;
+            Bucket<W, I> bk;
+            if (ok) { locate(it, baddr, tag); bk = load_bucket_at<W, I>(baddr); }
             TICK(3);
-            if constexpr (PAIRS) {
-                const bool ok1 = left1 && window_ok(it + 1, left1);
-                uint64_t a1 = 0; uint32_t t1 = 0;
-                Bucket<W, I> bk1;
-                if (ok1) { locate(it + 1, a1, t1); bk1 = load_bucket_at<W, I>(a1); }
-                PH_WAITVM;
-                TICK(4);
-                uint32_t rank0 = INVALID, rank1 = INVALID;
-                if (ok0) rank0 = resolve(it, bk0, a0, t0);
-                if (ok1) rank1 = resolve(it + 1, bk1, a1, t1);
-                TICK(5);
-                on_rank(rank0);                                              // itree.c:929-931
-                if (left1) on_rank(rank1);
-                TICK(6);
-            } else {
-                PH_WAITVM;
-                TICK(4);
-                uint32_t rank0 = INVALID;
-                if (ok0) rank0 = resolve(it, bk0, a0, t0);
-                TICK(5);
-                on_rank(rank0);                                              // itree.c:929-931
-                TICK(6);
-            }
+            PH_WAITVM;
+            TICK(4);
+            uint32_t rank = INVALID;
+            if (ok) rank = resolve(it, bk, baddr, tag);
+            TICK(5);
+            on_rank(rank);                                                // itree.c:929-931
+            TICK(6);
         }
         wave_lds_fence();
     }
@@ -404,29 +378,24 @@ constexpr int SHORT_CAP = UTREE_SHORT_CAP;          // 150 bp + reverse strand f
 constexpr int SHORT2_CAP = UTREE_SHORT2_CAP;        // 300 bp + reverse strand fits (used when a batch's longest read needs it)
 constexpr int MID_CAP = UTREE_MID_CAP;              // 1 kb + reverse strand fits; longer reads take classify_long_k
 constexpr int WAVES_PER_BLOCK = 4;
-#ifndef UTREE_WORK_GRAB
-#define UTREE_WORK_GRAB 32
-#endif
-constexpr uint32_t WORK_GRAB = UTREE_WORK_GRAB;                   // reads a wave takes per visit to a work counter (16: +0.3 %, 64: +2 %, 128: +7 % time)
+constexpr uint32_t WORK_GRAB = 32;                                // reads a wave takes per visit to a work counter (16: +0.3 %, 64: +2 %, 128: +7 % time)
 constexpr uint32_t TALLY_CHUNK = UTREE_TALLY_CHUNK;
 constexpr uint32_t TALLY_DIRECT = UTREE_TALLY_CHUNK / 16;   // hit lists this long get their own reservation
 constexpr int32_t CUT_PENDING = -3;                 // result.cut while a read waits for vote_k
 constexpr int32_t RANK_PENDING = -4;                // one distinct label: result.label holds its RANK until vote_k looks up the
                                                     // label index (a dependent load classify_short_k would otherwise wait for)
 
-// 8 waves/SIMD for u16-label databases measured faster than 5 even with a few spilled dwords (k = 32: +4 % in r01;
+// SHORT_MIN_WAVES: 8 waves/SIMD for u16-label databases measured faster than 5 even with a few spilled dwords (k = 32: +4 % in r01;
 // k = 64: 932 -> 1020 M reads/s, same-box); with u32 labels the hit list's LDS caps the occupancy at 5-6 anyway.  (Voting inside this kernel, 64 parked reads per
 // wave, was tried and measured slower at every occupancy: 295-331 vs 343 M reads/s with the separate vote_k.)
 // CAP = staged bases a wavefront's LDS slice holds.  CAP = SHORT_CAP walks all reads of the batch and routes the
 // longer ones to the mid / long lists; CAP = MID_CAP (LISTED) walks the mid list.  Its 37 KB of LDS per
 // workgroup allow 4 workgroups per CU, so it may use 128 VGPRs.
+constexpr int SHORT_MIN_WAVES = 8;
 template <int W, int I, bool EXC, typename OFF, int CAP, bool LISTED, int RCMODE = 2>   // RCMODE 0 / 1: strand handling known at compile time
-#ifndef UTREE_SHORT_MIN_WAVES
-#define UTREE_SHORT_MIN_WAVES 8
-#endif
 // (80 scalar registers at 8 waves per SIMD: the surplus sits in the lanes of a vector register, one v_readlane per use; lifting the
 // cap with amdgpu_waves_per_eu(1, 8) removes those and costs the eighth wave -- measured 9 % slower)
-__global__ __launch_bounds__(256, CAP > SHORT2_CAP ? (I == 2 ? 4 : 3) : (I == 2 ? UTREE_SHORT_MIN_WAVES : 5))
+__global__ __launch_bounds__(256, CAP > SHORT2_CAP ? (I == 2 ? 4 : 3) : (I == 2 ? SHORT_MIN_WAVES : 5))
 void classify_short_k(utk_image im, const uint8_t *__restrict__ bases, const uint64_t *__restrict__ off,
                       const uint32_t *__restrict__ len, uint32_t n_reads, int do_rc_arg, utree_result *__restrict__ out,
                       utk_workspace ws) {
@@ -442,13 +411,6 @@ void classify_short_k(utk_image im, const uint8_t *__restrict__ bases, const uin
     __shared__ HIT s_hits[WAVES_PER_BLOCK][CAP];
     // a 150 bp read with its reverse strand (270 windows) is two tiles of 256 instead of three of 128
     constexpr uint32_t TILE = CAP <= SHORT_CAP ? 256u : KEY_TILE;
-    // two rounds' buckets in flight at once (one memory wait per 128 windows): 16 more registers, 7 waves per SIMD -- measured
-    // 5 % slower than one bucket at 8 waves (same-box, round 2); -DUTREE_PAIRS builds it for comparison
-#ifdef UTREE_PAIRS
-    constexpr bool PAIRS = CAP <= SHORT2_CAP && I == 2;
-#else
-    constexpr bool PAIRS = false;
-#endif
     __shared__ uint64_t s_keys[WAVES_PER_BLOCK][TILE + 128];
     __shared__ uint64_t s_reg[256];
     // the mid-length pass has no room for a raw buffer of its own and less to gain: its raw bytes pass through the hit
@@ -639,8 +601,7 @@ void classify_short_k(utk_image im, const uint8_t *__restrict__ bases, const uin
         if (total64 <= (uint64_t)CAP) {
             const uint32_t total = (uint32_t)total64;
             uint32_t F = 0;
-#if !(defined(UTREE_ABLATE) && UTREE_ABLATE == 1)            /* ablation builds (profiles/run_pmc_variants.sh): 1 = staging only, */
-            if (total >= K) {                                      /* 2 = + sliding minimizers, 3 = + window lookups, no tally        */
+            if (total >= K) {
                 // ---- windows: lane l takes windows l, l+64, ... (itree.c:906-933) ----
                 auto on_rank = [&](uint32_t rank) {
                     const bool hit = rank != INVALID;
@@ -650,20 +611,15 @@ void classify_short_k(utk_image im, const uint8_t *__restrict__ bases, const uin
                 };
                 // a read without any bad base (most) takes the loop without the per-window test; with both strands staged the
                 // separator is one, so that instantiation only has the tested loop
-                if constexpr (RCMODE == 1) wave_scan_windows<W, I, EXC, OFF, TILE, true, PAIRS>(im, lb, sbad, Kk, 0u, total - K + 1, rg, lane, on_rank PH_PASS);
-                else if (!bad_cur) wave_scan_windows<W, I, EXC, OFF, TILE, false, PAIRS>(im, lb, sbad, Kk, 0u, total - K + 1, rg, lane, on_rank PH_PASS);
-                else wave_scan_windows<W, I, EXC, OFF, TILE, true, PAIRS>(im, lb, sbad, Kk, 0u, total - K + 1, rg, lane, on_rank PH_PASS);
+                if constexpr (RCMODE == 1) wave_scan_windows<W, I, EXC, OFF, TILE, true>(im, lb, sbad, Kk, 0u, total - K + 1, rg, lane, on_rank PH_PASS);
+                else if (!bad_cur) wave_scan_windows<W, I, EXC, OFF, TILE, false>(im, lb, sbad, Kk, 0u, total - K + 1, rg, lane, on_rank PH_PASS);
+                else wave_scan_windows<W, I, EXC, OFF, TILE, true>(im, lb, sbad, Kk, 0u, total - K + 1, rg, lane, on_rank PH_PASS);
                 wave_lds_fence();
             }
-#endif
             TICK(9);
             if (stage_next) bad_next = stage(o_next, L_next);   // sw / sbad now belong to the next read; hits[] to this one
             TICK(7);
-#if defined(UTREE_ABLATE)
-            if (lane == 0) store_result(&out[r], sw[0] + hits[0], -2, F, 0, 0, 0);
-#else
             finish(r, F);                                  // F == 0 (no window: no hit, no output line) included
-#endif
             TICK(8);
         } else if (stage_next) bad_next = stage(o_next, L_next);
         r = r_next; L = L_next; o = o_next; bad_cur = bad_next;
@@ -762,7 +718,7 @@ __global__ __launch_bounds__(LONG_THREADS, EXC ? 5 : 8) void classify_long_k(utk
             const uint32_t a = wv * PER_WAVE < tile_n ? wv * PER_WAVE : tile_n;
             const uint32_t b = a + PER_WAVE < tile_n ? a + PER_WAVE : tile_n;
             PH_DECL
-            wave_scan_windows<W, I, EXC, OFF, KEY_TILE, true, false>(im, lb, s_bad, s_keys[wv], a, b - a, rg, lane, [&](uint32_t rank) {
+            wave_scan_windows<W, I, EXC, OFF, KEY_TILE, true>(im, lb, s_bad, s_keys[wv], a, b - a, rg, lane, [&](uint32_t rank) {
                 // one atomic per DISTINCT label of the 64 windows, not per hit: a read's hits mostly share a few labels,
                 // and 64 atomics on one address serialise in L2
                 const bool hit = rank != INVALID;
@@ -987,11 +943,7 @@ __device__ __forceinline__ void vote_table(const utk_image &im, utree_result *ou
 
 // vote_table_k: vote_k for images with the label table (a kernel of its own: with both in one, the byte scans' registers cost the table path
 // three of its eight wavefronts per SIMD)
-#ifdef UTREE_VOTE_WPE8
-__attribute__((amdgpu_waves_per_eu(8, 8)))
-#endif
 __global__ __launch_bounds__(256) void vote_table_k(utk_image im, utree_result *__restrict__ out, utk_workspace ws, uint32_t n_reads) {
-#ifndef UTREE_VOTE_UNSORTED
     // The vote is a per-lane state machine: a wavefront executes the union of its lanes' paths, and a read of two labels takes a fraction of
     // the steps a read of four takes.  The workgroup's 256 reads are therefore dealt out again by what they need: reads of two labels fill the
     // workgroup's lanes from the bottom, reads of more from the top (the two kinds meet in one wavefront at most); a read of one label or none
@@ -1023,19 +975,6 @@ __global__ __launch_bounds__(256) void vote_table_k(utk_image im, utree_result *
     const uint32_t who = s_who[tid];
     if (who == 0xFFFFu) return;
     const uint32_t r = blockIdx.x * blockDim.x + who;
-#else
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_reads) return;
-    {
-        const uint32_t *res = (const uint32_t *)&out[r];
-        if ((int32_t)res[1] == RANK_PENDING) {             // one distinct label: only its file-order index is missing
-            uint32_t *o = (uint32_t *)&out[r];
-            o[0] = im.rank2ix[res[0]]; o[1] = (uint32_t)-2;
-            return;
-        }
-        if ((int32_t)res[1] != CUT_PENDING) return;        // finished by the classify kernel (no hit, or classify_long_k)
-    }
-#endif
     const uint32_t *res = (const uint32_t *)&out[r];
     vote_table(im, &out[r], ws.tally + ((uint64_t)res[4] | ((uint64_t)res[5] << 32)), res[2], res[3]);
 }

@@ -24,7 +24,7 @@
 // the read's reverse complement takes phases A and B a second time in the same slot.  The hits a read gets are the same
 // (window, record) pairs classify_short_k finds: it asks, per window, which entry of the minimizer's bucket carries the window's
 // key {hash bits, position, outer bases}; this kernel asks, per entry, which window of the run has that key.  Reads this kernel
-// does not finish -- two or more bases other than ACGTacgt, more distinct labels than LANES_TSLOTS, a wave whose run list is full -- go on the
+// does not finish -- two or more bases other than ACGTacgt, more distinct labels than TSLOTS, a wave whose run list is full -- go on the
 // batch's list for the wave-per-read kernel (utk_classify_listed), which also remains the kernel for u32 labels, irregular tables,
 // longer reads and databases whose reads hit in most windows (DESIGN.md sections 5c, 11).
 #include <hip/hip_runtime.h>
@@ -35,19 +35,6 @@
 #include "wave_common.hpp"
 
 using namespace utk;
-
-#ifndef UTREE_LANES_WAVES
-#define UTREE_LANES_WAVES 4
-#endif
-#ifndef UTREE_LANES_WPS
-#define UTREE_LANES_WPS 3                             /* wavefronts per SIMD the kernel is compiled for (LDS allows 12 per CU) */
-#endif
-#ifndef UTREE_LANES_WPS64
-#define UTREE_LANES_WPS64 3                           /* ... its k = 64 instantiation (same-box: 2 per SIMD 1.66 ms, 3 per SIMD 1.41 ms per 4 M reads) */
-#endif
-#ifndef UTREE_LANES_TSLOTS
-#define UTREE_LANES_TSLOTS 12                         /* distinct labels a read's tally table holds */
-#endif
 
 namespace {
 
@@ -60,7 +47,9 @@ __device__ unsigned long long g_lphase[8];
 #define LT(i)
 #endif
 
-constexpr int LANES_WAVES = UTREE_LANES_WAVES;        // waves per workgroup
+constexpr int LANES_WAVES = 4;                        // waves per workgroup
+constexpr int LANES_WPS = 3;                          // wavefronts per SIMD the kernel is compiled for (LDS allows 12 per CU; k = 64,
+                                                      // same-box: 2 per SIMD 1.66 ms, 3 per SIMD 1.41 ms per 4 M reads)
 constexpr uint32_t LCAP = UTREE_LANES_CAP;            // bases a lane's slot holds
 constexpr uint32_t NWORD = LCAP / 16;                 // stream words with data
 static_assert(LCAP % 32 == 0, "slot geometry");
@@ -75,7 +64,7 @@ template <int W> struct Geo {
     static constexpr uint32_t DNONE = 63;                              // minimizer offset no run has (<= 48)
     static_assert((STRIDE & 1) == 1, "slot geometry");
 };
-constexpr uint32_t TSLOTS = UTREE_LANES_TSLOTS;       // distinct labels per read this kernel keeps count of
+constexpr uint32_t TSLOTS = 12;                       // distinct labels per read this kernel keeps count of
 constexpr uint32_t T_EMPTY = 0xFFFFFFFFu;             // an unused slot of a tally table (rank 0xFFFF is no label's)
 constexpr int32_t CUT_PENDING = -3, RANK_PENDING = -4;   // as in kernels.hip (vote_k finishes those results)
 
@@ -387,11 +376,7 @@ _Pragma("unroll") \
                 irregular(m16, NB * (b + 1u) + (OFS + NB - 1u)); \
                 A[NB - 1] = CKEY() | (NB * (b + 1u) + (OFS + NB - 1u)); \
             }
-#ifdef UTREE_LANES_NOCLEAN
-            const bool clean = false;
-#else
             const bool clean = ballot64(badpos < 0xFFFF0000u || nwin != nwin_u) == 0ull;
-#endif
             if (clean) { PHASE_A_BLOCKS(true) } else { PHASE_A_BLOCKS(false) }
 #undef PHASE_A_BLOCKS
 #undef ROLL16
@@ -554,11 +539,9 @@ _Pragma("unroll") \
                     if (((om >> lane) & 1ull) && at >= ovf_room) { const uint32_t rd = q >> SEGSH; atomicOr(&full[rd >> 5], 1u << (rd & 31u)); }
                     if (((om >> lane) & 1ull) && at < ovf_room) {
                         runs[at] = (first + d) | (first << 8) | ((first + lenm1 + 1u) << 16) | (q << 24) | (rev ? 0x80000000u : 0u);   // (bit 31: the strand)
-#ifndef UTREE_LANES_REFETCH_DESC
                         // (the descriptor is in this lane's registers: the first 64 of a grab's overflowing runs keep it, and the
                         // overflow stage's first round starts without the trip that fetches it again)
                         if (at < 64u) ost[at] = (W == 8 && I == 4) ? (((uint64_t)Pk.y << 32) | Pk.x) : (((uint64_t)Pk.w << 32) | Pk.z);
-#endif
                     }
                     n_ovf = umin(n_ovf + (uint32_t)__popcll(om), ovf_room);
                 }
@@ -633,12 +616,9 @@ _Pragma("unroll") \
         // (descriptor, records) however many windows the run has.  A long one (a minimizer shared by the k-mers of many related
         // genomes) is searched per window by bisection like the wave-per-read kernel does (wave_common.hpp: min_find), one lane per
         // WINDOW and OVF_WAYS windows per lane at a time: the searches' dependent loads overlap. ----
-#ifndef UTREE_LANES_OVF_WAYS
-#define UTREE_LANES_OVF_WAYS 4
-#endif
         // (the threshold is the image's: 32 records, 16 for a database most of whose nodes sit in overflow runs -- related genomes --, where
         // same-box 16 is 3.5 % faster and 64 or more 12-20 % slower; UTREE_OVF_SCAN overrides)
-        constexpr uint32_t OVF_WAYS = UTREE_LANES_OVF_WAYS;
+        constexpr uint32_t OVF_WAYS = 4;
         const uint32_t OVF_SCAN = im.ovf_scan;
         const bool OVF_CHAINS = W == 8 && (im.flags & UTREE_F_OVF_CHAINS) != 0u;      // heavy runs are lists of chains (device_common.hpp)
         // the descriptor of overflowing run i: the key word of its bucket's last entry (a line phase B has fetched: an L2 hit mostly)
@@ -661,12 +641,8 @@ _Pragma("unroll") \
             uint32_t nrec = 0, wn = 0;                                             // records to scan / windows to search of the lane's item
             // round 0's descriptors were kept by the scans that found the runs; every later round's were requested during the round
             // before it: no round waits for them
-#ifdef UTREE_LANES_REFETCH_DESC
-            uint64_t dsc = fetch_desc(i);
-#else
             uint64_t dsc = ib == 0u ? ost[lane] : dsc_next;
             if (ib + 64u < n_ovf) dsc_next = fetch_desc(i + 64u);
-#endif
             if (i < n_ovf) {
                 const uint32_t rec = runs[i];
                 const uint64_t n = ovf_count(dsc);
@@ -979,7 +955,7 @@ _Pragma("unroll") for (uint32_t x = 0; x < NA; ++x) { A[x] = RA[x]; B[x] = RB[x]
 #define LANES_LDS s_stream[wv], s_runs[wv], s_tab[wv], s_full[wv], s_pref[wv], s_ost[wv], s_reg, wv
 
 template <int W, int I, int SEGS, bool IRR, int MODE, int NL, bool BS>
-__global__ __launch_bounds__(LANES_WAVES * 64, W == 16 ? UTREE_LANES_WPS64 : UTREE_LANES_WPS)
+__global__ __launch_bounds__(LANES_WAVES * 64, LANES_WPS)
 void classify_lanes_k(utk_image im, const uint8_t *__restrict__ bases, const uint64_t *__restrict__ off, const uint32_t *__restrict__ len,
                       uint32_t n_reads, int do_rc, utree_result *__restrict__ out, utk_workspace ws, uint32_t cls) {
     LANES_PROLOGUE(W)
@@ -994,7 +970,7 @@ void classify_lanes_k(utk_image im, const uint8_t *__restrict__ bases, const uin
 // (the bodies are inlined: called as functions -- one register allocation each -- their LDS pointers become generic ones and every LDS access a flat
 // one: 1.87 x the time, profiles/r04/mixed_one_launch_called_16M.json; inlined five times over, the hot body spills 70-90 registers and is still the faster)
 template <int W, int I, bool IRR, int NL, bool BS>
-__global__ __launch_bounds__(LANES_WAVES * 64, W == 16 ? UTREE_LANES_WPS64 : UTREE_LANES_WPS)
+__global__ __launch_bounds__(LANES_WAVES * 64, LANES_WPS)
 void classify_lanes_mixed_k(utk_image im, const uint8_t *__restrict__ bases, const uint64_t *__restrict__ off, const uint32_t *__restrict__ len,
                             uint32_t n_reads, int do_rc, utree_result *__restrict__ out, utk_workspace ws, uint32_t max_cls) {
     LANES_PROLOGUE(W)
@@ -1005,9 +981,9 @@ void classify_lanes_mixed_k(utk_image im, const uint8_t *__restrict__ bases, con
     if (max_cls >= 4u) lanes_body<W, I, 16, IRR, 1, NL, BS>(im, bases, off, len, n_reads, do_rc, out, ws, 4u, LANES_LDS);
 }
 
-static inline uint32_t lanes_resident_blocks(int W, int n_cu) {
-    const uint32_t wps = W == 16 ? UTREE_LANES_WPS64 : UTREE_LANES_WPS;
-    return (uint32_t)n_cu * (4u * wps / LANES_WAVES > 0 ? 4u * wps / LANES_WAVES : 1u);
+static inline uint32_t lanes_resident_blocks(int n_cu) {
+    static_assert(4 * LANES_WPS >= LANES_WAVES, "a CU holds at least one workgroup");
+    return (uint32_t)n_cu * (4u * LANES_WPS / LANES_WAVES);
 }
 
 template <int W, int I, int SEGS, bool IRR, int MODE, int NL, bool BS = false>
@@ -1015,7 +991,7 @@ static int launch_lanes(const utk_image *im, const uint8_t *d_bases, const uint6
                         int do_rc, utree_result *d_out, const utk_workspace *ws, int n_cu, void *stream, uint32_t cls = 0) {
     static_assert(NL == 1 || NL == 2, "bucket size");
     uint32_t blocks = (n_reads + (64u / SEGS) * LANES_WAVES - 1) / ((64u / SEGS) * LANES_WAVES);
-    const uint32_t cap = lanes_resident_blocks(W, n_cu);
+    const uint32_t cap = lanes_resident_blocks(n_cu);
     if (blocks > cap) blocks = cap;
     classify_lanes_k<W, I, SEGS, IRR, MODE, NL, BS><<<dim3(blocks), dim3(LANES_WAVES * 64), 0, (hipStream_t)stream>>>(*im, d_bases, d_off, d_len, n_reads, do_rc, d_out, *ws, cls);
     return (int)hipGetLastError();
@@ -1026,7 +1002,7 @@ static int launch_lanes_mixed(const utk_image *im, const uint8_t *d_bases, const
                               int do_rc, utree_result *d_out, const utk_workspace *ws, int n_cu, void *stream, uint32_t max_cls) {
     // (the classes' read counts are on the device: the grid is what the batch's reads of one lane could fill, at most the resident one)
     uint32_t blocks = (n_reads + 64u * LANES_WAVES - 1) / (64u * LANES_WAVES);
-    const uint32_t cap = lanes_resident_blocks(W, n_cu);
+    const uint32_t cap = lanes_resident_blocks(n_cu);
     if (blocks > cap) blocks = cap;
     classify_lanes_mixed_k<W, I, IRR, NL, BS><<<dim3(blocks), dim3(LANES_WAVES * 64), 0, (hipStream_t)stream>>>(*im, d_bases, d_off, d_len, n_reads, do_rc, d_out, *ws, max_cls);
     return (int)hipGetLastError();

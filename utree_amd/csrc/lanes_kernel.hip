@@ -11,10 +11,6 @@
 
 using namespace utk;
 
-#ifndef UTREE_LANES_WAVES
-#define UTREE_LANES_WAVES 4
-#endif
-
 extern "C" {
 #define PART_DECL(W_, I_, NL_, BS_) int utk_lanes_part_##W_##_##I_##_##NL_##_##BS_(int segs, int irr, int mode, const utk_image *im, const uint8_t *d_bases, const uint64_t *d_off, \
                                                                               const uint32_t *d_len, uint32_t n_reads, int do_rc, utree_result *d_out, const utk_workspace *ws, \

@@ -14,14 +14,6 @@ extern "C" {
 #define UTREE_IMG_MAGIC 0x31474d4945525455ull    /* "UTREIMG1" */
 #define UTREE_IMG_HEADER_BYTES 4096u
 #define UTREE_IMG_VERSION 14u                    /* 9: buckets of 64 or 128 bytes; any number of buckets per hash region; 10: the vote records carry the file-order index; 11: canonical minimizers, strand-paired buckets; 12: heavy overflow runs start with a position directory; 13: k = 64: minimizers keep two bases' distance from the k-mer's ends and those four bases split a hash value's pair of buckets (UTREE_MIN_MARGIN, sub-slices); 14: k = 32: heavy overflow runs are stored as CHAINS of consecutive k-mers (UTREE_F_OVF_CHAINS) */
-/* How a 16-mer gets its strand-independent rank and address (image version 11, device_common.hpp):
- *   1: the hash of its canonical form, the smaller of the 16-mer and its reverse complement -- three vector instructions per base of a read
- *      on top of the forward walk, but only every other hash value is some canonical 16-mer's: where the table has a pair of buckets per
- *      hash value (the dense end of the range) every other pair stays empty, and regions of a few values per pair must be sized for the lumps
- *   2: the smaller of the two hashes -- a second hash per base (seven instructions), every value in use, the table as small as before */
-#ifndef UTREE_CANON_MODE
-#define UTREE_CANON_MODE 1
-#endif
 #define UTREE_REGION_NB_BITS 25                  /* regions[r] = base_r << 34 | sub_r << 25 | nb_r (nb_r <= 2^24 slots of hash values, each of sub_r <= 256 pairs) */
 #define UTREE_REGION_SUB_BITS 9
 #define UTREE_REGION_BASE_SHIFT (UTREE_REGION_NB_BITS + UTREE_REGION_SUB_BITS)
