@@ -42,13 +42,15 @@ enum {
     UTREE_E_RCCL = 9,
     UTREE_E_BUILD = 10,      /* BUILD input rejected: details in utree_build_stats.error_kind                   */
     UTREE_E_DEVICE = 11,     /* a batch's kernels found the workspace too small for it (utree_classify_poll)    */
-    UTREE_E_PROFILE = 12     /* the search itself succeeded, its profile was not written: utree_last_hip_error
+    UTREE_E_PROFILE = 12,    /* the search itself succeeded, its profile was not written: utree_last_hip_error
                                 says why (utree_search_file_profile)                                            */
+    UTREE_E_COVERAGE = 13    /* ... its coverage file was not written (utree_search_file_coverage)              */
 };
 
 const char *utree_strerror(int code);
 /* what the calling thread's last UTREE_E_HIP / UTREE_E_DEVICE was: the failing HIP call and the runtime's message for it (no
- * counterpart in the reference, which has no device; "" when there was none); after UTREE_E_PROFILE, why the profile was not written */
+ * counterpart in the reference, which has no device; "" when there was none); after UTREE_E_PROFILE / UTREE_E_COVERAGE, why the
+ * file was not written */
 const char *utree_last_hip_error(void);
 int utree_abi_version(void);
 
@@ -365,6 +367,52 @@ int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev,
 int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
                                    const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
                                    utree_search_stats *stats);
+
+/* ------------------------------------------------------------------------------------------------
+ * Distinct database k-mers covered per taxon (no counterpart in itree.c; the idea of KrakenUniq's and xtree's coverage reports).  A read
+ * count alone does not say whether ten thousand reads pile up on forty k-mers or spread over forty thousand.  For the GG search's windows
+ * (itree.c:903-927; with RC the read's and its reverse complement's), a window is a HIT when XT_getIX32 (720-730, 699-707) ends on a record
+ * whose stored label index is < n_labels (929); the hit's NODE is that record's position in the dump.  Per label l:
+ *     db_kmers[l]  records of the dump whose stored index is l (reachable or not)
+ *     hits[l]      hit windows with label l, every occurrence
+ *     covered[l]   distinct nodes among them            (covered <= db_kmers and covered <= hits, always)
+ * The image cannot name a node (a k-mer may be stored there twice, in an overflow run or in a chain), so a coverage handle keeps the .ctr's
+ * bin table and node dump in file order in HBM itself, plus one bit per node and one counter per label: utree_coverage_bytes -- for 1.2 G
+ * 32-mers 8.5 GB of records, 64 MB of bin table and a 152 MB bitmap per device, next to the image.  File layout:
+ *     # reads\t<N>\thits\t<H>\tcovered\t<D>\tdb_kmers\t<T>\n
+ *     # taxon\tdb_kmers\tcovered\thits\tclade_db_kmers\tclade_covered\tclade_hits\n
+ *     <s>\t...\n    for every label text with hits > 0 and every ';'-prefix of one, in unsigned bytewise order (shorter first)
+ * The first three figures are those of the label(s) whose text is exactly s, the clade_ figures sum over ALL labels of the database, hit or
+ * not, whose text is s or begins with s + ";".  The rank-specific search examines a hit-dependent subset of windows and has no coverage.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct utree_coverage utree_coverage;
+/* bytes of HBM a coverage handle for ctr takes */
+size_t utree_coverage_bytes(const utree_ctr *ctr);
+/* A handle on dev's device.  d_binix / d_records: the raw on-disk pieces in HBM as for utree_dev_build (they are copied; the caller keeps
+ * its own), or both NULL to stream the dump from the .ctr file / the host copy as utree_dev_upload does. */
+int utree_coverage_create(const utree_ctr *ctr, utree_dev *dev, const void *d_binix, const void *d_records, utree_coverage **out);
+/* Adds the reads of a batch, given as utree_classify_batch takes them, on `stream` (a hipStream_t, NULL = default stream), asynchronously;
+ * any number of streams may add to one handle at the same time.  Reads of any length; shorter than k or empty ones count as reads. */
+int utree_coverage_add(utree_coverage *c, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads, int do_rc,
+                       void *stream);
+/* Clears bitmap and counters (synchronous: waits for the device first). */
+int utree_coverage_reset(utree_coverage *c);
+/* dst += src: bitmaps OR-ed, hit counters and reads added (synchronous; the handles may be on different devices, same database) */
+int utree_coverage_merge(utree_coverage *dst, utree_coverage *src);
+typedef struct { uint32_t label, pad; uint64_t db_kmers, covered, hits; } utree_coverage_entry;
+/* Synchronous: one streaming pass over dump and bitmap, then ONE entry per label (index order; cap >= n_labels, else UTREE_E_ARG with
+ * *n = n_labels); *n_reads = reads added, *n_hits = the sum of the entries' hits (either may be NULL). */
+int utree_coverage_read(utree_coverage *c, utree_coverage_entry *h, size_t cap, size_t *n, uint64_t *n_reads, uint64_t *n_hits);
+void utree_coverage_free(utree_coverage *c);
+/* Host only: entries (label indices of ctr; several with one label are added up) -> merged by text, rolled up, written to `path`. */
+int utree_coverage_write(const utree_ctr *ctr, const utree_coverage_entry *e, size_t n, uint64_t n_reads, const char *path);
+/* utree_search_file_profile that also writes the coverage of the search to `coverage_path` (NULL: exactly utree_search_file_profile -- no
+ * handle, no launch).  One coverage handle per device handle, merged before the file is written.  A search that succeeds but whose coverage
+ * cannot be written returns UTREE_E_COVERAGE (utree_last_hip_error says why; a profile that failed too keeps UTREE_E_PROFILE); a search that
+ * fails leaves the path as it was. */
+int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
+                               int host_threads, int input_format, const char *profile_path, const char *coverage_path,
+                               utree_search_stats *stats);
 
 /* ------------------------------------------------------------------------------------------------
  * `.ubt` -> `.ctr` = XT_cmp32(filename, outfile) (itree.c:1234-1315; `xtree-compress`), SURVEY.md §8(f) rank 2.

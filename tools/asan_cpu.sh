@@ -8,8 +8,8 @@ R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 mkdir -p /tmp/asan
 cd $R/utree_amd/csrc
 SF="-fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g -std=gnu11 -fPIC -fopenmp -I/opt/rocm/include"
-for f in ctr_host dev_image fasta search search_dev rccl_replicate compress rank build profile; do gcc $SF -c $f.c -o /tmp/asan/$f.o; done
-HIPO=$(ls kernels.o lanes_kernel.o lanes_part_*.o rank_kernels.o text_kernels.o profile_kernels.o build_gpu.o image_build.o)
+for f in ctr_host dev_image fasta search search_dev rccl_replicate compress rank build profile coverage; do gcc $SF -c $f.c -o /tmp/asan/$f.o; done
+HIPO=$(ls kernels.o lanes_kernel.o lanes_part_*.o rank_kernels.o text_kernels.o profile_kernels.o coverage_kernels.o build_gpu.o image_build.o)
 gcc -shared -fopenmp -fsanitize=address,undefined -o /tmp/asan/libutree_amd_asan.so $HIPO /tmp/asan/*.o -L/opt/rocm/lib -lamdhip64 -lrccl -lstdc++ -lz -lm -lpthread -Wl,-rpath,/opt/rocm/lib
 cd $R/oracle
 gcc -O1 -g -std=gnu11 -fopenmp -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer -shared -o /tmp/asan/liboracle.so utree_oracle.c utree_build_oracle.c
@@ -18,7 +18,7 @@ cp /tmp/asan/liboracle.so liboracle.so
 trap "cp /tmp/asan/liboracle_plain.so $R/oracle/liboracle.so" EXIT
 cd $R
 LD_PRELOAD="$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so)" ASAN_OPTIONS=detect_leaks=0:halt_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 \
-    UTREE_AMD_SO=/tmp/asan/libutree_amd_asan.so python -m pytest tests/test_host_cpu.py tests/test_profile_cpu.py tests/test_oracle_golden.py tests/test_dist_gloo.py -q -m "not gpu" > /tmp/asan/tests.log 2>&1 || true
+    UTREE_AMD_SO=/tmp/asan/libutree_amd_asan.so python -m pytest tests/test_host_cpu.py tests/test_profile_cpu.py tests/test_coverage_cpu.py tests/test_oracle_golden.py tests/test_dist_gloo.py -q -m "not gpu" > /tmp/asan/tests.log 2>&1 || true
 tail -6 /tmp/asan/tests.log
 echo "sanitizer reports outside oracle/_ref:"
 grep -n "runtime error" /tmp/asan/tests.log || true

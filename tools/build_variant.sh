@@ -20,6 +20,6 @@ for P in 8_2_1_0 8_2_1_1 8_2_2_0 8_4_1_0 8_4_1_1 8_4_2_0 16_2_1_0 16_2_1_1 16_2_
 done
 gcc -std=gnu11 -O2 -g -fPIC -fopenmp -I/opt/rocm/include "$@" -c dev_image.c -o "$O/dev_image.o"
 for p in $PIDS; do wait $p; done
-OBJS="text_kernels.o profile_kernels.o build_gpu.o image_build.o rank_kernels.o ctr_host.o fasta.o search.o search_dev.o rccl_replicate.o compress.o rank.o build.o profile.o"
+OBJS="text_kernels.o profile_kernels.o coverage_kernels.o build_gpu.o image_build.o rank_kernels.o ctr_host.o fasta.o search.o search_dev.o rccl_replicate.o compress.o rank.o build.o profile.o"
 gcc -shared -fopenmp -o ../libexp_$N.so "$O/kernels.o" "$O/lanes_kernel.o" $PARTS "$O/dev_image.o" $OBJS -L/opt/rocm/lib -lamdhip64 -lrccl -lstdc++ -lz -lm -lpthread -Wl,-rpath,/opt/rocm/lib
 echo built libexp_$N.so

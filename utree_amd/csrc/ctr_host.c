@@ -27,6 +27,7 @@ const char *utree_strerror(int code) {
         case UTREE_E_BUILD: return "BUILD input rejected";
         case UTREE_E_DEVICE: return "a kernel found the batch's workspace too small";
         case UTREE_E_PROFILE: return "the search succeeded but its profile was not written";
+        case UTREE_E_COVERAGE: return "the search succeeded but its coverage file was not written";
         default: return "unknown error";
     }
 }

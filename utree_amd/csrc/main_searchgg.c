@@ -21,6 +21,10 @@
  *                           before the search (nothing is created there).  A profile that cannot be written after the search (the file,
  *                           a table too small: UTREE_PROFILE_CAPACITY): the usual stdout, a message on stderr, exit 1.  A search that fails
  *                           leaves the path as it was.  Unset: no profile, no extra work
+ *     UTREE_COVERAGE=<path> opt-in, xtree-searchGG only (xtree-search ignores it): also write, per taxon, the k-mers the database holds, the
+ *                           DISTINCT ones the sample hit and the hits (include/utree_amd.h: utree_coverage_write), collected on the GPU
+ *                           while it searches; needs the node dump a second time in HBM (utree_coverage_bytes).  Path checks, failures and
+ *                           exit codes as for UTREE_PROFILE, with which it may be combined.  Unset: nothing of it runs
  * `threads` sizes the host formatting team (the GPU does the search).  `SPEED` is parsed and ignored, as
  * in the reference (itree.c:858, 907-918).
  */
@@ -76,6 +80,15 @@ int main(int argc, char *argv[]) {
         close(pf);
         if (created) unlink(profile);
     } else profile = NULL;
+    const char *coverage = DO_GG ? getenv("UTREE_COVERAGE") : NULL;
+    if (coverage && *coverage) {                                                          /* the same check, the same promise */
+        int cf = open(coverage, O_WRONLY | O_CREAT | O_EXCL, 0644);
+        const int created = cf >= 0;
+        if (cf < 0 && errno == EEXIST) cf = open(coverage, O_WRONLY);
+        if (cf < 0) { fprintf(stderr, "ERROR: cannot open the coverage file %s: %s\n", coverage, strerror(errno)); exit(1); }
+        close(cf);
+        if (created) unlink(coverage);
+    } else coverage = NULL;
 
     utree_ctr *ctr = NULL;
     int rc = utree_ctr_open(argv[1], &ctr);
@@ -147,8 +160,9 @@ int main(int argc, char *argv[]) {
     rc = profile ? utree_rank_search_file_profile(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, &st)
                  : utree_rank_search_file_opts(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, &st);
 #else
-    rc = profile ? utree_search_file_profile(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, &st)
-                 : utree_search_file_opts(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, &st);
+    rc = coverage ? utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st)
+         : profile ? utree_search_file_profile(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, &st)
+                   : utree_search_file_opts(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, &st);
 #endif
     if (rc == UTREE_E_IO) { puts("Invalid input files"); exit(1); }                      /* itree.c:835 */
     if (rc == UTREE_E_FASTA) {
@@ -161,15 +175,15 @@ int main(int argc, char *argv[]) {
         }
         exit(2);
     }
-    if (rc && rc != UTREE_E_PROFILE) { fprintf(stderr, "ERROR: %s\n", utree_strerror(rc)); exit(3); }
+    if (rc && rc != UTREE_E_PROFILE && rc != UTREE_E_COVERAGE) { fprintf(stderr, "ERROR: %s\n", utree_strerror(rc)); exit(3); }
     printf("Good finds: %llu\n", (unsigned long long)st.good_finds);                      /* itree.c:1106 */
     printf("Searched %llu queries\n", (unsigned long long)st.n_reads);                    /* itree.c:1375 */
     fprintf(stderr, "[utree_amd] search %.3f s (%.0f reads/s), GPU batches %.3f s%s\n", st.seconds_total,
             st.seconds_total > 0 ? (double)st.n_reads / st.seconds_total : 0.0, st.seconds_kernels,
             st.pipeline ? " (lane-seconds; framing and formatting on the GPU)" : "");
-    if (rc == UTREE_E_PROFILE) fprintf(stderr, "ERROR: %s\n", utree_last_hip_error());    /* the search and its output are complete; the profile is not */
+    if (rc == UTREE_E_PROFILE || rc == UTREE_E_COVERAGE) fprintf(stderr, "ERROR: %s\n", utree_last_hip_error());    /* the search and its output are complete; the profile / coverage file is not */
     for (int i = n_dev - 1; i >= 0; --i) utree_dev_free(devs[i]);
     if (devs[0] != built) utree_dev_free(built);                                          /* UTREE_RCCL_FORCE: devs[0] was a replica */
     utree_ctr_close(ctr);
-    exit(rc == UTREE_E_PROFILE ? 1 : 0);
+    exit(rc == UTREE_E_PROFILE || rc == UTREE_E_COVERAGE ? 1 : 0);
 }

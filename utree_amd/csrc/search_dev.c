@@ -182,6 +182,7 @@ typedef struct {
     dpipe *P;
     utree_dev *dev;
     utree_profile *prof;                        /* non-NULL: this device's profile of the search                   */
+    utree_coverage *cov;                        /* non-NULL: this device's coverage handle                         */
     lane_buf *b;
     int read_threads;
     pthread_t th;
@@ -416,6 +417,8 @@ static void *lane_main(void *arg) {
         pthread_mutex_unlock(&P->mu);
         /* the chunk is committed (published chunks are never dropped): its records go into the profile, on this lane's stream behind the vote */
         if (L->prof && nr) { int pe = utree_profile_add(L->prof, b->d_res, nr, b->stream); if (pe) { dfail(P, pe); return NULL; } }
+        /* ... and its reads into the coverage: d_in, d_seq_off and d_seq_len still hold the chunk */
+        if (L->cov && nr) { int ce = utree_coverage_add(L->cov, b->d_in, b->d_seq_off, b->d_seq_len, nr, P->do_rc, b->stream); if (ce) { dfail(P, ce); return NULL; } }
         double t4 = now_s();
         L->t_wait += t4 - t3;
         LH(hipStreamSynchronize(b->stream));
@@ -475,8 +478,8 @@ int utree_search_prepare(const utree_ctr *ctr, utree_dev **devs, int n_dev, int 
 }
 
 int utree_search_file_device(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
-                             int do_rc, int host_threads, utree_profile **profs, utree_search_stats *stats, uint64_t *progress_printed,
-                             utree_search_resume *resume) {
+                             int do_rc, int host_threads, utree_profile **profs, utree_coverage **covs, utree_search_stats *stats,
+                             uint64_t *progress_printed, utree_search_resume *resume) {
     const double t_start = now_s();
     if (progress_printed) *progress_printed = 0;
     if (resume) { memset(resume, 0, sizeof *resume); resume->fo = -1; }
@@ -530,6 +533,7 @@ int utree_search_file_device(const utree_ctr *ctr, utree_dev **devs, int n_dev, 
         int started = 0;
         for (int i = 0; i < n_lanes; ++i) {                                       /* lane i: device i % n_dev, so consecutive chunks go to different GPUs */
             lanes[i].P = P; lanes[i].dev = devs[i % n_dev]; lanes[i].prof = profs ? profs[i % n_dev] : NULL;
+            lanes[i].cov = covs ? covs[i % n_dev] : NULL;
             lanes[i].b = &((struct utree_search_ctx *)devs[i % n_dev]->search_ctx)->lane[i / n_dev];
             lanes[i].read_threads = per_lane;
             if (i == 0) { P->lane0 = &lanes[0]; P->lanes_alive = n_lanes; }

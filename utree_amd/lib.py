@@ -17,7 +17,7 @@ BUILD_GG_CLI_PATH = os.path.join(_HERE, "utree-buildGG")
 BUILD_CLI_PATH = os.path.join(_HERE, "utree-build")
 _LIB = None
 
-OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE = range(13)
+OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE = range(14)
 BUILD_E_MAP_EMPTY, BUILD_E_MAP, BUILD_E_FASTA, BUILD_E_NO_KMERS, BUILD_E_NAME = range(1, 6)
 FINE_AUTO = -1
 FANOUT_NONE, FANOUT_BROADCAST, FANOUT_UPLOAD = range(3)
@@ -71,6 +71,11 @@ class RankParams(C.Structure):
 class ProfileEntry(C.Structure):
     """utree_profile_entry: reads whose line prints (label, cut) -- cut -2 whole label, -1 empty taxon, >= 0 the first cut bytes."""
     _fields_ = [("label", C.c_uint32), ("cut", C.c_int32), ("reads", C.c_uint64)]
+
+
+class CoverageEntry(C.Structure):
+    """utree_coverage_entry: per label, the records the dump holds, the distinct ones hit, the hits."""
+    _fields_ = [("label", C.c_uint32), ("pad", C.c_uint32), ("db_kmers", C.c_uint64), ("covered", C.c_uint64), ("hits", C.c_uint64)]
 
 
 class Result(C.Structure):
@@ -150,6 +155,17 @@ SYMBOLS = {
     "utree_profile_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p]),
     "utree_search_file_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                             C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
+    "utree_coverage_bytes": (C.c_size_t, [C.c_void_p]),
+    "utree_coverage_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "utree_coverage_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "utree_coverage_reset": (C.c_int, [C.c_void_p]),
+    "utree_coverage_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "utree_coverage_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64)]),
+    "utree_coverage_free": (None, [C.c_void_p]),
+    "utree_coverage_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p]),
+    "utree_search_file_coverage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                             C.c_int, C.c_char_p, C.c_char_p, C.POINTER(SearchStats)]),
     "utree_rank_search_file_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RankParams),
                                                  C.c_int, C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
 }
@@ -170,7 +186,7 @@ class UtreeError(RuntimeError):
     def __init__(self, code, what=""):
         self.code = code
         msg = load().utree_strerror(code).decode() if _LIB is not None else str(code)
-        if _LIB is not None and code in (4, 5, 11, 12):    # UTREE_E_NOMEM, UTREE_E_HIP, UTREE_E_DEVICE: which call, and what the runtime said; UTREE_E_PROFILE: why
+        if _LIB is not None and code in (4, 5, 11, 12, 13):    # UTREE_E_NOMEM, UTREE_E_HIP, UTREE_E_DEVICE: which call, and what the runtime said; UTREE_E_PROFILE / UTREE_E_COVERAGE: why
             hip = (_LIB.utree_last_hip_error() or b"").decode(errors="replace")
             if hip:
                 msg += " [" + hip + "]"

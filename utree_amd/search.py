@@ -6,6 +6,7 @@
     tree.classify(bases, off, len)   ~ the per-read body of XT_doSearch32, GG branch     itree.c:891-1088
     search_gg(db, trees, in, out)    ~ size_t XT_doSearch32(utree, in, out, 8, 0, doRC)  itree.c:833
     tree.profile(capacity)           per-taxon read counts of classified batches (no counterpart in the reference)
+    tree.coverage()                  per-taxon database k-mers, distinct ones hit, hits (no counterpart in the reference)
 
 torch is used only for device memory and streams (plumbing); every computation happens in the HIP kernels
 behind libutree_amd.so.  Nothing here falls back to the CPU.
@@ -23,6 +24,7 @@ RESULT_FIELDS = ("label", "cut", "found", "uix", "sl", "ol")
 RESULT_DTYPE = np.dtype([("label", "<u4"), ("cut", "<i4"), ("found", "<u4"), ("uix", "<u4"), ("sl", "<u4"),
                          ("ol", "<u4")])
 PROFILE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("cut", "<i4"), ("reads", "<u8")])
+COVERAGE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("pad", "<u4"), ("db_kmers", "<u8"), ("covered", "<u8"), ("hits", "<u8")])
 
 
 class CtrDB:
@@ -326,6 +328,11 @@ class DeviceTree:
         """Per-taxon read counts on this device (utree_profile_create); `capacity` = slots for truncated taxa."""
         return Profile(self, capacity)
 
+    def coverage(self, d_binix=None, d_records=None) -> "Coverage":
+        """A coverage handle on this device (utree_coverage_create).  d_binix / d_records: torch uint8 CUDA tensors with the on-disk
+        bin table and node dump (they are copied), or neither to stream the dump from the .ctr / the host copy."""
+        return Coverage(self, d_binix, d_records)
+
     def close(self):
         if self._h:
             _lib.load().utree_dev_free(self._h)
@@ -400,14 +407,92 @@ def write_profile(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
                "utree_profile_write")
 
 
+class Coverage:
+    """Which database k-mers a sample touched, on one device (utree_coverage_*): add() batches of reads as classify() takes them,
+    entries() reads back one (label, db_kmers, covered, hits) entry per label, write() writes the coverage file."""
+
+    def __init__(self, tree: DeviceTree, d_binix=None, d_records=None):
+        if (d_binix is None) != (d_records is None):
+            raise ValueError("Coverage: give both d_binix and d_records, or neither")
+        self.tree = tree
+        h = C.c_void_p()
+        _lib.check(_lib.load().utree_coverage_create(tree.db._h, tree._h, d_binix.data_ptr() if d_binix is not None else None,
+                                                     d_records.data_ptr() if d_records is not None else None, C.byref(h)),
+                   "utree_coverage_create")
+        self._h = h
+
+    @staticmethod
+    def bytes_needed(db: CtrDB) -> int:
+        return _lib.load().utree_coverage_bytes(db._h)
+
+    def add(self, bases, off, length, rc: bool = False):
+        """bases: uint8 CUDA tensor; off: int64; length: int32 (as DeviceTree.classify).  Asynchronous on torch's current stream."""
+        import torch
+        dev = self.tree.info.device
+        for t, dt in ((bases, torch.uint8), (off, torch.int64), (length, torch.int32)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.is_cuda and t.device.index == dev):
+                raise ValueError("Coverage.add: bases / off / length must be contiguous uint8 / int64 / int32 tensors on cuda:%d" % dev)
+        if off.numel() != length.numel():
+            raise ValueError("Coverage.add: %d offsets, %d lengths" % (off.numel(), length.numel()))
+        stream = torch.cuda.current_stream(bases.device).cuda_stream
+        _lib.check(_lib.load().utree_coverage_add(self._h, bases.data_ptr(), off.data_ptr(), length.data_ptr(), off.numel(), int(rc),
+                                                  stream), "utree_coverage_add")
+
+    def reset(self):
+        _lib.check(_lib.load().utree_coverage_reset(self._h), "utree_coverage_reset")
+
+    def merge(self, other: "Coverage"):
+        """self += other (bitmaps OR-ed, counters added); the handles may be on different devices."""
+        _lib.check(_lib.load().utree_coverage_merge(self._h, other._h), "utree_coverage_merge")
+
+    def entries(self):
+        """(entries, n_reads, n_hits): entries a numpy array of COVERAGE_ENTRY_DTYPE, one per label in index order."""
+        L = _lib.load()
+        cap = self.tree.db.info.n_labels
+        buf = np.zeros(cap, dtype=COVERAGE_ENTRY_DTYPE)
+        n = C.c_size_t(0)
+        nr = C.c_uint64(0)
+        nh = C.c_uint64(0)
+        _lib.check(L.utree_coverage_read(self._h, buf.ctypes.data if cap else None, cap, C.byref(n), C.byref(nr), C.byref(nh)),
+                   "utree_coverage_read")
+        return buf[:n.value].copy(), nr.value, nh.value
+
+    def write(self, path: str):
+        e, nr, _ = self.entries()
+        write_coverage(self.tree.db, e, nr, path)
+
+    def close(self):
+        if self._h:
+            _lib.load().utree_coverage_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_coverage(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
+    """utree_coverage_write: entries (COVERAGE_ENTRY_DTYPE; all labels of the database) merged by text, rolled up, written."""
+    e = np.ascontiguousarray(entries, dtype=COVERAGE_ENTRY_DTYPE)
+    _lib.check(_lib.load().utree_coverage_write(db._h, e.ctypes.data if len(e) else None, len(e), n_reads, path.encode()),
+               "utree_coverage_write")
+
+
 def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: bool = False, threads: int = 0,
-              input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None):
+              input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
-    FASTA / gzip input.  profile: also write the per-taxon read counts there (utree_search_file_profile)."""
+    FASTA / gzip input.  profile: also write the per-taxon read counts there (utree_search_file_profile); coverage: also
+    write the per-taxon k-mer coverage there (utree_search_file_coverage)."""
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     st = _lib.SearchStats()
-    if profile is not None:
+    if coverage is not None:
+        code = _lib.load().utree_search_file_coverage(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads,
+                                                      input_format, profile.encode() if profile is not None else None,
+                                                      coverage.encode(), C.byref(st))
+    elif profile is not None:
         code = _lib.load().utree_search_file_profile(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads,
                                                      input_format, profile.encode(), C.byref(st))
     else:
