@@ -8,8 +8,8 @@ R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 mkdir -p /tmp/asan
 cd $R/utree_amd/csrc
 SF="-fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g -std=gnu11 -fPIC -fopenmp -I/opt/rocm/include"
-for f in ctr_host dev_image fasta search search_dev rccl_replicate compress rank build profile coverage; do gcc $SF -c $f.c -o /tmp/asan/$f.o; done
-HIPO=$(ls kernels.o lanes_kernel.o lanes_part_*.o rank_kernels.o text_kernels.o profile_kernels.o coverage_kernels.o build_gpu.o image_build.o)
+for f in $(make -s print-host-objs); do gcc $SF -c ${f%.o}.c -o /tmp/asan/$f; done                 # (the Makefile owns the object lists)
+HIPO=$(make -s print-hip-objs)
 gcc -shared -fopenmp -fsanitize=address,undefined -o /tmp/asan/libutree_amd_asan.so $HIPO /tmp/asan/*.o -L/opt/rocm/lib -lamdhip64 -lrccl -lstdc++ -lz -lm -lpthread -Wl,-rpath,/opt/rocm/lib
 cd $R/oracle
 gcc -O1 -g -std=gnu11 -fopenmp -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer -shared -o /tmp/asan/liboracle.so utree_oracle.c utree_build_oracle.c

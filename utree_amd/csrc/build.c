@@ -9,12 +9,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 #include <unistd.h>
-#include "../../include/utree_amd.h"
+#include "utree_internal.h"
 #include "build_gpu.h"
 
-static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 static uint8_t *read_all(const char *path, uint64_t *n) {
     int fd = open(path, O_RDONLY);

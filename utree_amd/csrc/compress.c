@@ -14,13 +14,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 #include <unistd.h>
 #include "utree_internal.h"
 
 #define HIPC(x) do { if ((x) != hipSuccess) { rc = UTREE_E_HIP; goto done; } } while (0)
 
-static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 /* label tail as readSamplesFPdelim(…, delim = 0) leaves it (itree.c:1154-1211): labels in first-seen order;
  * a line's count goes to SampCnts[sampIX] -- the NEWEST label so far, also when the line repeats an older label */

@@ -21,6 +21,7 @@
 #include "ctr_host.h"
 #include "dev_image.h"
 #include "coverage.h"
+#include "taxon_table.h"
 
 struct utree_coverage {
     int device, n_cu;
@@ -64,18 +65,7 @@ static int stream_dump(const utree_ctr *ctr, utree_coverage *c) {
     for (int slot = 0; done < total; slot ^= 1) {
         const size_t bytes = total - done < piece ? total - done : piece;
         CHK(hipEventSynchronize(ev[slot]));
-        int T = 8, bad = 0;
-        if ((size_t)T > bytes / ((size_t)4 << 20) + 1) T = (int)(bytes / ((size_t)4 << 20) + 1);
-#pragma omp parallel for num_threads(T) schedule(static, 1) reduction(| : bad)
-        for (int t = 0; t < T; ++t) {
-            size_t a = bytes * (size_t)t / (size_t)T, e = bytes * (size_t)(t + 1) / (size_t)T;
-            while (a < e) {
-                ssize_t r = pread(fd, (char *)h_pin[slot] + a, e - a, (off_t)(ctr->records_file_off + done + a));
-                if (r <= 0) { bad |= 1; break; }
-                a += (size_t)r;
-            }
-        }
-        if (bad) { rc = UTREE_E_FORMAT; goto fail; }
+        if (utree_pread_team(fd, h_pin[slot], bytes, ctr->records_file_off + done, 8)) { rc = UTREE_E_FORMAT; goto fail; }
         CHK(hipMemcpyAsync((char *)c->d_recs + done, h_pin[slot], bytes, hipMemcpyHostToDevice, NULL));
         CHK(hipEventRecord(ev[slot], NULL));
         done += bytes;
@@ -211,45 +201,11 @@ void utree_coverage_free(utree_coverage *c) {
     free(c);
 }
 
-/* ---- host: merge by text, roll up, write ---------------------------------------------------------------------------- */
-typedef struct { const char *s; uint32_t len; uint64_t own[3], clade[3]; } crow;       /* {db_kmers, covered, hits} */
-
-static int text_cmp(const char *a, uint32_t la, const char *b, uint32_t lb) {
-    const uint32_t m = la < lb ? la : lb;
-    const int c = m ? memcmp(a, b, m) : 0;
-    if (c) return c;
-    return la < lb ? -1 : la > lb;
-}
-static int crow_cmp(const void *a, const void *b) {
-    const crow *x = (const crow *)a, *y = (const crow *)b;
-    return text_cmp(x->s, x->len, y->s, y->len);
-}
-/* sort rows by text and add up the own figures of rows of equal text; returns the count left */
-static size_t merge_rows(crow *r, size_t n) {
-    if (!n) return 0;
-    qsort(r, n, sizeof *r, crow_cmp);
-    size_t w = 0;
-    for (size_t i = 1; i < n; ++i) {
-        if (!crow_cmp(&r[w], &r[i])) for (int q = 0; q < 3; ++q) r[w].own[q] += r[i].own[q];
-        else r[++w] = r[i];
-    }
-    return w + 1;
-}
-static crow *find_row(crow *r, size_t n, const char *s, uint32_t len) {
-    size_t lo = 0, hi = n;
-    while (lo < hi) {
-        const size_t mid = (lo + hi) / 2;
-        const int c = text_cmp(r[mid].s, r[mid].len, s, len);
-        if (!c) return &r[mid];
-        if (c < 0) lo = mid + 1; else hi = mid;
-    }
-    return NULL;
-}
-
+/* ---- host: every label's figures as rows of the taxon table (taxon_table.c) ----------------------------------------------- */
 int utree_coverage_write(const utree_ctr *ctr, const utree_coverage_entry *e, size_t n, uint64_t n_reads, const char *path) {
     if (!ctr || (n && !e) || !path) return UTREE_E_ARG;
     uint64_t tot[3] = {0, 0, 0};
-    crow *t = (crow *)calloc(n ? n : 1, sizeof *t);
+    utree_taxon_row *t = (utree_taxon_row *)calloc(n ? n : 1, sizeof *t);      /* own: {db_kmers, covered, hits} */
     if (!t) return UTREE_E_NOMEM;
     for (size_t i = 0; i < n; ++i) {                        /* every label of the database, hit or not */
         if (e[i].label >= ctr->info.n_labels) { free(t); return UTREE_E_ARG; }
@@ -257,83 +213,11 @@ int utree_coverage_write(const utree_ctr *ctr, const utree_coverage_entry *e, si
         t[i].own[0] = e[i].db_kmers; t[i].own[1] = e[i].covered; t[i].own[2] = e[i].hits;
         for (int q = 0; q < 3; ++q) tot[q] += t[i].own[q];
     }
-    const size_t nt = merge_rows(t, n);                      /* one row per distinct text */
-    size_t nr = 0;
-    for (size_t i = 0; i < nt; ++i) {
-        if (!t[i].own[2]) continue;
-        ++nr;
-        for (uint32_t j = 0; j < t[i].len; ++j) nr += t[i].s[j] == ';';
-    }
-    crow *r = (crow *)calloc(nr ? nr : 1, sizeof *r);
-    if (!r) { free(t); return UTREE_E_NOMEM; }
-    size_t k = 0;
-    for (size_t i = 0; i < nt; ++i) {                        /* the rows: every hit taxon and every ';'-prefix of one (own figures 0 unless a label has that text) */
-        if (!t[i].own[2]) continue;
-        r[k++] = t[i];
-        for (uint32_t j = 0; j < t[i].len; ++j)
-            if (t[i].s[j] == ';') { r[k].s = t[i].s; r[k].len = j; ++k; }
-    }
-    nr = merge_rows(r, k);
-    for (size_t i = 0; i < nr; ++i) {                        /* a prefix row that is also some (unhit) label's whole text shows that label's figures */
-        const crow *o = find_row(t, nt, r[i].s, r[i].len);
-        for (int q = 0; q < 3; ++q) { r[i].own[q] = o ? o->own[q] : 0; r[i].clade[q] = 0; }
-    }
-    for (size_t i = 0; i < nt; ++i) {                        /* clade figures: over ALL labels whose text is the row's or begins with it + ';' */
-        crow *o = find_row(r, nr, t[i].s, t[i].len);
-        if (o) for (int q = 0; q < 3; ++q) o->clade[q] += t[i].own[q];
-        for (uint32_t j = 0; j < t[i].len; ++j)
-            if (t[i].s[j] == ';' && (o = find_row(r, nr, t[i].s, j))) for (int q = 0; q < 3; ++q) o->clade[q] += t[i].own[q];
-    }
+    char header[320];
+    snprintf(header, sizeof header, "# reads\t%llu\thits\t%llu\tcovered\t%llu\tdb_kmers\t%llu\n"
+                                    "# taxon\tdb_kmers\tcovered\thits\tclade_db_kmers\tclade_covered\tclade_hits\n",
+             (unsigned long long)n_reads, (unsigned long long)tot[2], (unsigned long long)tot[1], (unsigned long long)tot[0]);
+    const int rc = utree_taxon_table_write(t, n, 3, 2, header, path);       /* the rows are the HIT taxa and their prefixes; the clades sum over all labels */
     free(t);
-    FILE *f = fopen(path, "wb");
-    if (!f) { free(r); return UTREE_E_IO; }
-    int bad = fprintf(f, "# reads\t%llu\thits\t%llu\tcovered\t%llu\tdb_kmers\t%llu\n"
-                         "# taxon\tdb_kmers\tcovered\thits\tclade_db_kmers\tclade_covered\tclade_hits\n",
-                      (unsigned long long)n_reads, (unsigned long long)tot[2], (unsigned long long)tot[1], (unsigned long long)tot[0]) < 0;
-    for (size_t i = 0; i < nr && !bad; ++i) {
-        if (r[i].len && fwrite(r[i].s, 1, r[i].len, f) != r[i].len) bad = 1;
-        if (fprintf(f, "\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)r[i].own[0], (unsigned long long)r[i].own[1],
-                    (unsigned long long)r[i].own[2], (unsigned long long)r[i].clade[0], (unsigned long long)r[i].clade[1],
-                    (unsigned long long)r[i].clade[2]) < 0) bad = 1;
-    }
-    free(r);
-    if (fclose(f) != 0) bad = 1;
-    return bad ? UTREE_E_IO : UTREE_OK;
-}
-
-/* ---- whole-file searches: one handle per device handle, merged at the end ------------------------------------------------ */
-int utree_coverages_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, utree_coverage **out) {
-    for (int g = 0; g < n_dev; ++g) {
-        int rc = utree_coverage_create(ctr, devs[g], NULL, NULL, &out[g]);
-        if (rc) { utree_coverages_free(out, g); return rc; }
-    }
-    return UTREE_OK;
-}
-
-void utree_coverages_free(utree_coverage **c, int n) { for (int g = 0; g < n; ++g) { utree_coverage_free(c[g]); c[g] = NULL; } }
-
-int utree_coverages_reset(utree_coverage **c, int n) {
-    for (int g = 0; g < n; ++g) { int rc = utree_coverage_reset(c[g]); if (rc) return rc; }
-    return UTREE_OK;
-}
-
-int utree_coverages_write(const utree_ctr *ctr, utree_coverage **c, int n, uint64_t n_reads_expected, const char *path) {
-    int rc = UTREE_OK;
-    size_t k = 0;
-    uint64_t reads = 0;
-    utree_coverage_entry *e = (utree_coverage_entry *)malloc(((size_t)ctr->info.n_labels + 1) * sizeof *e);
-    if (!e) return UTREE_E_NOMEM;
-    for (int g = 1; g < n && !rc; ++g) rc = utree_coverage_merge(c[0], c[g]);
-    if (!rc) rc = utree_coverage_read(c[0], e, ctr->info.n_labels, &k, &reads, NULL);
-    char msg[256];
-    if (rc) snprintf(msg, sizeof msg, "coverage %s: the counters could not be merged and read back (%s)", path, utree_strerror(rc));
-    else if (reads != n_reads_expected) {                          /* every read added exactly once, or no file */
-        snprintf(msg, sizeof msg, "coverage %s: %llu reads added, the search read %llu", path, (unsigned long long)reads,
-                 (unsigned long long)n_reads_expected);
-        rc = UTREE_E_DEVICE;
-    } else if ((rc = utree_coverage_write(ctr, e, k, reads, path)))
-        snprintf(msg, sizeof msg, "coverage %s: cannot write the file (%s)", path, utree_strerror(rc));
-    if (rc) utree_set_error_text(msg);
-    free(e);
     return rc;
 }

@@ -28,13 +28,6 @@ int utk_coverage_count(const utk_cov_db *db, const uint32_t *bitmap, unsigned lo
 int utk_coverage_or(uint32_t *dst, const uint32_t *src, uint64_t n, void *stream);
 int utk_coverage_sum(unsigned long long *dst, const unsigned long long *src, uint64_t n, void *stream);
 
-/* the whole-file searches' coverage: one handle per device handle, merged into the first when the file is written */
-int utree_coverages_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, utree_coverage **out);
-void utree_coverages_free(utree_coverage **c, int n);
-int utree_coverages_reset(utree_coverage **c, int n);
-/* merges, checks that n_reads_expected reads were added (else UTREE_E_DEVICE) and writes the file; on failure utree_last_hip_error says why */
-int utree_coverages_write(const utree_ctr *ctr, utree_coverage **c, int n, uint64_t n_reads_expected, const char *path);
-
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 #include "ctr_host.h"
 
 const char *utree_strerror(int code) {
@@ -32,6 +33,21 @@ const char *utree_strerror(int code) {
     }
 }
 int utree_abi_version(void) { return UTREE_ABI_VERSION; }
+
+int utree_pread_team(int fd, void *dst, size_t bytes, uint64_t off, int max_threads) {
+    int T = max_threads, bad = 0;
+    if ((size_t)T > bytes / ((size_t)4 << 20) + 1) T = (int)(bytes / ((size_t)4 << 20) + 1);
+#pragma omp parallel for num_threads(T) schedule(static, 1) reduction(| : bad)
+    for (int t = 0; t < T; ++t) {
+        size_t a = bytes * (size_t)t / (size_t)T, e = bytes * (size_t)(t + 1) / (size_t)T;
+        while (a < e) {
+            ssize_t r = pread(fd, (char *)dst + a, e - a, (off_t)(off + a));
+            if (r <= 0) { bad |= 1; break; }
+            a += (size_t)r;
+        }
+    }
+    return bad;
+}
 
 /* ---- label table: index = order of first appearance; repeats map to the first index (itree.c:191-220) ---- */
 static uint64_t hash_bytes(const char *s, size_t n) {

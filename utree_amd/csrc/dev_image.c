@@ -34,10 +34,6 @@ void utree_dev_set_hip_error(int err, const char *what) {
 const char *utree_last_hip_error(void) { return g_hip_msg; }
 void utree_set_error_text(const char *msg) { snprintf(g_hip_msg, sizeof g_hip_msg, "%s", msg); }
 
-#include <time.h>
-static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-static int timing_on(void) { return getenv("UTREE_TIMING") != NULL || getenv("UTREE_DEBUG") != NULL; }
-
 static uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 /* A bucket's size, in 8-byte words: 8 (64 bytes) unless UTREE_BUCKET_BYTES=128 asks for line-sized buckets (16).  Same-box on config 2
@@ -602,20 +598,8 @@ int utree_dev_upload(const utree_ctr *ctr, int device, int fine_bits, utree_dev 
         uint64_t cnt = N - done < chunk_recs ? N - done : chunk_recs;
         size_t bytes = (size_t)cnt * SZ;
         HIPCHK(hipEventSynchronize(ev[slot]));                 /* the pinned buffer is free again */
-        if (fd >= 0) {
-            int T = 8, bad = 0;
-            if ((size_t)T > bytes / ((size_t)4 << 20) + 1) T = (int)(bytes / ((size_t)4 << 20) + 1);
-#pragma omp parallel for num_threads(T) schedule(static, 1) reduction(| : bad)
-            for (int t = 0; t < T; ++t) {
-                size_t a = bytes * (size_t)t / (size_t)T, e = bytes * (size_t)(t + 1) / (size_t)T;
-                while (a < e) {
-                    ssize_t r = pread(fd, (char *)h_pin[slot] + a, e - a, (off_t)(ctr->records_file_off + done * SZ + a));
-                    if (r <= 0) { bad |= 1; break; }
-                    a += (size_t)r;
-                }
-            }
-            if (bad) { rc = UTREE_E_FORMAT; goto fail; }                   /* "Error in reading tree." itree.c:768 */
-        } else memcpy(h_pin[slot], ctr->h_records + done * SZ, bytes);
+        if (fd < 0) memcpy(h_pin[slot], ctr->h_records + done * SZ, bytes);
+        else if (utree_pread_team(fd, h_pin[slot], bytes, ctr->records_file_off + done * SZ, 8)) { rc = UTREE_E_FORMAT; goto fail; }   /* "Error in reading tree." itree.c:768 */
         HIPCHK(hipMemcpyAsync(d_raw[slot], h_pin[slot], bytes, hipMemcpyHostToDevice, NULL));
         rc = build_chunk(&b, d_raw[slot], done, cnt);
         if (rc) goto fail;

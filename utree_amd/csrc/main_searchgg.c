@@ -50,6 +50,17 @@
 static const char *TYPEARR[17] = {"NA", "uint8_t", "uint16_t", "NA", "uint32_t", "NA", "NA", "NA", "uint64_t", "NA", "NA",
                                   "NA", "NA", "NA", "NA", "NA", "__uint128_t"};
 
+/* can the report file `path` be opened for writing?  Else a message and exit 1.  Nothing is created or changed here: a search that fails leaves
+ * the path as it was (the file is written after a successful search) */
+static void check_report_path(const char *path, const char *what) {
+    int f = open(path, O_WRONLY | O_CREAT | O_EXCL, 0644);
+    const int created = f >= 0;
+    if (f < 0 && errno == EEXIST) f = open(path, O_WRONLY);
+    if (f < 0) { fprintf(stderr, "ERROR: cannot open the %s file %s: %s\n", what, path, strerror(errno)); exit(1); }
+    close(f);
+    if (created) unlink(path);
+}
+
 int main(int argc, char *argv[]) {
     if (argc < 4) {                                                                       /* itree.c:1358-1360 */
         printf(VER " usage: xtree-search%s compTree.ctr fastaToSearch.fa output.txt [threads] [SPEED <X>] [RC]\n", DO_GG ? "GG" : "");
@@ -70,25 +81,9 @@ int main(int argc, char *argv[]) {
     printf("Using up to %d threads.\n", threads);
 
     const char *profile = getenv("UTREE_PROFILE");
-    if (profile && *profile) {
-        /* can it be opened for writing?  Nothing is created or changed here: a search that fails leaves the path as it was (the file is written
-         * after a successful search) */
-        int pf = open(profile, O_WRONLY | O_CREAT | O_EXCL, 0644);
-        const int created = pf >= 0;
-        if (pf < 0 && errno == EEXIST) pf = open(profile, O_WRONLY);
-        if (pf < 0) { fprintf(stderr, "ERROR: cannot open the profile file %s: %s\n", profile, strerror(errno)); exit(1); }
-        close(pf);
-        if (created) unlink(profile);
-    } else profile = NULL;
+    if (profile && *profile) check_report_path(profile, "profile"); else profile = NULL;
     const char *coverage = DO_GG ? getenv("UTREE_COVERAGE") : NULL;
-    if (coverage && *coverage) {                                                          /* the same check, the same promise */
-        int cf = open(coverage, O_WRONLY | O_CREAT | O_EXCL, 0644);
-        const int created = cf >= 0;
-        if (cf < 0 && errno == EEXIST) cf = open(coverage, O_WRONLY);
-        if (cf < 0) { fprintf(stderr, "ERROR: cannot open the coverage file %s: %s\n", coverage, strerror(errno)); exit(1); }
-        close(cf);
-        if (created) unlink(coverage);
-    } else coverage = NULL;
+    if (coverage && *coverage) check_report_path(coverage, "coverage"); else coverage = NULL;
 
     utree_ctr *ctr = NULL;
     int rc = utree_ctr_open(argv[1], &ctr);
@@ -157,12 +152,9 @@ int main(int argc, char *argv[]) {
     if (getenv("UTREE_SLACK")) prm.slack = (uint32_t)atoi(getenv("UTREE_SLACK"));
     if (getenv("UTREE_SPARSITY")) prm.sparsity = (uint32_t)atoi(getenv("UTREE_SPARSITY"));
     if (getenv("UTREE_TOLERANCE")) prm.tolerance = (uint32_t)atoi(getenv("UTREE_TOLERANCE"));
-    rc = profile ? utree_rank_search_file_profile(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, &st)
-                 : utree_rank_search_file_opts(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, &st);
+    rc = utree_rank_search_file_profile(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, &st);   /* (a NULL path: no such report) */
 #else
-    rc = coverage ? utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st)
-         : profile ? utree_search_file_profile(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, &st)
-                   : utree_search_file_opts(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, &st);
+    rc = utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st);   /* (a NULL path: no such report) */
 #endif
     if (rc == UTREE_E_IO) { puts("Invalid input files"); exit(1); }                      /* itree.c:835 */
     if (rc == UTREE_E_FASTA) {

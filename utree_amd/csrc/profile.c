@@ -18,6 +18,7 @@
 #include "ctr_host.h"
 #include "dev_image.h"
 #include "profile.h"
+#include "taxon_table.h"
 
 struct utree_profile {
     int device, n_cu;
@@ -96,33 +97,11 @@ void utree_profile_free(utree_profile *p) {
     free(p);
 }
 
-/* ---- host: merge by text, roll up, write -------------------------------------------------------------------------- */
-typedef struct { const char *s; uint32_t len; uint64_t assigned, clade; } prow;
-
-static int row_cmp(const void *a, const void *b) {
-    const prow *x = (const prow *)a, *y = (const prow *)b;
-    const uint32_t m = x->len < y->len ? x->len : y->len;
-    const int c = m ? memcmp(x->s, y->s, m) : 0;
-    if (c) return c;
-    return x->len < y->len ? -1 : x->len > y->len;
-}
-
-/* sort rows by text and add up rows of equal text; returns the count left */
-static size_t merge_rows(prow *r, size_t n) {
-    if (!n) return 0;
-    qsort(r, n, sizeof *r, row_cmp);
-    size_t w = 0;
-    for (size_t i = 1; i < n; ++i) {
-        if (!row_cmp(&r[w], &r[i])) { r[w].assigned += r[i].assigned; r[w].clade += r[i].clade; }
-        else r[++w] = r[i];
-    }
-    return w + 1;
-}
-
+/* ---- host: the entries' texts and counts as rows of the taxon table (taxon_table.c) ------------------------------------- */
 int utree_profile_write(const utree_ctr *ctr, const utree_profile_entry *e, size_t n, uint64_t n_reads, const char *path) {
     if (!ctr || (n && !e) || !path) return UTREE_E_ARG;
     uint64_t classified = 0;
-    prow *t = (prow *)malloc((n ? n : 1) * sizeof *t);
+    utree_taxon_row *t = (utree_taxon_row *)calloc(n ? n : 1, sizeof *t);
     if (!t) return UTREE_E_NOMEM;
     size_t nt = 0;
     for (size_t i = 0; i < n; ++i) {                       /* the text each entry's lines print (utree_format_records, rank: the label) */
@@ -135,80 +114,14 @@ int utree_profile_write(const utree_ctr *ctr, const utree_profile_entry *e, size
             len = ctr->label_len[e[i].label];
             if (e[i].cut >= 0 && (uint32_t)e[i].cut < len) len = (uint32_t)e[i].cut;
         }
-        t[nt].s = s; t[nt].len = len; t[nt].assigned = e[i].reads; t[nt].clade = e[i].reads;
+        t[nt].s = s; t[nt].len = len; t[nt].own[0] = e[i].reads;
         classified += e[i].reads;
         ++nt;
     }
-    nt = merge_rows(t, nt);                                /* T: the assigned taxa */
-    size_t nr = nt;
-    for (size_t i = 0; i < nt; ++i) for (uint32_t j = 0; j < t[i].len; ++j) nr += t[i].s[j] == ';';
-    prow *r = (prow *)malloc((nr ? nr : 1) * sizeof *r);
-    if (!r) { free(t); return UTREE_E_NOMEM; }
-    size_t k = 0;
-    for (size_t i = 0; i < nt; ++i) {                      /* every taxon, and every ';'-prefix of it with the taxon's reads in its clade */
-        r[k++] = t[i];
-        for (uint32_t j = 0; j < t[i].len; ++j)
-            if (t[i].s[j] == ';') { r[k].s = t[i].s; r[k].len = j; r[k].assigned = 0; r[k].clade = t[i].assigned; ++k; }
-    }
+    char header[256];
+    snprintf(header, sizeof header, "# reads\t%llu\tclassified\t%llu\tunclassified\t%llu\n# taxon\tassigned\tclade\n", (unsigned long long)n_reads,
+             (unsigned long long)classified, (unsigned long long)(n_reads - classified));
+    const int rc = utree_taxon_table_write(t, nt, 1, 0, header, path);     /* one figure, the reads: every row is an assigned taxon or a prefix of one */
     free(t);
-    nr = merge_rows(r, k);
-    FILE *f = fopen(path, "wb");
-    if (!f) { free(r); return UTREE_E_IO; }
-    int bad = fprintf(f, "# reads\t%llu\tclassified\t%llu\tunclassified\t%llu\n# taxon\tassigned\tclade\n", (unsigned long long)n_reads,
-                      (unsigned long long)classified, (unsigned long long)(n_reads - classified)) < 0;
-    for (size_t i = 0; i < nr && !bad; ++i) {
-        if (r[i].len && fwrite(r[i].s, 1, r[i].len, f) != r[i].len) bad = 1;
-        if (fprintf(f, "\t%llu\t%llu\n", (unsigned long long)r[i].assigned, (unsigned long long)r[i].clade) < 0) bad = 1;
-    }
-    free(r);
-    if (fclose(f) != 0) bad = 1;
-    return bad ? UTREE_E_IO : UTREE_OK;
-}
-
-/* ---- whole-file searches: one profile per device handle, merged at the end ------------------------------------------- */
-int utree_profiles_create(utree_dev **devs, int n_dev, utree_profile **out) {
-    const char *e = getenv("UTREE_PROFILE_CAPACITY");
-    const uint32_t cap = e && atoll(e) >= 1 && atoll(e) <= (1ll << 30) ? (uint32_t)atoll(e) : UTREE_PROFILE_DEFAULT_CAPACITY;
-    for (int g = 0; g < n_dev; ++g) {
-        int rc = utree_profile_create(devs[g], cap, &out[g]);
-        if (rc) { utree_profiles_free(out, g); return rc; }
-    }
-    return UTREE_OK;
-}
-
-void utree_profiles_free(utree_profile **p, int n) { for (int g = 0; g < n; ++g) { utree_profile_free(p[g]); p[g] = NULL; } }
-
-int utree_profiles_reset(utree_profile **p, int n) {
-    for (int g = 0; g < n; ++g) { int rc = utree_profile_reset(p[g]); if (rc) return rc; }
-    return UTREE_OK;
-}
-
-int utree_profiles_write(const utree_ctr *ctr, utree_profile **p, int n, uint64_t n_reads_expected, const char *path) {
-    size_t total = 0;
-    for (int g = 0; g < n; ++g) total += utree_profile_max_entries(p[g]);
-    utree_profile_entry *e = (utree_profile_entry *)malloc((total ? total : 1) * sizeof *e);
-    if (!e) return UTREE_E_NOMEM;
-    size_t at = 0;
-    uint64_t reads = 0;
-    int rc = UTREE_OK;
-    for (int g = 0; g < n && !rc; ++g) {
-        size_t k = 0;
-        uint64_t nr = 0;
-        rc = utree_profile_read(p[g], e + at, total - at, &k, &nr, NULL);
-        at += k; reads += nr;
-    }
-    char msg[256];
-    if (rc == UTREE_E_DEVICE)
-        snprintf(msg, sizeof msg, "profile %s: the table of truncated taxa was too small (raise UTREE_PROFILE_CAPACITY), or a read named no label", path);
-    else if (rc)
-        snprintf(msg, sizeof msg, "profile %s: the counters could not be read back (%s)", path, utree_strerror(rc));
-    else if (reads != n_reads_expected) {                          /* every read counted exactly once, or no file */
-        snprintf(msg, sizeof msg, "profile %s: %llu reads counted, the search read %llu", path, (unsigned long long)reads,
-                 (unsigned long long)n_reads_expected);
-        rc = UTREE_E_DEVICE;
-    } else if ((rc = utree_profile_write(ctr, e, at, reads, path)))
-        snprintf(msg, sizeof msg, "profile %s: cannot write the file (%s)", path, utree_strerror(rc));
-    if (rc) utree_set_error_text(msg);
-    free(e);
     return rc;
 }

@@ -14,15 +14,6 @@ extern "C" {
 int utk_profile_add(const utree_result *d_res, uint32_t n, uint32_t n_labels, unsigned long long *d_whole, unsigned long long *d_table,
                     uint32_t mask, unsigned long long *d_misc, int n_cu, void *stream);
 
-/* the whole-file searches' profiles: one per device handle (truncated-taxon slots: UTREE_PROFILE_CAPACITY, default below) */
-#define UTREE_PROFILE_DEFAULT_CAPACITY (1u << 20)
-int utree_profiles_create(utree_dev **devs, int n_dev, utree_profile **out);
-void utree_profiles_free(utree_profile **p, int n);
-int utree_profiles_reset(utree_profile **p, int n);
-/* reads every device's entries, checks that they counted n_reads_expected reads (else UTREE_E_DEVICE) and writes the file; on failure
- * utree_last_hip_error says why */
-int utree_profiles_write(const utree_ctr *ctr, utree_profile **p, int n, uint64_t n_reads_expected, const char *path);
-
 #ifdef __cplusplus
 }
 #endif

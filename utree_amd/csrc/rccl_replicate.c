@@ -19,14 +19,12 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 #include "ctr_host.h"
 #include "dev_image.h"
 
 #define BCAST_PIECE ((size_t)1 << 30)
 
 static int env_on(const char *name) { const char *e = getenv(name); return e && atoi(e) > 0; }
-static double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 
 static double g_last_bcast_s;
 double utree_dev_replicate_seconds(void) { return g_last_bcast_s; }

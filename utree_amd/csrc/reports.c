@@ -1,0 +1,116 @@
+/* reports.c -- the opt-in reports of one whole-file search (reports.h): a profile (profile.c) and / or a coverage handle (coverage.c) per
+ * device handle, fed chunk by chunk, merged and written when the search has succeeded. */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "ctr_host.h"
+#include "dev_image.h"
+#include "reports.h"
+
+struct utree_reports {
+    int n_dev;
+    const char *profile_path, *coverage_path;
+    struct { utree_profile *prof; utree_coverage *cov; } dev[];      /* NULL: the search writes no such report */
+};
+
+int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *profile_path, const char *coverage_path,
+                         utree_reports **out) {
+    *out = NULL;
+    if (!profile_path && !coverage_path) return UTREE_OK;
+    if (!ctr || !devs || n_dev < 1) return UTREE_E_ARG;
+    utree_reports *rep = (utree_reports *)calloc(1, sizeof *rep + (size_t)n_dev * sizeof rep->dev[0]);
+    if (!rep) return UTREE_E_NOMEM;
+    rep->n_dev = n_dev; rep->profile_path = profile_path; rep->coverage_path = coverage_path;
+    const char *e = getenv("UTREE_PROFILE_CAPACITY");
+    const uint32_t cap = e && atoll(e) >= 1 && atoll(e) <= (1ll << 30) ? (uint32_t)atoll(e) : UTREE_PROFILE_DEFAULT_CAPACITY;
+    int rc = UTREE_OK;
+    for (int g = 0; profile_path && g < n_dev && !rc; ++g) rc = utree_profile_create(devs[g], cap, &rep->dev[g].prof);
+    for (int g = 0; coverage_path && g < n_dev && !rc; ++g) rc = utree_coverage_create(ctr, devs[g], NULL, NULL, &rep->dev[g].cov);
+    if (rc) { utree_reports_free(rep); return rc; }
+    *out = rep;
+    return UTREE_OK;
+}
+
+void utree_reports_free(utree_reports *rep) {
+    if (!rep) return;
+    for (int g = 0; g < rep->n_dev; ++g) utree_profile_free(rep->dev[g].prof);
+    for (int g = 0; g < rep->n_dev; ++g) utree_coverage_free(rep->dev[g].cov);
+    free(rep);
+}
+
+int utree_reports_reset(utree_reports *rep) {
+    int rc = UTREE_OK;
+    for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].prof) rc = utree_profile_reset(rep->dev[g].prof);
+    for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].cov) rc = utree_coverage_reset(rep->dev[g].cov);
+    return rc;
+}
+
+int utree_reports_add(utree_reports *rep, int g, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                      const utree_result *d_res, uint32_t n, int do_rc, int rank, void *stream) {
+    if (!rep) return UTREE_OK;
+    int rc = rep->dev[g].prof ? utree_profile_add(rep->dev[g].prof, d_res, n, stream) : UTREE_OK;
+    if (!rc && rep->dev[g].cov && !rank) rc = utree_coverage_add(rep->dev[g].cov, d_bases, d_off, d_len, n, do_rc, stream);
+    return rc;
+}
+
+/* reads every device's entries, checks that they counted n_reads_expected reads (else UTREE_E_DEVICE) and writes the file */
+static int write_profile(const utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads_expected) {
+    const char *path = rep->profile_path;
+    size_t total = 0;
+    for (int g = 0; g < rep->n_dev; ++g) total += utree_profile_max_entries(rep->dev[g].prof);
+    utree_profile_entry *e = (utree_profile_entry *)malloc((total ? total : 1) * sizeof *e);
+    if (!e) return UTREE_E_NOMEM;
+    size_t at = 0;
+    uint64_t reads = 0;
+    int rc = UTREE_OK;
+    for (int g = 0; g < rep->n_dev && !rc; ++g) {
+        size_t k = 0;
+        uint64_t nr = 0;
+        rc = utree_profile_read(rep->dev[g].prof, e + at, total - at, &k, &nr, NULL);
+        at += k; reads += nr;
+    }
+    char msg[256];
+    if (rc == UTREE_E_DEVICE)
+        snprintf(msg, sizeof msg, "profile %s: the table of truncated taxa was too small (raise UTREE_PROFILE_CAPACITY), or a read named no label", path);
+    else if (rc)
+        snprintf(msg, sizeof msg, "profile %s: the counters could not be read back (%s)", path, utree_strerror(rc));
+    else if (reads != n_reads_expected) {                          /* every read counted exactly once, or no file */
+        snprintf(msg, sizeof msg, "profile %s: %llu reads counted, the search read %llu", path, (unsigned long long)reads,
+                 (unsigned long long)n_reads_expected);
+        rc = UTREE_E_DEVICE;
+    } else if ((rc = utree_profile_write(ctr, e, at, reads, path)))
+        snprintf(msg, sizeof msg, "profile %s: cannot write the file (%s)", path, utree_strerror(rc));
+    if (rc) utree_set_error_text(msg);
+    free(e);
+    return rc;
+}
+
+/* merges the devices' handles into the first, checks that n_reads_expected reads were added (else UTREE_E_DEVICE) and writes the file */
+static int write_coverage(const utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads_expected) {
+    const char *path = rep->coverage_path;
+    int rc = UTREE_OK;
+    size_t k = 0;
+    uint64_t reads = 0;
+    utree_coverage_entry *e = (utree_coverage_entry *)malloc(((size_t)ctr->info.n_labels + 1) * sizeof *e);
+    if (!e) return UTREE_E_NOMEM;
+    for (int g = 1; g < rep->n_dev && !rc; ++g) rc = utree_coverage_merge(rep->dev[0].cov, rep->dev[g].cov);
+    if (!rc) rc = utree_coverage_read(rep->dev[0].cov, e, ctr->info.n_labels, &k, &reads, NULL);
+    char msg[256];
+    if (rc) snprintf(msg, sizeof msg, "coverage %s: the counters could not be merged and read back (%s)", path, utree_strerror(rc));
+    else if (reads != n_reads_expected) {                          /* every read added exactly once, or no file */
+        snprintf(msg, sizeof msg, "coverage %s: %llu reads added, the search read %llu", path, (unsigned long long)reads,
+                 (unsigned long long)n_reads_expected);
+        rc = UTREE_E_DEVICE;
+    } else if ((rc = utree_coverage_write(ctr, e, k, reads, path)))
+        snprintf(msg, sizeof msg, "coverage %s: cannot write the file (%s)", path, utree_strerror(rc));
+    if (rc) utree_set_error_text(msg);
+    free(e);
+    return rc;
+}
+
+int utree_reports_write(utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads) {
+    if (!rep) return UTREE_OK;
+    const int ce = rep->coverage_path ? write_coverage(rep, ctr, n_reads) : UTREE_OK;
+    if (rep->profile_path && write_profile(rep, ctr, n_reads)) return UTREE_E_PROFILE;
+    return ce ? UTREE_E_COVERAGE : UTREE_OK;      /* (a profile that was written sets no text: the coverage's stands) */
+}

@@ -1,0 +1,28 @@
+/* reports.h -- the opt-in reports a whole-file search feeds while it runs (reports.c), private.
+ *
+ * One object per search: for every device handle the profile (UTREE_PROFILE) and / or the coverage handle (UTREE_COVERAGE) its reads go into.
+ * The pipelines (search.c, search_dev.c) only pass it on and call utree_reports_add; which reports there are, when they are reset, merged and
+ * written is decided in reports.c and by search.c's one caller of create / write / free. */
+#ifndef UTREE_REPORTS_H
+#define UTREE_REPORTS_H
+#include "utree_internal.h"
+
+#define UTREE_PROFILE_DEFAULT_CAPACITY (1u << 20)   /* truncated-taxon slots of a search's profiles; UTREE_PROFILE_CAPACITY overrides */
+
+typedef struct utree_reports utree_reports;
+
+/* *out = NULL when both paths are NULL: nothing is allocated and nothing launched.  The paths are borrowed until utree_reports_free. */
+int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *profile_path, const char *coverage_path,
+                         utree_reports **out);
+/* n reads of device handle `g` whose output is committed: their records into its profile and -- unless `rank`: the coverage counts the GG
+ * search's windows -- the reads into its coverage handle; asynchronous on `stream`.  rep == NULL: nothing. */
+int utree_reports_add(utree_reports *rep, int g, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                      const utree_result *d_res, uint32_t n, int do_rc, int rank, void *stream);
+/* the search starts the file over: so do the reports */
+int utree_reports_reset(utree_reports *rep);
+/* after a search that succeeded and read n_reads reads: merges the devices' figures, checks that every read was counted exactly once and writes
+ * the files, the coverage first.  0, UTREE_E_PROFILE or UTREE_E_COVERAGE (the profile's failure wins); utree_last_hip_error says why */
+int utree_reports_write(utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads);
+void utree_reports_free(utree_reports *rep);
+
+#endif

@@ -18,7 +18,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 #include <unistd.h>
 #include <zlib.h>
 #ifdef _OPENMP
@@ -27,20 +26,13 @@
 #include "ctr_host.h"
 #include "dev_image.h"
 #include "search_dev.h"
-#include "profile.h"
-#include "coverage.h"
+#include "reports.h"
 
 #define CHUNK_BYTES ((size_t)96 << 20)        /* must hold two maximal (16 MiB) lines                    */
 #define MAX_READS_PER_BATCH ((size_t)2 << 20)  /* more reads in a chunk (tiny reads) simply take another batch */
 #define LINELEN_MAX 16777216u                 /* itree.c:836 */
 #define NSLOTS 4
 #define READ_THREADS 4
-
-static double now_s(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
-}
 
 enum { S_EMPTY = 0, S_FRAMED, S_DONE, S_FORMATTED };
 #define FMT_MAX_THREADS 16
@@ -74,14 +66,13 @@ static int slot_alloc(slot_t *s) {
 
 typedef struct {
     utree_dev *dev;
-    utree_profile *prof;                        /* non-NULL: the search writes a profile; this device's reads are counted here */
-    utree_coverage *cov;                        /* non-NULL: ... a coverage file; this device's reads are added here (GG search only) */
     hipStream_t stream;
     uint8_t *d_buf; uint64_t *d_off; uint32_t *d_len; utree_result *d_out; void *d_ws; size_t ws_bytes;
 } gpu_ctx;
 
 typedef struct {
     const utree_ctr *ctr;
+    utree_reports *rep;                         /* non-NULL: the search feeds reports (reports.h)            */
     gpu_ctx *G; int n_dev;
     int fd, fo;                                 /* input, output                                            */
     off_t out_pos, start_off;                   /* start_off: where the input begins for this pipeline (behind what the device pipeline wrote to a pipe) */
@@ -231,8 +222,8 @@ static void *gpu_main(void *arg) {
                             : utree_classify_batch(c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
                                                    c->d_out, c->d_ws, c->ws_bytes, c->stream);
             if (e) { set_error(P, e); return NULL; }
-            if (c->prof && (e = utree_profile_add(c->prof, c->d_out, (uint32_t)count, c->stream))) { set_error(P, e); return NULL; }
-            if (c->cov && !P->rank && (e = utree_coverage_add(c->cov, c->d_buf, c->d_off, c->d_len, (uint32_t)count, P->do_rc, c->stream))) { set_error(P, e); return NULL; }
+            e = utree_reports_add(P->rep, (int)g, c->d_buf, c->d_off, c->d_len, c->d_out, (uint32_t)count, P->do_rc, P->rank != NULL, c->stream);
+            if (e) { set_error(P, e); return NULL; }
             HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
         }
         for (size_t g = 0; g < n_dev && nr; ++g) {
@@ -341,8 +332,8 @@ static void free_ctx(gpu_ctx *g) {
 #define HIPM(x) do { if ((x) != hipSuccess) { rc = UTREE_E_HIP; goto done; } } while (0)
 
 static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
-                       int do_rc, const utree_rank_params *rank, int host_threads, int input_format, utree_profile **profs,
-                       utree_coverage **covs, utree_search_stats *stats) {
+                       int do_rc, const utree_rank_params *rank, int host_threads, int input_format, utree_reports *rep,
+                       utree_search_stats *stats) {
     if (!ctr || !devs || n_dev < 1 || !fasta_path || !out_path || input_format < 0 || input_format > UTREE_INPUT_AUTO) return UTREE_E_ARG;
     int rc = UTREE_OK;
     uint64_t dev_printed = 0;
@@ -352,18 +343,17 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
      * does not take -- malformed records, NUL bytes, lines fgets would split -- and the host framing below then reproduces
      * the reference on it case by case.  UTREE_HOST_TEXT=1 forces the host pipeline (tests, A/B). */
     if (!rank && input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
-        rc = utree_search_file_device(ctr, devs, n_dev, fasta_path, out_path, do_rc, host_threads, profs, covs, stats, &dev_printed, &resume);
+        rc = utree_search_file_device(ctr, devs, n_dev, fasta_path, out_path, do_rc, host_threads, rep, stats, &dev_printed, &resume);
         if (rc != UTREE_RETRY_HOST) return rc;
         rc = UTREE_OK;
-        /* a profile carries the chunks the device pipeline has written when this pipeline continues behind them (resume.fo >= 0), as the
-         * counts do; when it starts the file over, so does the profile */
-        if (profs && resume.fo < 0 && (rc = utree_profiles_reset(profs, n_dev))) return rc;
-        if (covs && resume.fo < 0 && (rc = utree_coverages_reset(covs, n_dev))) return rc;
+        /* the reports carry the chunks the device pipeline has written when this pipeline continues behind them (resume.fo >= 0), as the
+         * counts do; when it starts the file over, so do the reports */
+        if (resume.fo < 0 && (rc = utree_reports_reset(rep))) return rc;
     }
     double t_start = now_s();
     pipe_t *P = (pipe_t *)calloc(1, sizeof *P);
     if (!P) { if (resume.fo >= 0) close(resume.fo); return UTREE_E_NOMEM; }
-    P->ctr = ctr; P->n_dev = n_dev; P->do_rc = do_rc; P->rank = rank; P->input_format = input_format;
+    P->ctr = ctr; P->rep = rep; P->n_dev = n_dev; P->do_rc = do_rc; P->rank = rank; P->input_format = input_format;
     P->progress_printed = dev_printed;
     P->fd = open(fasta_path, O_RDONLY);
     if (resume.fo >= 0) {
@@ -407,8 +397,6 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     for (int g = 0; g < n_dev; ++g) {
         gpu_ctx *c = &P->G[g];
         c->dev = devs[g];
-        c->prof = profs ? profs[g] : NULL;
-        c->cov = covs ? covs[g] : NULL;
         HIPM(hipSetDevice(devs[g]->device));
         HIPM(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         HIPM(hipMalloc((void **)&c->d_buf, CHUNK_BYTES + 64));
@@ -453,7 +441,7 @@ done:
     P->st.pipeline = 0; P->st.n_lanes = 1;
     P->st.seconds_read = P->t_read; P->st.seconds_frame = P->t_frame; P->st.seconds_classify_format = P->t_gpu;
     P->st.seconds_d2h = P->t_format; P->st.seconds_write = P->t_write;
-    if (getenv("UTREE_DEBUG") || getenv("UTREE_TIMING"))
+    if (timing_on())
         fprintf(stderr, "[utree_amd] stages: read %.3f s, frame %.3f s | gpu %.3f s | format %.3f s, write %.3f s (overlapped)\n",
                 P->t_read, P->t_frame, P->t_gpu, P->t_format, P->t_write);
     if (stats) *stats = P->st;
@@ -463,78 +451,50 @@ done:
     return rc;
 }
 
+/* One whole-file search as every public entry point asks for it.  rank: NULL = the GG search over n_dev device handles; else XT_doSearch32(utree,
+ * in, out, 0, speed, doRC) (itree.c:1376 without DO_GG): the same pipeline, the batches to ONE device in file order because each read's vote
+ * depends on the reads before it (rank.c).  profile_path / coverage_path: NULL, or the report to feed while searching and to write when the
+ * search has succeeded (the search's own codes stay its own). */
+static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
+                          const utree_rank_params *rank, int host_threads, int input_format, const char *profile_path,
+                          const char *coverage_path, utree_search_stats *stats) {
+    utree_reports *rep = NULL;
+    utree_search_stats st;
+    memset(&st, 0, sizeof st);
+    int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, &rep);
+    if (!rc && !rep) return search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, rank, host_threads, input_format, NULL, stats);   /* no report asked for */
+    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, rank, host_threads, input_format, rep, &st);
+    if (!rc) rc = utree_reports_write(rep, ctr, st.n_reads);
+    utree_reports_free(rep);
+    if (stats) *stats = st;
+    return rc;
+}
+
 int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
                       int do_rc, int host_threads, utree_search_stats *stats) {
-    return search_file(ctr, devs, n_dev, fasta_path, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, stats);
+    return search_request(ctr, devs, n_dev, fasta_path, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, stats);
 }
 int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
                            int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
-    return search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, stats);
+    return search_request(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, stats);
 }
-
-/* the search with one profile per device handle; the devices' counts are merged into one file when the search has succeeded */
-static int search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
-                               const utree_rank_params *rank, int host_threads, int input_format, const char *profile_path,
-                               utree_search_stats *stats) {
-    if (!profile_path) return search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, rank, host_threads, input_format, NULL, NULL, stats);
-    if (!ctr || !devs || n_dev < 1) return UTREE_E_ARG;
-    utree_profile **profs = (utree_profile **)calloc((size_t)n_dev, sizeof *profs);
-    if (!profs) return UTREE_E_NOMEM;
-    utree_search_stats st;
-    memset(&st, 0, sizeof st);
-    int rc = utree_profiles_create(devs, n_dev, profs);
-    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, rank, host_threads, input_format, profs, NULL, &st);
-    if (!rc && utree_profiles_write(ctr, profs, n_dev, st.n_reads, profile_path)) rc = UTREE_E_PROFILE;   /* (the search's own codes stay its own) */
-    utree_profiles_free(profs, n_dev);
-    free(profs);
-    if (stats) *stats = st;
-    return rc;
-}
-
 int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                               int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
-    return search_file_profile(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, profile_path, stats);
+    return search_request(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, stats);
 }
-
-/* the GG search with a coverage handle (and, with profile_path, a profile) per device handle; both files are written when the search has succeeded */
 int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                                int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                                utree_search_stats *stats) {
-    if (!coverage_path)
-        return search_file_profile(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, profile_path, stats);
-    if (!ctr || !devs || n_dev < 1) return UTREE_E_ARG;
-    utree_profile **profs = profile_path ? (utree_profile **)calloc((size_t)n_dev, sizeof *profs) : NULL;
-    utree_coverage **covs = (utree_coverage **)calloc((size_t)n_dev, sizeof *covs);
-    if (!covs || (profile_path && !profs)) { free(profs); free(covs); return UTREE_E_NOMEM; }
-    utree_search_stats st;
-    memset(&st, 0, sizeof st);
-    int rc = profs ? utree_profiles_create(devs, n_dev, profs) : UTREE_OK;
-    if (!rc) rc = utree_coverages_create(ctr, devs, n_dev, covs);
-    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, profs, covs, &st);
-    if (!rc) {                                                  /* (the search's own codes stay its own) */
-        const int ce = utree_coverages_write(ctr, covs, n_dev, st.n_reads, coverage_path);
-        if (profs && utree_profiles_write(ctr, profs, n_dev, st.n_reads, profile_path)) rc = UTREE_E_PROFILE;
-        else if (ce) rc = UTREE_E_COVERAGE;                    /* (a profile that was written sets no text: the coverage's stands) */
-    }
-    if (profs) utree_profiles_free(profs, n_dev);
-    utree_coverages_free(covs, n_dev);
-    free(profs); free(covs);
-    if (stats) *stats = st;
-    return rc;
+    return search_request(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, stats);
 }
 
-/* XT_doSearch32(utree, in, out, 0, speed, doRC) (itree.c:1376 without DO_GG): the same three-stage pipeline; the
- * batches go to ONE device in file order because each read's vote depends on the reads before it (rank.c). */
 int utree_rank_search_file(const utree_ctr *ctr, utree_dev *dev, const char *fasta_path, const char *out_path, int do_rc,
                            const utree_rank_params *params, int host_threads, utree_search_stats *stats) {
-    return utree_rank_search_file_opts(ctr, dev, fasta_path, out_path, do_rc, params, host_threads, UTREE_INPUT_REFERENCE, stats);
+    return utree_rank_search_file_profile(ctr, dev, fasta_path, out_path, do_rc, params, host_threads, UTREE_INPUT_REFERENCE, NULL, stats);
 }
 int utree_rank_search_file_opts(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
                                 const utree_rank_params *params, int host_threads, int input_format, utree_search_stats *stats) {
-    if (!dev || !params) return UTREE_E_ARG;
-    int rc = utree_rank_reset(dev);
-    if (rc) return rc;
-    return search_file(ctr, &dev, 1, reads_path, out_path, do_rc, params, host_threads, input_format, NULL, NULL, stats);
+    return utree_rank_search_file_profile(ctr, dev, reads_path, out_path, do_rc, params, host_threads, input_format, NULL, stats);
 }
 int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
                                    const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
@@ -542,5 +502,5 @@ int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const c
     if (!dev || !params) return UTREE_E_ARG;
     int rc = utree_rank_reset(dev);
     if (rc) return rc;
-    return search_file_profile(ctr, &dev, 1, reads_path, out_path, do_rc, params, host_threads, input_format, profile_path, stats);
+    return search_request(ctr, &dev, 1, reads_path, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, stats);
 }

@@ -28,7 +28,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
-#include <time.h>
 #include <unistd.h>
 #ifdef _OPENMP
 #include <omp.h>
@@ -49,12 +48,6 @@ static size_t chunk_bytes(void) {
     const char *e = getenv("UTREE_CHUNK_BYTES");
     if (e && atoll(e) >= 64 && (size_t)atoll(e) < DCHUNK_BYTES) return (size_t)atoll(e);
     return DCHUNK_BYTES;
-}
-
-static double now_s(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
 /* ---- per-device buffers, kept in the utree_dev between searches (pinned memory is slow to allocate) ---- */
@@ -90,7 +83,7 @@ static void *host_alloc(size_t bytes, int *pageable, const char *what) {
     const hipError_t e = hipGetLastError();
     p = NULL;
     if (posix_memalign(&p, 4096, bytes) != 0) p = NULL;
-    if (getenv("UTREE_DEBUG") || getenv("UTREE_TIMING") || !p)
+    if (timing_on() || !p)
         fprintf(stderr, "[utree_amd] warning: no pinned host memory for %s (%zu bytes: %s); %s\n", what, bytes, hipGetErrorString(e), p ? "using pageable memory" : "and no ordinary memory either");
     *pageable = 1;
     return p;
@@ -181,8 +174,7 @@ typedef struct dpipe dpipe;
 typedef struct {
     dpipe *P;
     utree_dev *dev;
-    utree_profile *prof;                        /* non-NULL: this device's profile of the search                   */
-    utree_coverage *cov;                        /* non-NULL: this device's coverage handle                         */
+    int g;                                      /* the device handle's index (the search's reports are kept per handle) */
     lane_buf *b;
     int read_threads;
     pthread_t th;
@@ -192,6 +184,7 @@ typedef struct {
 
 struct dpipe {
     const utree_ctr *ctr;
+    utree_reports *rep;                         /* non-NULL: the search feeds reports (reports.h)                   */
     int fd, fo, do_rc;
     off_t file_size;
     size_t chunk_bytes;
@@ -332,7 +325,7 @@ static void *lane_main(void *arg) {
                 pthread_mutex_lock(&P->mu);
                 const int left = --P->lanes_alive;
                 pthread_mutex_unlock(&P->mu);
-                if (getenv("UTREE_DEBUG") || getenv("UTREE_TIMING")) fprintf(stderr, "[utree_amd] device %d: a lane could not allocate its buffers (%s); %d lane(s) left\n", L->dev->device, utree_strerror(arc), left);
+                if (timing_on()) fprintf(stderr, "[utree_amd] device %d: a lane could not allocate its buffers (%s); %d lane(s) left\n", L->dev->device, utree_strerror(arc), left);
                 if (left <= 0) dfail(P, arc);
                 return NULL;
             }
@@ -344,20 +337,7 @@ static void *lane_main(void *arg) {
         if (got <= 0) return NULL;
         /* ---- file -> pinned memory (the page-cache copy), a small team ---- */
         double t0 = now_s();
-        {
-            int T = L->read_threads, bad = 0;
-            if ((size_t)T > len / ((size_t)4 << 20) + 1) T = (int)(len / ((size_t)4 << 20) + 1);
-#pragma omp parallel for num_threads(T) schedule(static, 1) reduction(| : bad)
-            for (int t = 0; t < T; ++t) {
-                size_t a = len * (size_t)t / (size_t)T, e = len * (size_t)(t + 1) / (size_t)T;
-                while (a < e) {
-                    ssize_t r = pread(P->fd, b->h_in + a, e - a, off + (off_t)a);
-                    if (r <= 0) { bad |= 1; break; }
-                    a += (size_t)r;
-                }
-            }
-            if (bad) { dfail(P, UTREE_E_IO); return NULL; }
-        }
+        if (utree_pread_team(P->fd, b->h_in, len, (uint64_t)off, L->read_threads)) { dfail(P, UTREE_E_IO); return NULL; }
         size_t n = len;
         if (final && b->h_in[n - 1] != '\n') b->h_in[n++] = '\n';      /* the last line needs no newline (fgets ends at EOF) */
         double t1 = now_s();
@@ -415,10 +395,9 @@ static void *lane_main(void *arg) {
         P->published_part[part]++;
         pthread_cond_broadcast(&P->cv);
         pthread_mutex_unlock(&P->mu);
-        /* the chunk is committed (published chunks are never dropped): its records go into the profile, on this lane's stream behind the vote */
-        if (L->prof && nr) { int pe = utree_profile_add(L->prof, b->d_res, nr, b->stream); if (pe) { dfail(P, pe); return NULL; } }
-        /* ... and its reads into the coverage: d_in, d_seq_off and d_seq_len still hold the chunk */
-        if (L->cov && nr) { int ce = utree_coverage_add(L->cov, b->d_in, b->d_seq_off, b->d_seq_len, nr, P->do_rc, b->stream); if (ce) { dfail(P, ce); return NULL; } }
+        /* the chunk is committed (published chunks are never dropped): its records and reads go into the search's reports, on this lane's stream
+         * behind the vote -- d_in, d_seq_off and d_seq_len still hold the chunk */
+        if (nr) { int pe = utree_reports_add(P->rep, L->g, b->d_in, b->d_seq_off, b->d_seq_len, b->d_res, nr, P->do_rc, 0, b->stream); if (pe) { dfail(P, pe); return NULL; } }
         double t4 = now_s();
         L->t_wait += t4 - t3;
         LH(hipStreamSynchronize(b->stream));
@@ -478,14 +457,14 @@ int utree_search_prepare(const utree_ctr *ctr, utree_dev **devs, int n_dev, int 
 }
 
 int utree_search_file_device(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
-                             int do_rc, int host_threads, utree_profile **profs, utree_coverage **covs, utree_search_stats *stats,
-                             uint64_t *progress_printed, utree_search_resume *resume) {
+                             int do_rc, int host_threads, utree_reports *rep, utree_search_stats *stats, uint64_t *progress_printed,
+                             utree_search_resume *resume) {
     const double t_start = now_s();
     if (progress_printed) *progress_printed = 0;
     if (resume) { memset(resume, 0, sizeof *resume); resume->fo = -1; }
     dpipe *P = (dpipe *)calloc(1, sizeof *P);
     if (!P) return UTREE_E_NOMEM;
-    P->ctr = ctr; P->do_rc = do_rc; P->next_progress = 1048576;
+    P->ctr = ctr; P->rep = rep; P->do_rc = do_rc; P->next_progress = 1048576;
     P->fd = open(fasta_path, O_RDONLY);
     P->n_parts = utree_output_parts();
     for (int p = 0; p < P->n_parts; ++p) {
@@ -532,8 +511,7 @@ int utree_search_file_device(const utree_ctr *ctr, utree_dev **devs, int n_dev, 
     if (!rc) {
         int started = 0;
         for (int i = 0; i < n_lanes; ++i) {                                       /* lane i: device i % n_dev, so consecutive chunks go to different GPUs */
-            lanes[i].P = P; lanes[i].dev = devs[i % n_dev]; lanes[i].prof = profs ? profs[i % n_dev] : NULL;
-            lanes[i].cov = covs ? covs[i % n_dev] : NULL;
+            lanes[i].P = P; lanes[i].dev = devs[i % n_dev]; lanes[i].g = i % n_dev;
             lanes[i].b = &((struct utree_search_ctx *)devs[i % n_dev]->search_ctx)->lane[i / n_dev];
             lanes[i].read_threads = per_lane;
             if (i == 0) { P->lane0 = &lanes[0]; P->lanes_alive = n_lanes; }
@@ -567,7 +545,7 @@ int utree_search_file_device(const utree_ctr *ctr, utree_dev **devs, int n_dev, 
         stats->seconds_kernels = stats->seconds_frame + stats->seconds_classify_format;
         stats->seconds_total = now_s() - t_start;
     }
-    if ((getenv("UTREE_DEBUG") || getenv("UTREE_TIMING")) && lanes && rc == UTREE_OK) {
+    if (timing_on() && lanes && rc == UTREE_OK) {
         double r = 0, f = 0, c = 0, d = 0, w = 0, o = 0;
         for (int i = 0; i < n_lanes; ++i) { r += lanes[i].t_read; f += lanes[i].t_frame; c += lanes[i].t_classify; d += lanes[i].t_d2h; o += lanes[i].t_wait + lanes[i].t_wlock; w += lanes[i].t_write; }
         fprintf(stderr, "[utree_amd] device text pipeline, %d lanes x %d read threads, lane-seconds: read %.3f | H2D+frame %.3f | classify+format %.3f | "

@@ -2,6 +2,7 @@
 #ifndef UTREE_SEARCH_DEV_H
 #define UTREE_SEARCH_DEV_H
 #include "utree_internal.h"
+#include "reports.h"
 
 /* not an error of the ABI: the input needs the host framing (search.c runs it next) */
 #define UTREE_RETRY_HOST 1000
@@ -17,11 +18,10 @@ typedef struct { int fo; long long in_off; uint64_t n_reads, good_finds, bytes_i
 int utree_output_parts(void);
 
 int utree_search_file_device(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
-                             int do_rc, int host_threads, utree_profile **profs, utree_coverage **covs, utree_search_stats *stats,
-                             uint64_t *progress_printed,
+                             int do_rc, int host_threads, utree_reports *rep, utree_search_stats *stats, uint64_t *progress_printed,
                              utree_search_resume *resume);
-/* profs: NULL, or one profile per device handle: a chunk's reads are added to its device's profile once its output is committed (a chunk
- * that a hand-over to the host pipeline drops is not counted).  covs: the same for coverage handles (utree_coverage_add).
+/* rep: NULL, or the search's reports: a chunk's reads are added to its device's once its output is committed (a chunk that a hand-over to
+ * the host pipeline drops is not counted).
  * *progress_printed: "Searched N queries..." lines already on stdout when the call gives up with UTREE_RETRY_HOST: the host
  * pipeline that runs the file again does not print those a second time (the reference prints each once, itree.c:878) */
 void utree_search_ctx_free(void *ctx);

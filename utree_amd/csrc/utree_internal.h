@@ -3,6 +3,8 @@
 #define UTREE_INTERNAL_H
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <time.h>
 #include "../../include/utree_amd.h"
 
 #ifdef __cplusplus
@@ -227,6 +229,14 @@ const char *utk_classify_short_name(const utk_image *im, uint32_t short_cap, int
 const char *utk_classify_long_name(const utk_image *im, char *buf, size_t cap);
 int utk_model_counts(const utk_image *im, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads,
                      int do_rc, unsigned long long *d_counts, void *stream);
+
+/* ---- small things every host file uses ---- */
+static inline double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+/* UTREE_TIMING=1 / UTREE_DEBUG=1: stage timings and warnings on stderr */
+static inline int timing_on(void) { return getenv("UTREE_TIMING") != NULL || getenv("UTREE_DEBUG") != NULL; }
+/* [off, off + bytes) of `fd` into `dst`, read by a team of at most `max_threads` threads with at least 4 MiB each (the page-cache copy is the
+ * cost -- one thread moves ~5 GB/s); returns nonzero when the file ends or fails before `bytes` (ctr_host.c) */
+int utree_pread_team(int fd, void *dst, size_t bytes, uint64_t off, int max_threads);
 
 #ifdef __cplusplus
 }

@@ -484,20 +484,13 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
               input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
-    FASTA / gzip input.  profile: also write the per-taxon read counts there (utree_search_file_profile); coverage: also
-    write the per-taxon k-mer coverage there (utree_search_file_coverage)."""
+    FASTA / gzip input.  profile: also write the per-taxon read counts there; coverage: also write the per-taxon k-mer
+    coverage there (utree_search_file_coverage; None: no such report)."""
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     st = _lib.SearchStats()
-    if coverage is not None:
-        code = _lib.load().utree_search_file_coverage(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads,
-                                                      input_format, profile.encode() if profile is not None else None,
-                                                      coverage.encode(), C.byref(st))
-    elif profile is not None:
-        code = _lib.load().utree_search_file_profile(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads,
-                                                     input_format, profile.encode(), C.byref(st))
-    else:
-        code = _lib.load().utree_search_file_opts(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads,
-                                                  input_format, C.byref(st))
+    code = _lib.load().utree_search_file_coverage(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads, input_format,
+                                                  profile.encode() if profile is not None else None,
+                                                  coverage.encode() if coverage is not None else None, C.byref(st))
     return code, st
 
 
@@ -507,12 +500,8 @@ def search_rank(db: CtrDB, tree: DeviceTree, fasta: str, out: str, rc: bool = Fa
     search_gg's."""
     st = _lib.SearchStats()
     prm = _lib.RankParams(slack, sparsity, tolerance)
-    if profile is not None:
-        code = _lib.load().utree_rank_search_file_profile(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm),
-                                                          threads, input_format, profile.encode(), C.byref(st))
-    else:
-        code = _lib.load().utree_rank_search_file_opts(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm),
-                                                       threads, input_format, C.byref(st))
+    code = _lib.load().utree_rank_search_file_profile(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm), threads,
+                                                      input_format, profile.encode() if profile is not None else None, C.byref(st))
     return code, st
 
 
