@@ -44,13 +44,16 @@ enum {
     UTREE_E_DEVICE = 11,     /* a batch's kernels found the workspace too small for it (utree_classify_poll)    */
     UTREE_E_PROFILE = 12,    /* the search itself succeeded, its profile was not written: utree_last_hip_error
                                 says why (utree_search_file_profile)                                            */
-    UTREE_E_COVERAGE = 13    /* ... its coverage file was not written (utree_search_file_coverage)              */
+    UTREE_E_COVERAGE = 13,   /* ... its coverage file was not written (utree_search_file_coverage)              */
+    UTREE_E_PAIRS = 14       /* paired input: one file holds fewer records than the other, or an interleaved file an
+                                odd number; the complete pairs in front were classified and written, and
+                                utree_last_hip_error names the shorter file (utree_search_pairs_file)            */
 };
 
 const char *utree_strerror(int code);
 /* what the calling thread's last UTREE_E_HIP / UTREE_E_DEVICE was: the failing HIP call and the runtime's message for it (no
  * counterpart in the reference, which has no device; "" when there was none); after UTREE_E_PROFILE / UTREE_E_COVERAGE, why the
- * file was not written */
+ * file was not written; after UTREE_E_PAIRS, which file ended first */
 const char *utree_last_hip_error(void);
 int utree_abi_version(void);
 
@@ -413,6 +416,47 @@ int utree_coverage_write(const utree_ctr *ctr, const utree_coverage_entry *e, si
 int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                                int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                                utree_search_stats *stats);
+
+/* ------------------------------------------------------------------------------------------------
+ * Paired-end reads: both mates of a pair cast ONE vote.  Neither the reference nor its input format knows pairs, but the reference fixes
+ * what a pair's answer must be: with RC it searches read + 'N' + revcomp(read) as one query (itree.c:891-898) -- a byte that is no base
+ * breaks the k-mer windows and the hits of both sides go into one list for one vote.  A pair is the same thing with the second mate in
+ * the reverse complement's place:
+ *   - pair i is record i of the reads file with record i of the mates file, or records 2i and 2i+1 of one interleaved file; each file is
+ *     framed by the chosen UTREE_INPUT_* format's framing and its framing errors keep their codes (read_index counts that file's records);
+ *   - its result, and its output line if it has one, are those of the single query named by mate 1's name whose sequence is
+ *     seq1 + "N" + seq2, bytes as framed: always len1 + 1 + len2 bytes, also when a mate is empty.  With RC the existing path appends the
+ *     joined query's reverse complement, so all four strands are covered;
+ *   - one line per pair with found > 0, in input order, columns unchanged;
+ *   - mate NAMES ARE NOT COMPARED (the /1 and /2, " 1:N:0" and " 2:N:0" conventions differ): mate 2's name is ignored;
+ *   - n_reads, "Searched N queries" and the profile's "# reads" count pairs;
+ *   - unequal record counts: UTREE_E_PAIRS, after the complete pairs in front were classified and written (as the reads before a
+ *     malformed one are); utree_last_hip_error names the shorter file;
+ *   - a pair whose joined length exceeds 16 MiB (LINELEN, itree.c:836) is the framing error "sequence too long", code 5, read_index =
+ *     the pair's number;
+ *   - GG search only: the rank-specific search carries state from read to read and reads no pairs.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint64_t total_bases;   /* joined bytes of the batch: the sum of len1 + 1 + len2                                   */
+    uint32_t max_len;       /* the longest joined query                                                                */
+    uint32_t error;         /* 0; 1: the joined bytes exceed joined_capacity; 2: a pair's length does not fit 32 bits --
+                               then no joined byte was written and d_joff / d_jlen are not to be used                  */
+} utree_pairs_meta;
+/* The device join in front of utree_classify_batch: for pair i, d_joined[d_joff[i] .. d_joff[i] + d_jlen[i]) = mate 1's bytes, 'N', mate
+ * 2's bytes, with d_jlen[i] = d_len1[i] + 1 + d_len2[i] and tight offsets (d_joff[0] = 0).  Mates are given as utree_classify_batch takes
+ * reads, at any alignment and in any order; both mate buffers may be the same buffer.  The caller sizes d_joined as total1 + total2 +
+ * n_pairs bytes (= joined_capacity) and d_joff / d_jlen for n_pairs entries; *d_meta (device memory) is filled on the way.  No byte at or
+ * beyond the joined total is written; a capacity that is too small sets meta.error and writes nothing.  Asynchronous on `stream` (a
+ * hipStream_t, NULL = default stream). */
+int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_off1, const uint32_t *d_len1, const uint8_t *d_bases2,
+                     const uint64_t *d_off2, const uint32_t *d_len2, uint32_t n_pairs, uint8_t *d_joined, uint64_t joined_capacity,
+                     uint64_t *d_joff, uint32_t *d_jlen, utree_pairs_meta *d_meta, void *stream);
+/* utree_search_file_coverage over pairs: mates_path = the file of second mates, or NULL when reads_path is interleaved.  Always the host
+ * framing pipeline (stats.pipeline == 0), any input_format, plain or -- with a non-reference format -- gzip.  profile_path / coverage_path
+ * and their errors exactly as for utree_search_file_coverage; both reports see the joined queries (no window crosses the 'N'). */
+int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                            const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
+                            const char *coverage_path, utree_search_stats *stats);
 
 /* ------------------------------------------------------------------------------------------------
  * `.ubt` -> `.ctr` = XT_cmp32(filename, outfile) (itree.c:1234-1315; `xtree-compress`), SURVEY.md §8(f) rank 2.

@@ -29,6 +29,7 @@ const char *utree_strerror(int code) {
         case UTREE_E_DEVICE: return "a kernel found the batch's workspace too small";
         case UTREE_E_PROFILE: return "the search succeeded but its profile was not written";
         case UTREE_E_COVERAGE: return "the search succeeded but its coverage file was not written";
+        case UTREE_E_PAIRS: return "the paired input files do not hold the same number of records";
         default: return "unknown error";
     }
 }

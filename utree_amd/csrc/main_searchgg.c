@@ -25,6 +25,14 @@
  *                           DISTINCT ones the sample hit and the hits (include/utree_amd.h: utree_coverage_write), collected on the GPU
  *                           while it searches; needs the node dump a second time in HBM (utree_coverage_bytes).  Path checks, failures and
  *                           exit codes as for UTREE_PROFILE, with which it may be combined.  Unset: nothing of it runs
+ *     UTREE_MATES=<path>    opt-in, xtree-searchGG only: paired-end reads.  fastaToSearch.fa holds the first mates, <path> the second; pair i is
+ *                           record i of both.  A pair is searched as ONE query, mate 1 + "N" + mate 2, and prints one line under mate 1's name
+ *                           (include/utree_amd.h: utree_search_pairs_file; mate names are not compared); "Searched N queries" and the profile
+ *                           count pairs.  Works with UTREE_INPUT, UTREE_PROFILE and UTREE_COVERAGE.  A mates file that cannot be opened:
+ *                           "Invalid input files", exit 1, before the tree is loaded.  Files of unequal record counts: the complete pairs are
+ *                           written, a message on stderr, exit 2
+ *     UTREE_INTERLEAVED=1   opt-in, xtree-searchGG only: fastaToSearch.fa holds both mates, records 2i and 2i+1 are pair i.  Setting both
+ *                           variables is an error (exit 1); xtree-search reads no pairs and exits with 1 when either is set
  * `threads` sizes the host formatting team (the GPU does the search).  `SPEED` is parsed and ignored, as
  * in the reference (itree.c:858, 907-918).
  */
@@ -80,6 +88,17 @@ int main(int argc, char *argv[]) {
 #endif
     printf("Using up to %d threads.\n", threads);
 
+    const char *mates = getenv("UTREE_MATES");
+    const char *ei_pairs = getenv("UTREE_INTERLEAVED");
+    const int interleaved = ei_pairs && *ei_pairs && strcmp(ei_pairs, "0");
+    if (mates && !*mates) mates = NULL;
+    if (!DO_GG && (mates || interleaved)) { fputs("ERROR: the rank-specific search reads no pairs (UTREE_MATES / UTREE_INTERLEAVED are for xtree-searchGG)\n", stderr); exit(1); }
+    if (mates && interleaved) { fputs("ERROR: UTREE_MATES and UTREE_INTERLEAVED are both set: the mates are in a file of their own or in the reads file, not both\n", stderr); exit(1); }
+    if (mates) {                                                                          /* before the tree is loaded: it may take minutes */
+        int f = open(mates, O_RDONLY);
+        if (f < 0) { puts("Invalid input files"); exit(1); }                             /* itree.c:835 */
+        close(f);
+    }
     const char *profile = getenv("UTREE_PROFILE");
     if (profile && *profile) check_report_path(profile, "profile"); else profile = NULL;
     const char *coverage = DO_GG ? getenv("UTREE_COVERAGE") : NULL;
@@ -154,7 +173,8 @@ int main(int argc, char *argv[]) {
     if (getenv("UTREE_TOLERANCE")) prm.tolerance = (uint32_t)atoi(getenv("UTREE_TOLERANCE"));
     rc = utree_rank_search_file_profile(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, &st);   /* (a NULL path: no such report) */
 #else
-    rc = utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st);   /* (a NULL path: no such report) */
+    if (mates || interleaved) rc = utree_search_pairs_file(ctr, devs, n_dev, argv[2], mates, argv[3], doRC, threads, fmt, profile, coverage, &st);
+    else rc = utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st);   /* (a NULL path: no such report) */
 #endif
     if (rc == UTREE_E_IO) { puts("Invalid input files"); exit(1); }                      /* itree.c:835 */
     if (rc == UTREE_E_FASTA) {
@@ -167,6 +187,7 @@ int main(int argc, char *argv[]) {
         }
         exit(2);
     }
+    if (rc == UTREE_E_PAIRS) { fprintf(stderr, "ERROR: %s\n", utree_last_hip_error()); exit(2); }   /* the complete pairs are written */
     if (rc && rc != UTREE_E_PROFILE && rc != UTREE_E_COVERAGE) { fprintf(stderr, "ERROR: %s\n", utree_strerror(rc)); exit(3); }
     printf("Good finds: %llu\n", (unsigned long long)st.good_finds);                      /* itree.c:1106 */
     printf("Searched %llu queries\n", (unsigned long long)st.n_reads);                    /* itree.c:1375 */

@@ -8,6 +8,10 @@
  *   formatter: format the lines with a thread team
  *   writer   : write them in input order (= what the reference writes with one thread; with more threads it
  *              writes a permutation)
+ *
+ * Paired-end input (utree_search_pairs_file) takes the same four stages with a second input: the reader frames both files and commits the
+ * pairs both buffers hold, the gpu stage uploads both mates' bytes and joins them on the device (pairs_kernels.hip) in front of the batch
+ * kernels; formatter and writer see one query per pair, named by mate 1.
  */
 #define _FILE_OFFSET_BITS 64
 #define _GNU_SOURCE
@@ -27,6 +31,7 @@
 #include "dev_image.h"
 #include "search_dev.h"
 #include "reports.h"
+#include "pairs_kernels.h"
 
 #define CHUNK_BYTES ((size_t)96 << 20)        /* must hold two maximal (16 MiB) lines                    */
 #define MAX_READS_PER_BATCH ((size_t)2 << 20)  /* more reads in a chunk (tiny reads) simply take another batch */
@@ -35,7 +40,15 @@
 #define READ_THREADS 4
 
 enum { S_EMPTY = 0, S_FRAMED, S_DONE, S_FORMATTED };
+enum { PAIRS_NONE = 0, PAIRS_TWO_FILES, PAIRS_INTERLEAVED };
 #define FMT_MAX_THREADS 16
+
+/* paired input: the second mates of a slot's pairs -- a buffer of their own (two files) or spans of the slot's buffer (interleaved) */
+typedef struct {
+    uint8_t *h_buf;                            /* pinned; two files only                                    */
+    uint64_t *seq_off, *name_off, *rel_off;
+    uint32_t *seq_len, *name_len;
+} mate_t;
 
 typedef struct {
     uint8_t *h_buf;                            /* pinned: the chunk as read from the file                   */
@@ -51,11 +64,23 @@ typedef struct {
     size_t fmt_cap[FMT_MAX_THREADS], fmt_len[FMT_MAX_THREADS];
     int fmt_T;
     uint64_t good;
+    mate_t m2;                                 /* paired input only                                         */
+    utree_pairs_meta *h_meta;                  /* pinned, one per device: what the join reported            */
 } slot_t;
 
-static int slot_alloc(slot_t *s) {
+static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev) {
     if (s->h_buf) return UTREE_OK;
-    if (hipHostMalloc((void **)&s->h_buf, CHUNK_BYTES + 64, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
+    if (paired) {
+        mate_t *m = &s->m2;
+        if (paired == PAIRS_TWO_FILES && hipHostMalloc((void **)&m->h_buf, chunk + 64, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
+        if (hipHostMalloc((void **)&m->rel_off, MAX_READS_PER_BATCH * 8, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
+        if (hipHostMalloc((void **)&m->seq_len, MAX_READS_PER_BATCH * 4, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
+        if (hipHostMalloc((void **)&s->h_meta, (size_t)n_dev * sizeof(utree_pairs_meta), hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
+        m->seq_off = (uint64_t *)malloc(MAX_READS_PER_BATCH * 8); m->name_off = (uint64_t *)malloc(MAX_READS_PER_BATCH * 8);
+        m->name_len = (uint32_t *)malloc(MAX_READS_PER_BATCH * 4);
+        if (!m->seq_off || !m->name_off || !m->name_len) return UTREE_E_NOMEM;
+    }
+    if (hipHostMalloc((void **)&s->h_buf, chunk + 64, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
     if (hipHostMalloc((void **)&s->h_res, MAX_READS_PER_BATCH * sizeof(utree_result), hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
     if (hipHostMalloc((void **)&s->rel_off, MAX_READS_PER_BATCH * 8, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
     if (hipHostMalloc((void **)&s->seq_len, MAX_READS_PER_BATCH * 4, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
@@ -68,18 +93,30 @@ typedef struct {
     utree_dev *dev;
     hipStream_t stream;
     uint8_t *d_buf; uint64_t *d_off; uint32_t *d_len; utree_result *d_out; void *d_ws; size_t ws_bytes;
+    /* paired input: the second mates as uploaded, and the joined batch the kernels see */
+    uint8_t *d_buf2, *d_joined; uint64_t *d_off2, *d_joff; uint32_t *d_len2, *d_jlen; utree_pairs_meta *d_meta; size_t joined_cap;
+    uint64_t want_total;                        /* joined bytes of the shard in flight, as the host counted them */
 } gpu_ctx;
+
+/* one input file: plain (a team of pread) or, with an opt-in format, through zlib (plain and gzip alike) */
+typedef struct { int fd; gzFile gz; off_t pos; int eof; } input_t;
 
 typedef struct {
     const utree_ctr *ctr;
     utree_reports *rep;                         /* non-NULL: the search feeds reports (reports.h)            */
     gpu_ctx *G; int n_dev;
-    int fd, fo;                                 /* input, output                                            */
-    off_t out_pos, start_off;                   /* start_off: where the input begins for this pipeline (behind what the device pipeline wrote to a pipe) */
+    input_t in[2];                              /* input; [1]: the mates file of a paired search             */
+    int fo;                                     /* output                                                   */
+    off_t out_pos;
+    int paired;                                 /* PAIRS_*                                                  */
+    size_t chunk;                               /* bytes per slot and input: CHUNK_BYTES; a paired search honours UTREE_CHUNK_BYTES */
+    const char *path[2];
+    /* what utree_last_hip_error is to say: each text has ONE writer -- the reader stage (UTREE_E_PAIRS) and the gpu stage (a join the
+     * device refused) --, and the caller's thread reads the one that belongs to the search's code once the stages have ended */
+    char msg_pairs[512], msg_join[256];
     int do_rc, host_threads;
     const utree_rank_params *rank;              /* non-NULL: the rank-specific `xtree-search` (rank.c), one device  */
     int input_format;                           /* UTREE_INPUT_*: opt-in FASTQ / multi-line FASTA (+ gzip via zlib)   */
-    gzFile gz;
     slot_t slot[NSLOTS];
     pthread_mutex_t mu; pthread_cond_t cv;
     int rc;                                     /* first error of any stage                                  */
@@ -113,67 +150,82 @@ static void set_state(pipe_t *P, slot_t *s, int state) {
 }
 
 /* ---- stage 1: read + frame ------------------------------------------------------------------- */
+/* more of `in` behind buf[0 .. *have), up to `cap` bytes in all; in->eof is set where the file ends */
+static int fill_chunk(input_t *in, uint8_t *buf, size_t *have_io, size_t cap) {
+    size_t have = *have_io;
+    if (in->eof || have >= cap) return UTREE_OK;
+    if (in->gz) {                                 /* opt-in formats: zlib reads plain and gzip input alike */
+        size_t want = cap - have, done = 0;
+        while (done < want) {
+            int r = gzread(in->gz, buf + have + done, (unsigned)(want - done > (1u << 30) ? (1u << 30) : want - done));
+            if (r < 0) return UTREE_E_IO;
+            if (r == 0) { in->eof = 1; break; }
+            done += (size_t)r;
+        }
+        have += done;
+    } else {
+        /* parallel pread: the page-cache copy is the cost; several threads stream it */
+        size_t want = cap - have;
+        ssize_t got[READ_THREADS];
+        int T = READ_THREADS;
+        const off_t file_pos = in->pos;
+        const int fd = in->fd;
+#pragma omp parallel for num_threads(T) schedule(static, 1)
+        for (int t = 0; t < T; ++t) {
+            size_t a = want * (size_t)t / (size_t)T, b = want * (size_t)(t + 1) / (size_t)T, done = 0;
+            got[t] = 0;
+            while (done < b - a) {
+                ssize_t r = pread(fd, buf + have + a + done, b - a - done, file_pos + (off_t)(a + done));
+                if (r < 0) { got[t] = -1; break; }
+                if (r == 0) break;
+                done += (size_t)r; got[t] = (ssize_t)done;
+            }
+        }
+        size_t total = 0;
+        for (int t = 0; t < T; ++t) {
+            if (got[t] < 0) return UTREE_E_IO;
+            size_t seg = want * (size_t)(t + 1) / (size_t)T - want * (size_t)t / (size_t)T;
+            total += (size_t)got[t];
+            if ((size_t)got[t] < seg) { in->eof = 1; break; }       /* short segment: end of file inside it */
+        }
+        have += total; in->pos += (off_t)total;
+    }
+    *have_io = have;
+    return UTREE_OK;
+}
+
+static int frame_chunk(int format, uint8_t *buf, size_t have, int final, size_t max_reads, uint64_t *seq_off, uint32_t *seq_len,
+                       uint64_t *name_off, uint32_t *name_len, size_t *nr, size_t *used, utree_fasta_error *ferr) {
+    return format != UTREE_INPUT_REFERENCE
+        ? utree_reads_frame(buf, have, final, format, max_reads, seq_off, seq_len, name_off, name_len, nr, used, ferr)
+        : utree_fasta_frame(buf, have, final, max_reads, seq_off, seq_len, name_off, name_len, nr, used, ferr);
+}
+
 static void *reader_main(void *arg) {
     pipe_t *P = (pipe_t *)arg;
-    off_t file_pos = P->start_off;
+    input_t *in = &P->in[0];
     size_t carry = 0;                           /* bytes of an incomplete read carried into the next chunk */
     const uint8_t *carry_src = NULL;
-    int eof = 0;
-    for (int i = 0; !eof || carry; ++i) {
+    for (int i = 0; !in->eof || carry; ++i) {
         slot_t *s = &P->slot[i % NSLOTS];
         if (!wait_state(P, s, S_EMPTY)) return NULL;
         if (i < NSLOTS) {                       /* pinned memory is slow to allocate: do it while earlier chunks are in flight */
-            int arc = slot_alloc(s);
+            int arc = slot_alloc(s, P->chunk, PAIRS_NONE, P->n_dev);
             if (arc) { set_error(P, arc); return NULL; }
         }
         if (carry) memmove(s->h_buf, carry_src, carry);
         size_t have = carry;
         double t0 = now_s();
-        if (!eof && P->gz) {                      /* opt-in formats: zlib reads plain and gzip input alike */
-            size_t want = CHUNK_BYTES - have, done = 0;
-            while (done < want) {
-                int r = gzread(P->gz, s->h_buf + have + done, (unsigned)(want - done > (1u << 30) ? (1u << 30) : want - done));
-                if (r < 0) { set_error(P, UTREE_E_IO); return NULL; }
-                if (r == 0) { eof = 1; break; }
-                done += (size_t)r;
-            }
-            have += done;
-        } else if (!eof) {
-            /* parallel pread: the page-cache copy is the cost; several threads stream it */
-            size_t want = CHUNK_BYTES - have;
-            ssize_t got[READ_THREADS];
-            int T = READ_THREADS;
-#pragma omp parallel for num_threads(T) schedule(static, 1)
-            for (int t = 0; t < T; ++t) {
-                size_t a = want * (size_t)t / (size_t)T, b = want * (size_t)(t + 1) / (size_t)T, done = 0;
-                got[t] = 0;
-                while (done < b - a) {
-                    ssize_t r = pread(P->fd, s->h_buf + have + a + done, b - a - done, file_pos + (off_t)(a + done));
-                    if (r < 0) { got[t] = -1; break; }
-                    if (r == 0) break;
-                    done += (size_t)r; got[t] = (ssize_t)done;
-                }
-            }
-            size_t total = 0;
-            for (int t = 0; t < T; ++t) {
-                if (got[t] < 0) { set_error(P, UTREE_E_IO); return NULL; }
-                size_t seg = want * (size_t)(t + 1) / (size_t)T - want * (size_t)t / (size_t)T;
-                total += (size_t)got[t];
-                if ((size_t)got[t] < seg) { eof = 1; break; }       /* short segment: end of file inside it */
-            }
-            have += total; file_pos += (off_t)total;
-        }
+        if (fill_chunk(in, s->h_buf, &have, P->chunk)) { set_error(P, UTREE_E_IO); return NULL; }
         double t1 = now_s();
+        const int eof = in->eof;
         s->have = have;
         s->nr = 0; s->used = 0; s->frame_rc = UTREE_OK; s->last = 0;
         if (have && P->input_format == UTREE_INPUT_AUTO)
             P->input_format = s->h_buf[0] == '@' ? UTREE_INPUT_FASTQ : UTREE_INPUT_FASTA_MULTILINE;
         if (have) {
-            s->frame_rc = P->input_format != UTREE_INPUT_REFERENCE
-                ? utree_reads_frame(s->h_buf, have, eof, P->input_format, MAX_READS_PER_BATCH, s->seq_off, s->seq_len, s->name_off,
-                                    s->name_len, &s->nr, &s->used, &s->ferr)
-                : utree_fasta_frame(s->h_buf, have, eof, MAX_READS_PER_BATCH, s->seq_off, s->seq_len, s->name_off,
-                                            s->name_len, &s->nr, &s->used, &s->ferr);
+            s->frame_rc = frame_chunk(P->input_format, s->h_buf, have, eof, MAX_READS_PER_BATCH, s->seq_off, s->seq_len, s->name_off,
+                                      s->name_len, &s->nr, &s->used, &s->ferr);
             if (s->frame_rc != UTREE_OK && s->frame_rc != UTREE_E_FASTA) { set_error(P, s->frame_rc); return NULL; }
             if (s->frame_rc == UTREE_OK && !s->nr && !s->used && !eof) {
                 s->frame_rc = UTREE_E_FASTA; s->ferr.code = 5; s->ferr.read_index = 0;   /* a line pair larger than a chunk */
@@ -181,11 +233,148 @@ static void *reader_main(void *arg) {
         }
         P->t_read += t1 - t0; P->t_frame += now_s() - t1;
         carry = have - s->used; carry_src = s->h_buf + s->used;
-        if (s->frame_rc == UTREE_E_FASTA) { carry = 0; eof = 1; }
-        if (eof && !carry) s->last = 1;
-        if (eof && carry && s->frame_rc == UTREE_OK && s->used == 0 && s->nr == 0) { s->last = 1; carry = 0; }
+        if (s->frame_rc == UTREE_E_FASTA) { carry = 0; in->eof = 1; }
+        if (in->eof && !carry) s->last = 1;
+        if (in->eof && carry && s->frame_rc == UTREE_OK && s->used == 0 && s->nr == 0) { s->last = 1; carry = 0; }
         set_state(P, s, S_FRAMED);
         if (s->last) break;
+    }
+    return NULL;
+}
+
+/* ---- stage 1, paired input ---------------------------------------------------------------------
+ * Both inputs are framed by the chosen format's framing; a slot commits the pairs BOTH of its buffers hold and the rest of each file goes to
+ * the next slot, so the two buffers of a slot always begin at the same pair whatever the lengths of the files' headers.  Interleaved input
+ * is one file whose records 2i and 2i+1 are pair i; an odd record at the end of a slot is carried. */
+typedef struct {                                /* what a slot did not commit: framed records [from, nr) and the bytes behind them */
+    const uint8_t *buf; const uint64_t *name_off, *seq_off; const uint32_t *seq_len;
+    size_t from, nr, used, have;
+} carry_t;
+
+/* Multi-line FASTA was compacted in place when it was framed, so a framed record is written out again as header line + sequence + '\n'
+ * (at most one byte more than it took: the file's last line may lack its newline; the buffers have 64 bytes to spare); the other formats'
+ * bytes stand as they were read and are framed again. */
+static size_t carry_over(uint8_t *dst, const carry_t *c, int format) {
+    size_t w = 0;
+    if (!c->buf) return 0;
+    if (format == UTREE_INPUT_FASTA_MULTILINE) {
+        for (size_t r = c->from; r < c->nr; ++r) {
+            const size_t a = (size_t)c->name_off[r] - 1, b = (size_t)c->seq_off[r] + c->seq_len[r];
+            memmove(dst + w, c->buf + a, b - a); w += b - a;
+            dst[w++] = '\n';
+        }
+        memmove(dst + w, c->buf + c->used, c->have - c->used); w += c->have - c->used;
+    } else {
+        const size_t a = c->from < c->nr ? (size_t)c->name_off[c->from] - 1 : c->used;
+        memmove(dst, c->buf + a, c->have - a); w = c->have - a;
+    }
+    return w;
+}
+
+/* How a slot of a paired search ends, once its np pairs are known.  Per input k: the slot commits done[k] of the nr[k] records framed in its
+ * buffer of have[k] bytes, of which framing took used[k]; frc[k] / fe[k]: a malformed record stopped the framing (it is record nr[k] of the
+ * buffer); recs[k]: records the slots before committed.  In this order:
+ *   1. a malformed record that is the NEXT record of its file (interleaved: or the mate of the next) ends the search with its own code; its
+ *      number counts that file's records.  One further on is carried and met again;
+ *   2. one file is used up -- end of file, nothing left in the buffer -- and the other's buffer holds more: UTREE_E_PAIRS (interleaved: the
+ *      file is used up with an odd record left); the slot's complete pairs go through the stages first;
+ *   3. every file is used up: the last slot;
+ *   4. no pair, and a FULL buffer that holds no complete record (interleaved: no two): "sequence too long", as for single reads;
+ *   else the next slot goes on behind done[k] (a file that ended exactly at a buffer's end is seen to be used up there). */
+static void pairs_verdict(pipe_t *P, slot_t *s, size_t np, const size_t *done, const size_t *nr, const size_t *used, const size_t *have,
+                          const int *frc, const utree_fasta_error *fe, const uint64_t *recs, uint64_t pairs) {
+    const int two = P->paired == PAIRS_TWO_FILES, nin = two ? 2 : 1;
+    int rest[2] = {0, 0}, over[2] = {0, 0};                                               /* the buffer holds more of the file; the file is used up */
+    for (int k = 0; k < nin; ++k) {
+        rest[k] = done[k] < nr[k] || used[k] < have[k];
+        over[k] = !rest[k] && P->in[k].eof;
+    }
+    for (int k = 0; k < nin; ++k)                                                         /* 1 */
+        if (frc[k] == UTREE_E_FASTA && nr[k] - done[k] <= (two ? 0u : 1u)) {
+            s->frame_rc = UTREE_E_FASTA; s->ferr = fe[k]; s->ferr.read_index += recs[k];   /* (the framing counts from the buffer's first record) */
+            return;
+        }
+    if (two && over[0] != over[1] && rest[over[0] ? 1 : 0]) {                             /* 2 */
+        const int k = over[0] ? 0 : 1;                                                    /* the shorter file */
+        s->frame_rc = UTREE_E_PAIRS;
+        snprintf(P->msg_pairs, sizeof P->msg_pairs, "paired input: %s file %s ends after %llu records, %s goes on", k ? "the mates" : "the reads",
+                 P->path[k], (unsigned long long)(recs[k] + done[k]), P->path[1 - k]);
+    } else if (!two && P->in[0].eof && used[0] >= have[0] && (nr[0] & 1)) {
+        s->frame_rc = UTREE_E_PAIRS;
+        snprintf(P->msg_pairs, sizeof P->msg_pairs, "paired input: the interleaved file %s holds an odd number of records (%llu): its last read has no mate",
+                 P->path[0], (unsigned long long)(recs[0] + nr[0]));
+    } else if (over[0] && (!two || over[1])) s->last = 1;                                 /* 3 */
+    else if (!np) {                                                                       /* 4 */
+        int full = 0;
+        for (int k = 0; k < nin; ++k) full |= have[k] >= P->chunk && nr[k] < (two ? 1u : 2u) && (k == 0 || nr[0] > 0);   /* (the mates are framed only up to the reads' count) */
+        if (full) { s->frame_rc = UTREE_E_FASTA; s->ferr.code = 5; s->ferr.read_index = pairs + 1; }
+    }
+}
+
+static void *reader_pairs_main(void *arg) {
+    pipe_t *P = (pipe_t *)arg;
+    const int two = P->paired == PAIRS_TWO_FILES, nin = two ? 2 : 1;
+    carry_t cy[2];
+    uint64_t recs[2] = {0, 0}, pairs = 0;       /* records of each file, pairs, committed by the slots before */
+    memset(cy, 0, sizeof cy);
+    for (int i = 0;; ++i) {
+        slot_t *s = &P->slot[i % NSLOTS];
+        mate_t *m = &s->m2;
+        if (!wait_state(P, s, S_EMPTY)) return NULL;
+        if (i < NSLOTS) {
+            int arc = slot_alloc(s, P->chunk, P->paired, P->n_dev);
+            if (arc) { set_error(P, arc); return NULL; }
+        }
+        uint8_t *buf[2] = {s->h_buf, m->h_buf};
+        uint64_t *seq_off[2] = {s->seq_off, m->seq_off}, *name_off[2] = {s->name_off, m->name_off};
+        uint32_t *seq_len[2] = {s->seq_len, m->seq_len}, *name_len[2] = {s->name_len, m->name_len};
+        size_t have[2] = {0, 0}, nr[2] = {0, 0}, used[2] = {0, 0};
+        int frc[2] = {UTREE_OK, UTREE_OK};
+        utree_fasta_error fe[2];
+        double t0 = now_s();
+        for (int k = 0; k < nin; ++k) {
+            have[k] = carry_over(buf[k], &cy[k], P->input_format);
+            if (fill_chunk(&P->in[k], buf[k], &have[k], P->chunk)) { set_error(P, UTREE_E_IO); return NULL; }
+        }
+        double t1 = now_s();
+        if (have[0] && P->input_format == UTREE_INPUT_AUTO)
+            P->input_format = buf[0][0] == '@' ? UTREE_INPUT_FASTQ : UTREE_INPUT_FASTA_MULTILINE;
+        for (int k = 0; k < nin; ++k) {
+            memset(&fe[k], 0, sizeof fe[k]);
+            const size_t max_reads = k ? nr[0] : MAX_READS_PER_BATCH;                     /* no more mates than reads */
+            if (!have[k] || !max_reads) continue;
+            frc[k] = frame_chunk(P->input_format, buf[k], have[k], P->in[k].eof, max_reads, seq_off[k], seq_len[k], name_off[k], name_len[k],
+                                 &nr[k], &used[k], &fe[k]);
+            if (frc[k] != UTREE_OK && frc[k] != UTREE_E_FASTA) { set_error(P, frc[k]); return NULL; }
+        }
+        size_t np = two ? (nr[0] < nr[1] ? nr[0] : nr[1]) : nr[0] / 2;
+        if (!two)                                                                         /* records 2i, 2i+1 -> pair i (an odd last record stays where it is) */
+            for (size_t r = 0; r < np; ++r) {
+                m->seq_off[r] = s->seq_off[2 * r + 1]; m->seq_len[r] = s->seq_len[2 * r + 1];
+                s->seq_off[r] = s->seq_off[2 * r]; s->seq_len[r] = s->seq_len[2 * r];
+                s->name_off[r] = s->name_off[2 * r]; s->name_len[r] = s->name_len[2 * r];
+            }
+        s->have = have[0]; s->used = used[0]; s->frame_rc = UTREE_OK; s->last = 0;
+        memset(&s->ferr, 0, sizeof s->ferr);
+        for (size_t r = 0; r < np; ++r)
+            if ((uint64_t)s->seq_len[r] + 1 + m->seq_len[r] > LINELEN_MAX) {               /* "sequence too long": the pairs before it are written */
+                np = r; s->frame_rc = UTREE_E_FASTA; s->ferr.code = 5; s->ferr.read_index = pairs + r + 1;
+                break;
+            }
+        const size_t done[2] = {two ? np : 2 * np, np};                                   /* records of each file this slot commits */
+        if (s->frame_rc == UTREE_OK) pairs_verdict(P, s, np, done, nr, used, have, frc, fe, recs, pairs);
+        if (s->frame_rc != UTREE_OK) s->last = 1;
+        s->nr = np;
+        for (int k = 0; k < nin; ++k) {
+            cy[k].buf = buf[k]; cy[k].name_off = name_off[k]; cy[k].seq_off = seq_off[k]; cy[k].seq_len = seq_len[k];
+            cy[k].from = done[k]; cy[k].nr = nr[k]; cy[k].used = used[k]; cy[k].have = have[k];
+            recs[k] += done[k];
+        }
+        pairs += np;
+        P->t_read += t1 - t0; P->t_frame += now_s() - t1;
+        const int last = s->last;
+        set_state(P, s, S_FRAMED);
+        if (last) break;
     }
     return NULL;
 }
@@ -201,12 +390,50 @@ static void *gpu_main(void *arg) {
         double t0 = now_s();
         size_t nr = s->nr, n_dev = (size_t)P->n_dev;
         size_t per = (nr + n_dev - 1) / n_dev;
+        for (size_t g = 0; g < n_dev && nr && P->paired; ++g) { memset(&s->h_meta[g], 0, sizeof s->h_meta[g]); P->G[g].want_total = 0; }
         for (size_t g = 0; g < n_dev && nr; ++g) {
             gpu_ctx *c = &P->G[g];
             size_t first = g * per; if (first > nr) first = nr;
             size_t count = first + per <= nr ? per : nr - first;
             if (!count) continue;
             size_t last = first + count - 1;
+            if (P->paired) {
+                /* both mates' byte spans and framed arrays go up as they stand; the device joins them and the batch kernels, the reports
+                 * included, see one query per pair */
+                const int two = P->paired == PAIRS_TWO_FILES;
+                mate_t *m = &s->m2;
+                size_t lo1 = (size_t)s->seq_off[first], hi1 = (size_t)s->seq_off[last] + s->seq_len[last];
+                size_t lo2 = (size_t)m->seq_off[first], hi2 = (size_t)m->seq_off[last] + m->seq_len[last];
+                if (!two) { hi1 = hi2; lo2 = lo1; }                                        /* interleaved: one span holds both */
+                uint64_t total = 0; uint32_t mx = 0;
+                for (size_t r = first; r <= last; ++r) {
+                    s->rel_off[r] = s->seq_off[r] - lo1; m->rel_off[r] = m->seq_off[r] - lo2;
+                    const uint32_t jl = s->seq_len[r] + 1u + m->seq_len[r];                /* <= LINELEN_MAX: the reader saw to it */
+                    total += jl;
+                    if (jl > mx) mx = jl;
+                }
+                if (total > c->joined_cap) { set_error(P, UTREE_E_ARG); return NULL; }     /* (cannot happen: the buffers' bytes + one per pair) */
+                HIPOK(hipSetDevice(c->dev->device));
+                HIPOK(hipMemcpyAsync(c->d_buf, s->h_buf + lo1, hi1 - lo1, hipMemcpyHostToDevice, c->stream));
+                if (two) HIPOK(hipMemcpyAsync(c->d_buf2, m->h_buf + lo2, hi2 - lo2, hipMemcpyHostToDevice, c->stream));
+                HIPOK(hipMemcpyAsync(c->d_off, s->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
+                HIPOK(hipMemcpyAsync(c->d_len, s->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
+                HIPOK(hipMemcpyAsync(c->d_off2, m->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
+                HIPOK(hipMemcpyAsync(c->d_len2, m->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
+                /* the host has the lengths: total and max_len are its own, the join's meta comes back with the results and is checked then */
+                int e = utree_pairs_join(c->dev, c->d_buf, c->d_off, c->d_len, two ? c->d_buf2 : c->d_buf, c->d_off2, c->d_len2, (uint32_t)count,
+                                         c->d_joined, total, c->d_joff, c->d_jlen, c->d_meta, c->stream);
+                if (e) { set_error(P, e); return NULL; }
+                c->want_total = total;
+                HIPOK(hipMemcpyAsync(&s->h_meta[g], c->d_meta, sizeof(utree_pairs_meta), hipMemcpyDeviceToHost, c->stream));
+                e = utree_classify_batch(c->dev, c->d_joined, c->d_joff, c->d_jlen, (uint32_t)count, total, mx, P->do_rc, c->d_out, c->d_ws,
+                                         c->ws_bytes, c->stream);
+                if (e) { set_error(P, e); return NULL; }
+                e = utree_reports_add(P->rep, (int)g, c->d_joined, c->d_joff, c->d_jlen, c->d_out, (uint32_t)count, P->do_rc, 0, c->stream);
+                if (e) { set_error(P, e); return NULL; }
+                HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
+                continue;
+            }
             size_t lo = (size_t)s->seq_off[first], hi = (size_t)s->seq_off[last] + s->seq_len[last];
             uint64_t total = 0; uint32_t mx = 0;
             for (size_t r = first; r <= last; ++r) {
@@ -230,6 +457,11 @@ static void *gpu_main(void *arg) {
             HIPOK(hipSetDevice(P->G[g].dev->device));
             HIPOK(hipStreamSynchronize(P->G[g].stream));
             if (!P->rank) { int pe = utree_classify_poll(P->G[g].dev); if (pe) { set_error(P, pe); return NULL; } }   /* the batches' error words */
+            if (P->paired && (s->h_meta[g].error || s->h_meta[g].total_bases != P->G[g].want_total)) {               /* ... and the join's */
+                snprintf(P->msg_join, sizeof P->msg_join, "the device join of a batch of pairs reported error %u, %llu joined bytes where the host counted %llu",
+                         s->h_meta[g].error, (unsigned long long)s->h_meta[g].total_bases, (unsigned long long)P->G[g].want_total);
+                set_error(P, UTREE_E_DEVICE); return NULL;
+            }
         }
         P->t_gpu += now_s() - t0;
         int last = s->last;
@@ -308,10 +540,11 @@ static void *writer_main(void *arg) {
         int last = s->last;
         if (s->frame_rc == UTREE_E_FASTA) {                                       /* reads before the bad one are written */
             P->st.fasta_error = s->ferr;
-            P->st.fasta_error.read_index += P->st.n_reads - nr;
+            if (!P->paired) P->st.fasta_error.read_index += P->st.n_reads - nr;   /* (a paired reader counts each file's records itself) */
             set_error(P, UTREE_E_FASTA);
             break;
         }
+        if (s->frame_rc == UTREE_E_PAIRS) { set_error(P, UTREE_E_PAIRS); break; } /* ... and the complete pairs before a file ran out */
         set_state(P, s, S_EMPTY);
         if (last) break;
     }
@@ -326,15 +559,32 @@ static void free_ctx(gpu_ctx *g) {
     if (g->d_len) hipFree(g->d_len);
     if (g->d_out) hipFree(g->d_out);
     if (g->d_ws) hipFree(g->d_ws);
+    if (g->d_buf2) hipFree(g->d_buf2);
+    if (g->d_joined) hipFree(g->d_joined);
+    if (g->d_off2) hipFree(g->d_off2);
+    if (g->d_len2) hipFree(g->d_len2);
+    if (g->d_joff) hipFree(g->d_joff);
+    if (g->d_jlen) hipFree(g->d_jlen);
+    if (g->d_meta) hipFree(g->d_meta);
     if (g->stream) hipStreamDestroy(g->stream);
 }
 
 #define HIPM(x) do { if ((x) != hipSuccess) { rc = UTREE_E_HIP; goto done; } } while (0)
 
-static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
-                       int do_rc, const utree_rank_params *rank, int host_threads, int input_format, utree_reports *rep,
+/* bytes per slot and input of a paired search: CHUNK_BYTES; UTREE_CHUNK_BYTES lowers it as it does for the device pipeline (tests: many slot
+ * boundaries and a carry in each file of a small input) */
+static size_t pairs_chunk_bytes(void) {
+    const char *e = getenv("UTREE_CHUNK_BYTES");
+    if (e && atoll(e) >= 64 && (size_t)atoll(e) < CHUNK_BYTES) return (size_t)atoll(e);
+    return CHUNK_BYTES;
+}
+
+/* paired: PAIRS_TWO_FILES (mates_path holds the second mates) or PAIRS_INTERLEAVED (fasta_path holds both), GG search only */
+static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *mates_path, int paired,
+                       const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format, utree_reports *rep,
                        utree_search_stats *stats) {
     if (!ctr || !devs || n_dev < 1 || !fasta_path || !out_path || input_format < 0 || input_format > UTREE_INPUT_AUTO) return UTREE_E_ARG;
+    if (paired && (rank || (paired == PAIRS_TWO_FILES) != (mates_path != NULL))) return UTREE_E_ARG;
     int rc = UTREE_OK;
     uint64_t dev_printed = 0;
     utree_search_resume resume;
@@ -342,7 +592,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     /* The GG search on the reference's input format takes the device text pipeline (search_dev.c); it hands back input it
      * does not take -- malformed records, NUL bytes, lines fgets would split -- and the host framing below then reproduces
      * the reference on it case by case.  UTREE_HOST_TEXT=1 forces the host pipeline (tests, A/B). */
-    if (!rank && input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
+    if (!rank && !paired && input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
         rc = utree_search_file_device(ctr, devs, n_dev, fasta_path, out_path, do_rc, host_threads, rep, stats, &dev_printed, &resume);
         if (rc != UTREE_RETRY_HOST) return rc;
         rc = UTREE_OK;
@@ -355,10 +605,14 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     if (!P) { if (resume.fo >= 0) close(resume.fo); return UTREE_E_NOMEM; }
     P->ctr = ctr; P->rep = rep; P->n_dev = n_dev; P->do_rc = do_rc; P->rank = rank; P->input_format = input_format;
     P->progress_printed = dev_printed;
-    P->fd = open(fasta_path, O_RDONLY);
+    P->paired = paired; P->chunk = paired ? pairs_chunk_bytes() : CHUNK_BYTES;
+    P->path[0] = fasta_path; P->path[1] = mates_path;
+    P->in[1].fd = -1;
+    P->in[0].fd = open(fasta_path, O_RDONLY);
+    if (paired == PAIRS_TWO_FILES && P->in[0].fd >= 0 && (P->in[1].fd = open(mates_path, O_RDONLY)) < 0) { close(P->in[0].fd); P->in[0].fd = -1; }
     if (resume.fo >= 0) {
         /* the output is a pipe and the device pipeline has written the chunks in front of `in_off`: go on from there, on the same descriptor */
-        P->fo = resume.fo; P->start_off = (off_t)resume.in_off;
+        P->fo = resume.fo; P->in[0].pos = (off_t)resume.in_off;
         P->st.n_reads = resume.n_reads; P->st.good_finds = resume.good_finds; P->st.bytes_in = resume.bytes_in; P->st.bytes_out = resume.bytes_out;
     } else if (utree_output_parts() > 1) {
         /* UTREE_OUTPUT_PARTS: this pipeline writes in input order with one writer, so all of the output is part 000 and the other parts are
@@ -371,16 +625,23 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
         }
     } else
     P->fo = open(out_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);                   /* fopen(outfile, "wb"), itree.c:834 */
-    if (P->fd < 0 || P->fo < 0) {                                                 /* itree.c:835 */
-        if (P->fd >= 0) close(P->fd);
+    if (P->in[0].fd < 0 || P->fo < 0) {                                           /* itree.c:835 */
+        if (P->in[0].fd >= 0) close(P->in[0].fd);
+        if (P->in[1].fd >= 0) close(P->in[1].fd);
         if (P->fo >= 0) close(P->fo);
         free(P);
         return UTREE_E_IO;
     }
-    if (input_format != UTREE_INPUT_REFERENCE) {
-        P->gz = gzdopen(dup(P->fd), "rb");
-        if (!P->gz) { close(P->fd); close(P->fo); free(P); return UTREE_E_IO; }
-        gzbuffer(P->gz, 1u << 20);
+    for (int k = 0; k < 2 && input_format != UTREE_INPUT_REFERENCE; ++k) {
+        if (P->in[k].fd < 0) continue;
+        P->in[k].gz = gzdopen(dup(P->in[k].fd), "rb");
+        if (!P->in[k].gz) {
+            if (P->in[0].gz) gzclose(P->in[0].gz);
+            close(P->in[0].fd); if (P->in[1].fd >= 0) close(P->in[1].fd);
+            close(P->fo); free(P);
+            return UTREE_E_IO;
+        }
+        gzbuffer(P->in[k].gz, 1u << 20);
     }
 #ifdef _OPENMP
     if (host_threads <= 0) host_threads = omp_get_max_threads();
@@ -399,18 +660,28 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
         c->dev = devs[g];
         HIPM(hipSetDevice(devs[g]->device));
         HIPM(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        HIPM(hipMalloc((void **)&c->d_buf, CHUNK_BYTES + 64));
+        HIPM(hipMalloc((void **)&c->d_buf, P->chunk + 64));
         HIPM(hipMalloc((void **)&c->d_off, MAX_READS_PER_BATCH * 8));
         HIPM(hipMalloc((void **)&c->d_len, MAX_READS_PER_BATCH * 4));
         HIPM(hipMalloc((void **)&c->d_out, MAX_READS_PER_BATCH * sizeof(utree_result)));
+        if (paired) {                                                             /* the second mates, and the joined batch: both buffers' bytes + an 'N' per pair */
+            c->joined_cap = (paired == PAIRS_TWO_FILES ? 2 : 1) * P->chunk + MAX_READS_PER_BATCH;
+            if (paired == PAIRS_TWO_FILES) HIPM(hipMalloc((void **)&c->d_buf2, P->chunk + 64));
+            HIPM(hipMalloc((void **)&c->d_joined, c->joined_cap + 64));
+            HIPM(hipMalloc((void **)&c->d_off2, MAX_READS_PER_BATCH * 8));
+            HIPM(hipMalloc((void **)&c->d_len2, MAX_READS_PER_BATCH * 4));
+            HIPM(hipMalloc((void **)&c->d_joff, MAX_READS_PER_BATCH * 8));
+            HIPM(hipMalloc((void **)&c->d_jlen, MAX_READS_PER_BATCH * 4));
+            HIPM(hipMalloc((void **)&c->d_meta, sizeof(utree_pairs_meta)));
+        }
         c->ws_bytes = rank ? utree_rank_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, CHUNK_BYTES, LINELEN_MAX, do_rc, rank)
-                           : utree_classify_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, CHUNK_BYTES, LINELEN_MAX, do_rc);
+                           : utree_classify_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, paired ? c->joined_cap : CHUNK_BYTES, LINELEN_MAX, do_rc);
         if (!c->ws_bytes) { rc = UTREE_E_ARG; goto done; }
         HIPM(hipMalloc(&c->d_ws, c->ws_bytes));
     }
     {
         pthread_t tr, tg, tf, tw;
-        pthread_create(&tr, NULL, reader_main, P);
+        pthread_create(&tr, NULL, paired ? reader_pairs_main : reader_main, P);
         pthread_create(&tg, NULL, gpu_main, P);
         pthread_create(&tf, NULL, format_main, P);
         pthread_create(&tw, NULL, writer_main, P);
@@ -421,10 +692,14 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
         pthread_join(tg, NULL);
         pthread_join(tf, NULL);
         rc = P->rc;
+        if (rc == UTREE_E_PAIRS) utree_set_error_text(P->msg_pairs);               /* (the text is per thread, and this is the caller's) */
+        else if (rc == UTREE_E_DEVICE && P->msg_join[0]) utree_set_error_text(P->msg_join);
     }
 done:
-    if (P->gz) gzclose(P->gz);
-    if (P->fd >= 0) close(P->fd);
+    for (int k = 0; k < 2; ++k) {
+        if (P->in[k].gz) gzclose(P->in[k].gz);
+        if (P->in[k].fd >= 0) close(P->in[k].fd);
+    }
     if (P->fo >= 0) close(P->fo);
     if (P->G) { for (int g = 0; g < n_dev; ++g) free_ctx(&P->G[g]); free(P->G); }
     for (int i = 0; i < NSLOTS; ++i) {
@@ -434,6 +709,11 @@ done:
         if (s->rel_off) hipHostFree(s->rel_off);
         if (s->seq_len) hipHostFree(s->seq_len);
         free(s->seq_off); free(s->name_off); free(s->name_len);
+        if (s->m2.h_buf) hipHostFree(s->m2.h_buf);
+        if (s->m2.rel_off) hipHostFree(s->m2.rel_off);
+        if (s->m2.seq_len) hipHostFree(s->m2.seq_len);
+        if (s->h_meta) hipHostFree(s->h_meta);
+        free(s->m2.seq_off); free(s->m2.name_off); free(s->m2.name_len);
         for (int t = 0; t < FMT_MAX_THREADS; ++t) free(s->fmt_buf[t]);
     }
     P->st.seconds_total = now_s() - t_start;
@@ -455,15 +735,15 @@ done:
  * in, out, 0, speed, doRC) (itree.c:1376 without DO_GG): the same pipeline, the batches to ONE device in file order because each read's vote
  * depends on the reads before it (rank.c).  profile_path / coverage_path: NULL, or the report to feed while searching and to write when the
  * search has succeeded (the search's own codes stay its own). */
-static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
-                          const utree_rank_params *rank, int host_threads, int input_format, const char *profile_path,
-                          const char *coverage_path, utree_search_stats *stats) {
+static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int paired,
+                          const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format,
+                          const char *profile_path, const char *coverage_path, utree_search_stats *stats) {
     utree_reports *rep = NULL;
     utree_search_stats st;
     memset(&st, 0, sizeof st);
     int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, &rep);
-    if (!rc && !rep) return search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, rank, host_threads, input_format, NULL, stats);   /* no report asked for */
-    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, out_path, do_rc, rank, host_threads, input_format, rep, &st);
+    if (!rc && !rep) return search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, NULL, stats);   /* no report asked for */
+    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, rep, &st);
     if (!rc) rc = utree_reports_write(rep, ctr, st.n_reads);
     utree_reports_free(rep);
     if (stats) *stats = st;
@@ -472,20 +752,42 @@ static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, con
 
 int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
                       int do_rc, int host_threads, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, fasta_path, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, stats);
+    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, stats);
 }
 int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
                            int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, stats);
 }
 int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                               int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, stats);
 }
 int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                                int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                                utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, stats);
+}
+
+/* pairs: both mates of a pair cast one vote (include/utree_amd.h) */
+int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, const char *out_path,
+                            int do_rc, int host_threads, int input_format, const char *profile_path, const char *coverage_path,
+                            utree_search_stats *stats) {
+    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : PAIRS_INTERLEAVED, out_path, do_rc, NULL,
+                          host_threads, input_format, profile_path, coverage_path, stats);
+}
+
+int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_off1, const uint32_t *d_len1, const uint8_t *d_bases2,
+                     const uint64_t *d_off2, const uint32_t *d_len2, uint32_t n_pairs, uint8_t *d_joined, uint64_t joined_capacity,
+                     uint64_t *d_joff, uint32_t *d_jlen, utree_pairs_meta *d_meta, void *stream) {
+    if (!dev || !d_meta) return UTREE_E_ARG;
+    if (n_pairs && (!d_bases1 || !d_off1 || !d_len1 || !d_bases2 || !d_off2 || !d_len2 || !d_joff || !d_jlen || (!d_joined && joined_capacity)))
+        return UTREE_E_ARG;
+    hipError_t e = hipMemsetAsync(d_meta, 0, sizeof *d_meta, (hipStream_t)stream);
+    if (e == hipSuccess && n_pairs)
+        e = (hipError_t)utk_pairs_join(d_bases1, d_off1, d_len1, d_bases2, d_off2, d_len2, n_pairs, d_joined, joined_capacity, d_joff, d_jlen,
+                                       d_meta, stream);
+    if (e != hipSuccess) { utree_dev_set_hip_error((int)e, "utree_pairs_join"); return UTREE_E_HIP; }
+    return UTREE_OK;
 }
 
 int utree_rank_search_file(const utree_ctr *ctr, utree_dev *dev, const char *fasta_path, const char *out_path, int do_rc,
@@ -502,5 +804,5 @@ int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const c
     if (!dev || !params) return UTREE_E_ARG;
     int rc = utree_rank_reset(dev);
     if (rc) return rc;
-    return search_request(ctr, &dev, 1, reads_path, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, stats);
+    return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, stats);
 }

@@ -17,7 +17,7 @@ BUILD_GG_CLI_PATH = os.path.join(_HERE, "utree-buildGG")
 BUILD_CLI_PATH = os.path.join(_HERE, "utree-build")
 _LIB = None
 
-OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE = range(14)
+OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE, E_PAIRS = range(15)
 BUILD_E_MAP_EMPTY, BUILD_E_MAP, BUILD_E_FASTA, BUILD_E_NO_KMERS, BUILD_E_NAME = range(1, 6)
 FINE_AUTO = -1
 FANOUT_NONE, FANOUT_BROADCAST, FANOUT_UPLOAD = range(3)
@@ -76,6 +76,11 @@ class ProfileEntry(C.Structure):
 class CoverageEntry(C.Structure):
     """utree_coverage_entry: per label, the records the dump holds, the distinct ones hit, the hits."""
     _fields_ = [("label", C.c_uint32), ("pad", C.c_uint32), ("db_kmers", C.c_uint64), ("covered", C.c_uint64), ("hits", C.c_uint64)]
+
+
+class PairsMeta(C.Structure):
+    """utree_pairs_meta: what the device join of a batch of pairs reports (error 0, 1 joined buffer too small, 2 a pair too long)."""
+    _fields_ = [("total_bases", C.c_uint64), ("max_len", C.c_uint32), ("error", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -166,6 +171,10 @@ SYMBOLS = {
     "utree_coverage_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p]),
     "utree_search_file_coverage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                              C.c_int, C.c_char_p, C.c_char_p, C.POINTER(SearchStats)]),
+    "utree_pairs_join": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "utree_search_pairs_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
+                                          C.c_int, C.c_char_p, C.c_char_p, C.POINTER(SearchStats)]),
     "utree_rank_search_file_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RankParams),
                                                  C.c_int, C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
 }
@@ -186,7 +195,7 @@ class UtreeError(RuntimeError):
     def __init__(self, code, what=""):
         self.code = code
         msg = load().utree_strerror(code).decode() if _LIB is not None else str(code)
-        if _LIB is not None and code in (4, 5, 11, 12, 13):    # UTREE_E_NOMEM, UTREE_E_HIP, UTREE_E_DEVICE: which call, and what the runtime said; UTREE_E_PROFILE / UTREE_E_COVERAGE: why
+        if _LIB is not None and code in (4, 5, 11, 12, 13, 14):    # UTREE_E_NOMEM, UTREE_E_HIP, UTREE_E_DEVICE: which call, and what the runtime said; UTREE_E_PROFILE / UTREE_E_COVERAGE: why; UTREE_E_PAIRS: which file ended first
             hip = (_LIB.utree_last_hip_error() or b"").decode(errors="replace")
             if hip:
                 msg += " [" + hip + "]"

@@ -5,6 +5,8 @@
     tree.get_ix(words)               ~ IXTYPE XT_getIX32(UTree*, WTYPE word)             itree.c:720
     tree.classify(bases, off, len)   ~ the per-read body of XT_doSearch32, GG branch     itree.c:891-1088
     search_gg(db, trees, in, out)    ~ size_t XT_doSearch32(utree, in, out, 8, 0, doRC)  itree.c:833
+    search_gg(..., mates=, interleaved=)   the same over paired-end reads: both mates of a pair cast one vote
+    tree.join_pairs(...)             the device join in front of classify(): mate 1 + 'N' + mate 2 per pair
     tree.profile(capacity)           per-taxon read counts of classified batches (no counterpart in the reference)
     tree.coverage()                  per-taxon database k-mers, distinct ones hit, hits (no counterpart in the reference)
 
@@ -271,6 +273,34 @@ class DeviceTree:
                                                     workspace.numel(), stream), "utree_classify_batch")
         return out
 
+    def join_pairs(self, bases1, off1, len1, bases2, off2, len2, capacity: Optional[int] = None):
+        """utree_pairs_join: per pair mate 1 + 'N' + mate 2 as one query.  Mates as classify() takes reads (uint8 / int64 / int32 CUDA tensors,
+        any alignment and order; both may lie in one buffer).  capacity: bytes of the joined buffer (default: total1 + total2 + pairs).
+        Returns (joined, joff, jlen, meta): uint8 [capacity], int64 [n] and int32 [n] CUDA tensors for classify(), and meta = the dict
+        {total_bases, max_len, error} read back once the stream has drained (error != 0: capacity too small or a pair too long -- nothing
+        was joined)."""
+        import torch
+        dev = self.info.device
+        for t, dt in ((bases1, torch.uint8), (off1, torch.int64), (len1, torch.int32), (bases2, torch.uint8), (off2, torch.int64), (len2, torch.int32)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.is_cuda and t.device.index == dev):
+                raise ValueError("join_pairs: bases / off / len must be contiguous uint8 / int64 / int32 tensors on cuda:%d" % dev)
+        n = off1.numel()
+        if not (len1.numel() == off2.numel() == len2.numel() == n):
+            raise ValueError("join_pairs: the four offset and length tensors must have one entry per pair")
+        if capacity is None:
+            capacity = int(len1.sum().item()) + int(len2.sum().item()) + n
+        joined = torch.empty(capacity, dtype=torch.uint8, device=bases1.device)
+        joff = torch.empty(n, dtype=torch.int64, device=bases1.device)
+        jlen = torch.empty(n, dtype=torch.int32, device=bases1.device)
+        d_meta = torch.zeros(2, dtype=torch.int64, device=bases1.device)
+        stream = torch.cuda.current_stream(bases1.device)
+        _lib.check(_lib.load().utree_pairs_join(self._h, bases1.data_ptr(), off1.data_ptr(), len1.data_ptr(), bases2.data_ptr(), off2.data_ptr(),
+                                                len2.data_ptr(), n, joined.data_ptr(), capacity, joff.data_ptr(), jlen.data_ptr(),
+                                                d_meta.data_ptr(), stream.cuda_stream), "utree_pairs_join")
+        stream.synchronize()
+        m = _lib.PairsMeta.from_buffer_copy(d_meta.cpu().numpy().tobytes())
+        return joined, joff, jlen, dict(total_bases=int(m.total_bases), max_len=int(m.max_len), error=int(m.error))
+
     def poll(self):
         """utree_classify_poll: raises UtreeError(E_DEVICE) if a batch that has finished since the last call found its workspace
         too small (call after the stream has drained; its results are not to be used)."""
@@ -481,13 +511,25 @@ def write_coverage(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
 
 
 def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: bool = False, threads: int = 0,
-              input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None):
+              input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None,
+              mates: Optional[str] = None, interleaved: bool = False):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
     FASTA / gzip input.  profile: also write the per-taxon read counts there; coverage: also write the per-taxon k-mer
-    coverage there (utree_search_file_coverage; None: no such report)."""
+    coverage there (utree_search_file_coverage; None: no such report).
+    Paired-end reads (utree_search_pairs_file): mates = the file of second mates, or interleaved=True when `fasta` holds records 2i and
+    2i+1 of pair i.  A pair is searched as mate 1 + "N" + mate 2, named by mate 1 (mate names are not compared); stats.n_reads counts
+    pairs; unequal record counts return E_PAIRS after the complete pairs were written."""
+    if mates is not None and interleaved:
+        raise ValueError("search_gg: give mates= or interleaved=True, not both")
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     st = _lib.SearchStats()
+    if mates is not None or interleaved:
+        code = _lib.load().utree_search_pairs_file(db._h, arr, len(trees), fasta.encode(), mates.encode() if mates is not None else None,
+                                                   out.encode(), int(rc), threads, input_format,
+                                                   profile.encode() if profile is not None else None,
+                                                   coverage.encode() if coverage is not None else None, C.byref(st))
+        return code, st
     code = _lib.load().utree_search_file_coverage(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads, input_format,
                                                   profile.encode() if profile is not None else None,
                                                   coverage.encode() if coverage is not None else None, C.byref(st))
