@@ -53,7 +53,7 @@ enum {
 const char *utree_strerror(int code);
 /* what the calling thread's last UTREE_E_HIP / UTREE_E_DEVICE was: the failing HIP call and the runtime's message for it (no
  * counterpart in the reference, which has no device; "" when there was none); after UTREE_E_PROFILE / UTREE_E_COVERAGE, why the
- * file was not written; after UTREE_E_PAIRS, which file ended first */
+ * file (profile, redistribution, coverage) was not written; after UTREE_E_PAIRS, which file ended first */
 const char *utree_last_hip_error(void);
 int utree_abi_version(void);
 
@@ -457,6 +457,81 @@ int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_
 int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
                             const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
                             const char *coverage_path, utree_search_stats *stats);
+
+/* ------------------------------------------------------------------------------------------------
+ * Redistribution of ambiguous reads among tied labels (no counterpart in itree.c; the "capitalist redistribution" of the same author's
+ * xtree, xtree.c:1190-1234 and 1321-1403, which the reference's README names as the condition of its recall claim: "after Bracken-like
+ * redistribution of lower-rank hits").  The vote interpolates a read that hits two sibling species three times each to their genus; this
+ * step instead keeps the labels a read hit most often and lets the sample decide among them.  GG search only.
+ *   Hits.  For a read (or a joined pair; with RC the read + 'N' + its reverse complement) a window is a HIT when XT_getIX32 ends on a record
+ *     whose stored label index is < n_labels, as for the coverage above; c[l] = hit windows with file-order label index l.
+ *   Candidates.  A read's candidate SET is { l : c[l] == max c }: none without a hit (the read stays unclassified), exactly the label of a
+ *     read with one distinct label, no cap on the size.  Labels are label INDICES: two indices with one text are two labels until the file
+ *     is written.
+ *   Passes.  N = reads searched (a pair counts once), T0[l] = reads whose set contains l.  win(S, T) = the l in S with the largest T[l], the
+ *     SMALLEST file-order index among equal tallies.  Pass p = 1, 2, ... computes T_p[l] = reads with win(S, T_{p-1}) == l and
+ *     changes_p = sum over l of |T_p[l] - T_{p-1}[l]|; passes run while p <= max_passes and, after the first, while the previous
+ *     changes > N / 100000 (integer division, xtree.c:1360-1362).  At least one pass runs; max_passes = 1 is xtree's fast mode.  With P
+ *     passes run, assigned[l] = reads with win(S, T_P) == l (the final assignment of xtree.c:1389-1398: one more evaluation, not T_P itself),
+ *     unique[l] = reads whose set is exactly {l}, ambiguous = reads with more than one candidate.
+ *   xtree's special case for an empty taxonomy string (firstIx) is NOT taken over: a label is a label.
+ * File layout (labels of equal text merged at write time, as the profile does; keyed on `assigned`):
+ *     # reads\t<N>\tclassified\t<G>\tunclassified\t<N-G>\tambiguous\t<A>\tpasses\t<P>\n
+ *     # taxon\tassigned\tunique\tclade_assigned\tclade_unique\n
+ *     <s>\t...\n    for every label text with assigned > 0 and every ';'-prefix of one, in unsigned bytewise order (shorter first)
+ * G is the profile's `classified` (every read with found > 0 has a candidate): the `assigned` column sums to it.
+ * What this is not: a read whose best label is itself an interior taxon stays there (BUILD_GG relabels colliding k-mers to shorter labels,
+ * itree.c:268-307); there is no genome-length or k-mer-distribution normalisation; there is no per-read reassignment output.
+ *
+ * A handle lives on ONE device for one database: a 64-bit counter per label for the single-candidate reads, an open-addressed table of the
+ * multi-label sets with their read counts (16 B a slot) and an arena of eight labels per slot for the sets' members.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct utree_redist utree_redist;
+#define UTREE_REDIST_DEFAULT_CAPACITY (1u << 22)
+#define UTREE_REDIST_DEFAULT_PASSES 100
+/* set_capacity: slots of the table of multi-label sets (rounded up to a power of two, at most 2^28) -- keep it at twice the distinct sets a
+ * search can produce. */
+int utree_redist_create(utree_dev *dev, uint32_t set_capacity, utree_redist **out);
+/* Forgets every set (synchronous: waits for the device first). */
+int utree_redist_reset(utree_redist *rd);
+void utree_redist_free(utree_redist *rd);
+/* utree_classify_batch (same arguments, `dev` = the image rd was created for; d_out bit for bit the same) that also adds the candidate sets
+ * of the batch's reads to rd: ONE more kernel between the classify kernels and the vote, which reads the per-read label lists the vote
+ * consumes.  Any number of streams may add to one handle at the same time. */
+int utree_redist_classify_batch(utree_redist *rd, utree_dev *dev, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                                uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace,
+                                size_t workspace_bytes, void *stream);
+typedef struct { uint64_t reads, first; uint32_t n, pad; } utree_redist_set;
+/* The read-back (synchronous): every distinct candidate set with its read count -- set i is the file-order label indices
+ * h_labels[h_sets[i].first .. + h_sets[i].n), in no particular order, single-label sets included.  *n_sets / *n_labels = what there is;
+ * UTREE_E_ARG when set_cap / label_cap are smaller (nothing is written then: call with 0, 0 to size the arrays).  *n_reads = reads added,
+ * *n_classified = the sum of the sets' reads (either may be NULL).  UTREE_E_DEVICE when the table or the arena was too small for a batch:
+ * the sets are then incomplete. */
+int utree_redist_read(utree_redist *rd, utree_redist_set *h_sets, size_t set_cap, uint32_t *h_labels, size_t label_cap, size_t *n_sets,
+                      size_t *n_labels, uint64_t *n_reads, uint64_t *n_classified);
+/* dst += src: src's sets re-inserted into dst, its counters and reads added (synchronous; the handles may be on different devices, same
+ * database). */
+int utree_redist_merge(utree_redist *dst, utree_redist *src);
+typedef struct { uint32_t label, pad; uint64_t assigned, unique; } utree_redist_entry;
+/* The passes, on the device (synchronous; max_passes 1 .. 1000).  One entry per label with a non-zero figure, index order; *n = their number
+ * (UTREE_E_ARG if that exceeds cap; cap = the database's labels always suffices); *passes = P, *ambiguous = A (either may be NULL).  The
+ * handle keeps its sets: more batches may be added and solved again.  UTREE_E_DEVICE as for utree_redist_read. */
+int utree_redist_solve(utree_redist *rd, uint32_t max_passes, utree_redist_entry *h, size_t cap, size_t *n, uint32_t *passes, uint64_t *ambiguous);
+/* Host only: entries (label indices of ctr; several with one label are added up) -> merged by text, rolled up, written to `path`. */
+int utree_redist_write(const utree_ctr *ctr, const utree_redist_entry *e, size_t n, uint64_t n_reads, uint64_t ambiguous, uint32_t passes,
+                       const char *path);
+/* utree_search_pairs_file that also writes the redistribution of the search to `redistribute_path` (NULL: exactly the existing calls -- no
+ * handle, no launch).  Single reads: mates_path NULL and interleaved 0 (then the pipelines of utree_search_file_coverage); pairs: mates_path,
+ * or interleaved != 0.  One handle per device handle (UTREE_REDIST_CAPACITY slots, default 2^22), merged into the first and solved with
+ * max_passes (0: the default) before the file is written -- after the coverage, before the profile.  A search that succeeds but whose
+ * redistribution cannot be written -- the file, a table too small, the devices did not add every read once -- returns UTREE_E_PROFILE (there
+ * is no code of its own) and utree_last_hip_error names the redistribution file and the cause; a search that fails leaves the path as it was.
+ * (A search into a pipe that the host pipeline has to take over half-way cannot take back the sets of the chunks it drops: it ends with this
+ * error rather than a wrong table.) */
+int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                                   int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
+                                   const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
+                                   utree_search_stats *stats);
 
 /* ------------------------------------------------------------------------------------------------
  * `.ubt` -> `.ctr` = XT_cmp32(filename, outfile) (itree.c:1234-1315; `xtree-compress`), SURVEY.md §8(f) rank 2.

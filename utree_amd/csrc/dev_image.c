@@ -889,6 +889,14 @@ size_t utree_classify_workspace_bytes(const utree_dev *dev, uint32_t n_reads, ui
 int utree_classify_batch(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
                          uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out,
                          void *d_workspace, size_t workspace_bytes, void *stream) {
+    return utree_classify_batch_redist(d, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream, NULL);
+}
+
+/* rd: NULL (utree_classify_batch: nothing new is launched), or the redistribution handle the batch's candidate sets go into -- one more
+ * pass over the records between the classify kernels and the vote, while each read's (rank, count) list still stands (redist.c) */
+int utree_classify_batch_redist(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                                uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out,
+                                void *d_workspace, size_t workspace_bytes, void *stream, struct utree_redist *rd) {
     int rc = UTREE_OK;
     if (!d || !d_out || (!d_workspace && n_reads)) return UTREE_E_ARG;
     if (!n_reads) return UTREE_OK;
@@ -968,6 +976,7 @@ int utree_classify_batch(utree_dev *d, const uint8_t *d_bases, const uint64_t *d
             if (e0) { HIPCHK(hipEventRecord(e1, st)); d->recorded[tslot] = 1; }
         }
     }
+    if (rd && (rc = utree_redist_add_pending(rd, &d->kimg, d_out, &w, n_reads, d->n_cu, st))) goto fail;     /* every path has converged here */
     KCHK(utk_vote(&d->kimg, d_out, &w, n_reads, st));
     /* the reads the lane pass left, and the batch's error word, come back behind the kernels without a wait */
     if (ring_post(d, &w, lanes ? n_reads : 0, st)) { (void)hipGetLastError(); }

@@ -37,6 +37,15 @@ struct utree_dev {
     void *search_ctx;
 };
 
+/* utree_classify_batch with the candidate sets of the batch added to `rd` (NULL: none) in front of the vote; redist.c */
+struct utree_redist;
+int utree_classify_batch_redist(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads,
+                                uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace, size_t workspace_bytes,
+                                void *stream, struct utree_redist *rd);
+int utree_redist_add_pending(struct utree_redist *rd, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, uint32_t n_reads,
+                             int n_cu, void *stream);
+int utree_redist_reads(struct utree_redist *rd, uint64_t *n_reads);
+
 void utree_dev_set_hip_error(int err, const char *what);
 const char *utree_last_hip_error(void);
 void utree_set_error_text(const char *msg);   /* what utree_last_hip_error returns next, for errors that are not HIP's */

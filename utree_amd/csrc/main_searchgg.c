@@ -25,6 +25,12 @@
  *                           DISTINCT ones the sample hit and the hits (include/utree_amd.h: utree_coverage_write), collected on the GPU
  *                           while it searches; needs the node dump a second time in HBM (utree_coverage_bytes).  Path checks, failures and
  *                           exit codes as for UTREE_PROFILE, with which it may be combined.  Unset: nothing of it runs
+ *     UTREE_REDISTRIBUTE=<path> opt-in, xtree-searchGG only (xtree-search ignores it): also write the sample's reads redistributed among the labels
+ *                           each read hit most often (include/utree_amd.h: utree_redist_write) -- the candidate sets are collected on the GPU
+ *                           while it searches, one more pass per batch, and iterated there after the search.  Path checks, failures and exit
+ *                           codes as for UTREE_PROFILE, with which and with UTREE_COVERAGE / UTREE_MATES it may be combined.
+ *                           UTREE_REDIST_PASSES=<1..1000> caps the passes (default 100; 1: one pass, xtree's fast mode),
+ *                           UTREE_REDIST_CAPACITY=<slots> sizes the table of distinct sets (default 2^22).  Unset: nothing of it runs
  *     UTREE_MATES=<path>    opt-in, xtree-searchGG only: paired-end reads.  fastaToSearch.fa holds the first mates, <path> the second; pair i is
  *                           record i of both.  A pair is searched as ONE query, mate 1 + "N" + mate 2, and prints one line under mate 1's name
  *                           (include/utree_amd.h: utree_search_pairs_file; mate names are not compared); "Searched N queries" and the profile
@@ -103,6 +109,15 @@ int main(int argc, char *argv[]) {
     if (profile && *profile) check_report_path(profile, "profile"); else profile = NULL;
     const char *coverage = DO_GG ? getenv("UTREE_COVERAGE") : NULL;
     if (coverage && *coverage) check_report_path(coverage, "coverage"); else coverage = NULL;
+    const char *redist = DO_GG ? getenv("UTREE_REDISTRIBUTE") : NULL;
+    if (redist && *redist) check_report_path(redist, "redistribution"); else redist = NULL;
+    unsigned redist_passes = 0;                                                           /* 0: the default */
+    if (redist && getenv("UTREE_REDIST_PASSES")) {
+        const long v = atol(getenv("UTREE_REDIST_PASSES"));
+        if (v < 1 || v > 1000) { fputs("ERROR: UTREE_REDIST_PASSES must be 1 .. 1000\n", stderr); exit(1); }
+        redist_passes = (unsigned)v;
+    }
+    (void)redist_passes;                                                                  /* (xtree-search: no redistribution) */
 
     utree_ctr *ctr = NULL;
     int rc = utree_ctr_open(argv[1], &ctr);
@@ -173,7 +188,8 @@ int main(int argc, char *argv[]) {
     if (getenv("UTREE_TOLERANCE")) prm.tolerance = (uint32_t)atoi(getenv("UTREE_TOLERANCE"));
     rc = utree_rank_search_file_profile(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, &st);   /* (a NULL path: no such report) */
 #else
-    if (mates || interleaved) rc = utree_search_pairs_file(ctr, devs, n_dev, argv[2], mates, argv[3], doRC, threads, fmt, profile, coverage, &st);
+    if (redist) rc = utree_search_file_redistribute(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, &st);
+    else if (mates || interleaved) rc = utree_search_pairs_file(ctr, devs, n_dev, argv[2], mates, argv[3], doRC, threads, fmt, profile, coverage, &st);
     else rc = utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st);   /* (a NULL path: no such report) */
 #endif
     if (rc == UTREE_E_IO) { puts("Invalid input files"); exit(1); }                      /* itree.c:835 */
@@ -194,7 +210,7 @@ int main(int argc, char *argv[]) {
     fprintf(stderr, "[utree_amd] search %.3f s (%.0f reads/s), GPU batches %.3f s%s\n", st.seconds_total,
             st.seconds_total > 0 ? (double)st.n_reads / st.seconds_total : 0.0, st.seconds_kernels,
             st.pipeline ? " (lane-seconds; framing and formatting on the GPU)" : "");
-    if (rc == UTREE_E_PROFILE || rc == UTREE_E_COVERAGE) fprintf(stderr, "ERROR: %s\n", utree_last_hip_error());    /* the search and its output are complete; the profile / coverage file is not */
+    if (rc == UTREE_E_PROFILE || rc == UTREE_E_COVERAGE) fprintf(stderr, "ERROR: %s\n", utree_last_hip_error());    /* the search and its output are complete; the profile / redistribution / coverage file is not */
     for (int i = n_dev - 1; i >= 0; --i) utree_dev_free(devs[i]);
     if (devs[0] != built) utree_dev_free(built);                                          /* UTREE_RCCL_FORCE: devs[0] was a replica */
     utree_ctr_close(ctr);

@@ -1,0 +1,336 @@
+// redist_kernels.hip -- the candidate sets of ambiguous reads, kept on the device for a whole search, and their redistribution (redist.c,
+// include/utree_amd.h: utree_redist_*).
+//
+// redist_add_k runs between a batch's classify kernels and vote_k, one lane per read, as vote_k walks the same records: a read's distinct
+// labels and their hit counts still stand as a (rank, count) list in the workspace (ascending rank), the record points at it.  The labels tied
+// for the highest count are the read's candidate set.  One candidate: a counter per label (d_single), counted in LDS first for the reason
+// profile_kernels.hip gives -- a sample is dominated by a few taxa and one atomic per read on one word would serialise.  More: the set goes
+// into an open-addressed table of {key, reads} slots, key = arena offset << 32 | labels (0: free), the labels (file-order indices, in the list's order:
+// equal sets arrive as equal sequences) in an arena.
+//
+// Insert: probe read-only and compare WHOLE sets (a hash alone would merge two sets silently); only on a miss write the labels to freshly
+// reserved arena space and claim the free slot with one compare-and-swap of the key (release: the labels are visible before the key).  Whoever
+// loses that race compares against the winner's labels -- complete, they were written before the claim --, adds to its count when they are
+// equal (its own arena space stays unused) and probes on otherwise, keeping its space for the next free slot.  No lane ever waits for another
+// lane to publish: the lanes of a wavefront make no independent progress.  A table or arena that is used up sets a flag in the error word;
+// the read-back then fails (UTREE_E_DEVICE), no read is dropped silently.
+//
+// redist_tally0_k / redist_pass_k: one thread per slot; the set's reads go to every member (T0) or to the richest member under the previous
+// tally, the smallest file-order index on a tie (a pass), one no-return atomic each; the singleton counters enter every tally as a constant;
+// redist_changes_k reduces sum |next - prev| to one word, the only thing the host reads per pass.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "redist.h"
+
+#define RD_BLOCK 1024
+#define RD_DENSE 27648u                    // labels counted by index in LDS: 108 KiB
+#define RD_PROBES 4096u
+#define RD_FREE 0ull                       // a key holds at least two labels in its low word: never 0
+#define RD_CUT_PENDING (-3)                // as in kernels.hip (vote_k finishes those records)
+#define RD_RANK_PENDING (-4)
+
+__device__ __forceinline__ void rd_add(unsigned long long *p, unsigned long long v) {
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void rd_flag(const utk_redist_tab &t, unsigned long long f) {
+    (void)__hip_atomic_fetch_or(t.misc + 1, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t rd_mix(uint32_t h, uint32_t v) {
+    h ^= v; h *= 0x9E3779B1u; h ^= h >> 15; h *= 0x85EBCA77u;
+    return h ^ (h >> 13);
+}
+
+// the tied entries of a (rank, count) list as file-order indices, in list order: the first four in registers (most sets are that small: the
+// hash and every compare then read no memory), the rest by walking the list on from `pos4`
+struct TiedSeq {
+    const uint64_t *T; const uint32_t *r2i; uint32_t mx, uix, n_labels, c0, c1, c2, c3, pos4, idx, pos;
+    __device__ void reset() { idx = 0; pos = pos4; }
+    __device__ uint32_t next() {                           // ~0: beyond the list, or a rank the database does not have (rd_insert refuses it)
+        const uint32_t i = idx++;
+        if (i < 4u) return i == 0u ? c0 : i == 1u ? c1 : i == 2u ? c2 : c3;
+        while (pos < uix) { const uint64_t e = T[pos++]; if ((uint32_t)(e >> 32) == mx) return (uint32_t)e < n_labels ? r2i[(uint32_t)e] : 0xFFFFFFFFu; }
+        return 0xFFFFFFFFu;
+    }
+};
+struct FlatSeq {
+    const uint32_t *p; uint32_t pos;
+    __device__ void reset() { pos = 0; }
+    __device__ uint32_t next() { return p[pos++]; }
+};
+
+// `reads` reads whose candidate set is the n (>= 2) labels of `seq`
+template <class SEQ>
+__device__ void rd_insert(const utk_redist_tab &t, SEQ &seq, uint32_t n, unsigned long long reads) {
+    uint32_t h = 0x811C9DC5u;
+    seq.reset();
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t l = seq.next();
+        if (l >= t.n_labels) { rd_flag(t, UTK_REDIST_F_LABEL); return; }      // every label in the arena indexes a tally
+        h = rd_mix(h, l);
+    }
+    unsigned long long mine = RD_FREE;                     // the key of this lane's own arena copy, once written
+    const uint32_t probes = t.mask + 1 < RD_PROBES ? t.mask + 1 : RD_PROBES;
+    for (uint32_t p = 0; p < probes; ++p) {
+        unsigned long long *slot = t.slots + 2 * (size_t)((h + p) & t.mask);
+        unsigned long long k = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == RD_FREE) {
+            if (mine == RD_FREE) {
+                const unsigned long long at = __hip_atomic_fetch_add(t.misc + 2, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (at + n > t.arena_cap) { rd_flag(t, UTK_REDIST_F_ARENA); return; }
+                seq.reset();
+                for (uint32_t i = 0; i < n; ++i) t.arena[at + i] = seq.next();
+                mine = at << 32 | n;
+            }
+            unsigned long long expect = RD_FREE;
+            if (__hip_atomic_compare_exchange_strong(slot, &expect, mine, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) {
+                rd_add(slot + 1, reads);
+                return;
+            }
+            k = expect;                                    // somebody else's set, complete: compare like any occupied slot
+        }
+        if ((uint32_t)k != n) continue;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // the labels behind a key that has been seen
+        const uint32_t *a = t.arena + (k >> 32);
+        bool same = true;
+        seq.reset();
+        for (uint32_t i = 0; i < n && same; ++i) same = __hip_atomic_load(a + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == seq.next();
+        if (same) { rd_add(slot + 1, reads); return; }
+    }
+    rd_flag(t, UTK_REDIST_F_TABLE);
+}
+
+#define RD_TILE 4096u                      // reads a workgroup takes per round = the capacity of its queue of listed reads
+#define RD_Q2 8192u                        // capacity of its queue of reads with several candidates, emptied when a further round might not fit
+#define RD_UNROLL 4
+struct RdLds { uint32_t dense[RD_DENSE]; uint32_t q[RD_TILE]; uint32_t q2[RD_Q2]; uint32_t qn, q2n; };
+
+__device__ __forceinline__ void rd_single(const utk_redist_tab &t, RdLds &s, uint32_t n_dense, uint32_t one) {
+    if (one >= t.n_labels) { rd_flag(t, UTK_REDIST_F_LABEL); return; }
+    if (one < n_dense) atomicAdd(&s.dense[one], 1u);
+    else rd_add(t.single + one, 1ull);
+}
+
+// RD_UNROLL queued reads per thread, each with a (rank, count) list whose tied maximum is its candidate set.  The four reads' records, list
+// entries and index look-ups are requested side by side: every step of one read's chain is a dependent load, and most listed reads end as
+// a single candidate (one label has the most hits), so the loads are the cost.
+__device__ void rd_listed(const utk_redist_tab &t, RdLds &s, uint32_t n_dense, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
+                          const uint64_t *__restrict__ tally, uint32_t first, uint32_t qn) {
+    const uint32_t nl = t.n_labels;
+    uint32_t uix[RD_UNROLL], mx[RD_UNROLL], ties[RD_UNROLL], k0[RD_UNROLL], rr[RD_UNROLL], umax = 0;
+    const uint64_t *T[RD_UNROLL];
+#pragma unroll
+    for (int u = 0; u < RD_UNROLL; ++u) {
+        const uint32_t i = first + (uint32_t)u * RD_BLOCK;
+        uix[u] = 0; T[u] = tally; mx[u] = 0; ties[u] = 0; k0[u] = 0; rr[u] = 0;
+        if (i < qn) {
+            rr[u] = s.q[i];
+            const uint32_t *rec = (const uint32_t *)&res[rr[u]];
+            uix[u] = rec[3];
+            T[u] = tally + ((uint64_t)rec[4] | ((uint64_t)rec[5] << 32));
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < RD_UNROLL; ++u) umax = uix[u] > umax ? uix[u] : umax;
+    for (uint32_t i = 0; i < umax; ++i) {
+        uint64_t e[RD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < RD_UNROLL; ++u) e[u] = i < uix[u] ? T[u][i] : 0ull;
+#pragma unroll
+        for (int u = 0; u < RD_UNROLL; ++u) {
+            if (i >= uix[u]) continue;
+            const uint32_t c = (uint32_t)(e[u] >> 32), rk = (uint32_t)e[u];
+            if (c > mx[u]) { mx[u] = c; ties[u] = 1; k0[u] = rk; }
+            else if (c == mx[u]) ++ties[u];
+        }
+    }
+    uint32_t c0[RD_UNROLL];
+#pragma unroll
+    for (int u = 0; u < RD_UNROLL; ++u) c0[u] = ties[u] == 1 && k0[u] < nl ? rank2ix[k0[u]] : 0xFFFFFFFFu;
+#pragma unroll
+    for (int u = 0; u < RD_UNROLL; ++u) {
+        if (first + (uint32_t)u * RD_BLOCK >= qn) continue;
+        if (!ties[u] || !mx[u]) { rd_flag(t, UTK_REDIST_F_LABEL); continue; }       // (an empty list: the classify kernels write none; never dropped silently)
+        if (ties[u] == 1) rd_single(t, s, n_dense, c0[u]);
+        else s.q2[atomicAdd(&s.q2n, 1u)] = rr[u];                                   // several candidates: the table, with full wavefronts (below)
+    }
+}
+
+// a queued read with several candidates: its set into the table
+__device__ void rd_multi(const utk_redist_tab &t, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
+                         const uint64_t *__restrict__ tally, uint32_t r) {
+    const uint32_t *rec = (const uint32_t *)&res[r];
+    const uint32_t uix = rec[3], nl = t.n_labels;
+    const uint64_t *T = tally + ((uint64_t)rec[4] | ((uint64_t)rec[5] << 32));
+    uint32_t mx = 0, ties = 0, k0 = 0, k1 = 0, k2 = 0, k3 = 0, pos4 = 0;
+    for (uint32_t i = 0; i < uix; ++i) {
+        const uint64_t e = T[i];
+        const uint32_t c = (uint32_t)(e >> 32), rk = (uint32_t)e;
+        if (c > mx) { mx = c; ties = 1; k0 = rk; }
+        else if (c == mx) {
+            if (ties == 1) k1 = rk; else if (ties == 2) k2 = rk; else if (ties == 3) { k3 = rk; pos4 = i + 1; }
+            ++ties;
+        }
+    }
+    if (ties < 2) { rd_flag(t, UTK_REDIST_F_LABEL); return; }     // (rd_listed queued it for having more: never dropped silently)
+    TiedSeq seq = {T, rank2ix, mx, uix, nl, k0 < nl ? rank2ix[k0] : 0xFFFFFFFFu, k1 < nl ? rank2ix[k1] : 0xFFFFFFFFu,
+                   ties > 2 && k2 < nl ? rank2ix[k2] : 0xFFFFFFFFu, ties > 3 && k3 < nl ? rank2ix[k3] : 0xFFFFFFFFu, pos4, 0, 0};
+    rd_insert(t, seq, ties, 1ull);
+}
+
+// Rounds of RD_TILE reads per workgroup.  First every thread takes its records, four loads in flight: no hit -- nothing; one distinct label --
+// counted in LDS; a list -- the read's index goes on the workgroup's queue.  Then that queue is dealt out over all lanes, which find each
+// list's tied maximum: one candidate is counted, several put the read on a second queue, and that one is dealt out in turn when it may not
+// hold another round's reads.  A wavefront executes the union of its lanes' paths, and a probe of the table is a chain of device-scope
+// round trips: with one read in twelve ambiguous nearly every wavefront ran that chain for a few of its lanes in every step when the reads were
+// taken as they came (measured: 2.6 ms per 16 M reads that way, 1.9 ms with the first queue alone, of which 1.7 ms were the probes).
+__global__ void __launch_bounds__(RD_BLOCK) redist_add_k(utk_redist_tab t, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
+                                                         const uint64_t *__restrict__ tally, uint32_t n, uint32_t per_block) {
+    __shared__ RdLds s;
+    const uint32_t n_dense = t.n_labels < RD_DENSE ? t.n_labels : RD_DENSE;
+    for (uint32_t i = threadIdx.x; i < n_dense; i += RD_BLOCK) s.dense[i] = 0;
+    const uint64_t begin = (uint64_t)blockIdx.x * per_block;
+    const uint64_t end = begin + per_block < n ? begin + per_block : n;
+    for (uint64_t tile = begin; tile < end; tile += RD_TILE) {
+        const uint64_t tend = tile + RD_TILE < end ? tile + RD_TILE : end;
+        if (threadIdx.x == 0) { s.qn = 0; if (tile == begin) s.q2n = 0; }
+        __syncthreads();
+        for (uint64_t r0 = tile + threadIdx.x; r0 < tend; r0 += RD_UNROLL * RD_BLOCK) {
+            uint32_t lab[RD_UNROLL], fnd[RD_UNROLL];
+            int32_t cut[RD_UNROLL];
+#pragma unroll
+            for (int u = 0; u < RD_UNROLL; ++u) {
+                const uint64_t r = r0 + (uint64_t)u * RD_BLOCK;
+                lab[u] = 0; cut[u] = -2; fnd[u] = 0;
+                if (r < tend) { lab[u] = res[r].label; cut[u] = res[r].cut; fnd[u] = res[r].found; }
+            }
+#pragma unroll
+            for (int u = 0; u < RD_UNROLL; ++u) {
+                if (!fnd[u]) continue;
+                if (cut[u] == RD_CUT_PENDING) s.q[atomicAdd(&s.qn, 1u)] = (uint32_t)(r0 + (uint64_t)u * RD_BLOCK);     // (at most RD_TILE per round)
+                else if (cut[u] == RD_RANK_PENDING) rd_single(t, s, n_dense, lab[u] < t.n_labels ? rank2ix[lab[u]] : 0xFFFFFFFFu);
+                else rd_single(t, s, n_dense, lab[u]);     // finished by classify_long_k: one label, already a file-order index
+            }
+        }
+        __syncthreads();
+        const uint32_t qn = s.qn;
+        for (uint32_t i = threadIdx.x; i < qn; i += RD_UNROLL * RD_BLOCK) rd_listed(t, s, n_dense, rank2ix, res, tally, i, qn);
+        __syncthreads();
+        const uint32_t q2n = s.q2n;
+        if (q2n + RD_TILE > RD_Q2 || tend == end) {                 // (the same decision in every thread)
+            for (uint32_t i = threadIdx.x; i < q2n; i += RD_BLOCK) rd_multi(t, rank2ix, res, tally, s.q2[i]);
+            __syncthreads();
+            if (threadIdx.x == 0) s.q2n = 0;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_dense; i += RD_BLOCK)
+        if (s.dense[i]) rd_add(t.single + i, s.dense[i]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) rd_add(t.misc + 0, n);
+}
+
+__global__ void __launch_bounds__(256) redist_insert_k(utk_redist_tab t, const unsigned long long *__restrict__ reads,
+                                                       const unsigned long long *__restrict__ first, const uint32_t *__restrict__ cnt,
+                                                       const uint32_t *__restrict__ labels, uint64_t n_sets) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_sets || !reads[i]) return;
+    const uint32_t *p = labels + first[i];
+    for (uint32_t j = 0; j < cnt[i]; ++j) if (p[j] >= t.n_labels) { rd_flag(t, UTK_REDIST_F_LABEL); return; }
+    if (cnt[i] == 1) { rd_add(t.single + p[0], reads[i]); return; }
+    if (!cnt[i]) return;
+    FlatSeq seq = {p, 0};
+    rd_insert(t, seq, cnt[i], reads[i]);
+}
+
+__global__ void __launch_bounds__(256) redist_sum_k(unsigned long long *dst, const unsigned long long *__restrict__ src, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) if (src[i]) dst[i] += src[i];
+}
+
+// PASS false: every member gets the set's reads (T0), the sets' reads summed into misc[4]; true: the richest member under `prev`
+template <bool PASS>
+__global__ void __launch_bounds__(256) redist_pass_k(utk_redist_tab t, const unsigned long long *__restrict__ prev, unsigned long long *next) {
+    unsigned long long amb = 0;
+    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= t.mask; s += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long k = t.slots[2 * s];
+        if (k == RD_FREE) continue;
+        const unsigned long long reads = t.slots[2 * s + 1];
+        const uint32_t *a = t.arena + (k >> 32);
+        const uint32_t n = (uint32_t)k;
+        if (!PASS) {
+            for (uint32_t i = 0; i < n; ++i) rd_add(next + a[i], reads);
+            amb += reads;
+        } else {
+            uint32_t best = a[0];
+            unsigned long long tb = prev[best];
+            for (uint32_t i = 1; i < n; ++i) {
+                const uint32_t l = a[i];
+                const unsigned long long tl = prev[l];
+                if (tl > tb || (tl == tb && l < best)) { best = l; tb = tl; }
+            }
+            rd_add(next + best, reads);
+        }
+    }
+    if (!PASS) {
+        for (int d = 32; d; d >>= 1) amb += __shfl_down(amb, d);
+        if ((threadIdx.x & 63u) == 0 && amb) rd_add(t.misc + 4, amb);
+    }
+}
+
+__global__ void __launch_bounds__(256) redist_changes_k(const unsigned long long *__restrict__ prev, const unsigned long long *__restrict__ next, uint32_t n,
+                                                        unsigned long long *out) {
+    unsigned long long c = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+        c += next[i] > prev[i] ? next[i] - prev[i] : prev[i] - next[i];
+    for (int d = 32; d; d >>= 1) c += __shfl_down(c, d);
+    if ((threadIdx.x & 63u) == 0 && c) rd_add(out, c);
+}
+
+static inline uint32_t grid_for(uint64_t n, uint32_t block, uint32_t most) {
+    uint64_t g = (n + block - 1) / block;
+    return (uint32_t)(g < 1 ? 1 : g > most ? most : g);
+}
+
+extern "C" int utk_redist_add(const utk_redist_tab *t, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, uint32_t n_reads,
+                              int n_cu, void *stream) {
+    if (!n_reads) return 0;
+    // one workgroup per CU at most (the LDS counters take 112 KiB of its 160), each over a contiguous run of records
+    uint32_t blocks = (uint32_t)(n_cu > 0 ? n_cu : 256);
+    const uint32_t min_per = 4u * RD_BLOCK;
+    if ((n_reads + min_per - 1) / min_per < blocks) blocks = (n_reads + min_per - 1) / min_per;
+    const uint32_t per = (uint32_t)(((uint64_t)n_reads + blocks - 1) / blocks);
+    hipLaunchKernelGGL(redist_add_k, dim3(blocks), dim3(RD_BLOCK), 0, (hipStream_t)stream, *t, im->rank2ix, d_res, ws->tally, n_reads, per);
+    return (int)hipGetLastError();
+}
+
+extern "C" int utk_redist_insert(const utk_redist_tab *t, const unsigned long long *d_reads, const unsigned long long *d_first, const uint32_t *d_n,
+                                 const uint32_t *d_labels, uint64_t n_sets, void *stream) {
+    if (!n_sets) return 0;
+    hipLaunchKernelGGL(redist_insert_k, dim3((uint32_t)((n_sets + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *t, d_reads, d_first, d_n, d_labels,
+                       n_sets);
+    return (int)hipGetLastError();
+}
+
+extern "C" int utk_redist_sum(unsigned long long *dst, const unsigned long long *src, uint64_t n, void *stream) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(redist_sum_k, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, dst, src, n);
+    return (int)hipGetLastError();
+}
+
+extern "C" int utk_redist_tally0(const utk_redist_tab *t, unsigned long long *tally, void *stream) {
+    hipError_t e = hipMemcpyAsync(tally, t->single, (size_t)t->n_labels * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->misc + 4, 0, 8, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(redist_pass_k<false>, dim3(grid_for((uint64_t)t->mask + 1, 256, 4096)), dim3(256), 0, (hipStream_t)stream, *t,
+                       (const unsigned long long *)NULL, tally);
+    return (int)hipGetLastError();
+}
+
+extern "C" int utk_redist_pass(const utk_redist_tab *t, const unsigned long long *prev, unsigned long long *next, void *stream) {
+    hipError_t e = hipMemcpyAsync(next, t->single, (size_t)t->n_labels * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->misc + 3, 0, 8, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(redist_pass_k<true>, dim3(grid_for((uint64_t)t->mask + 1, 256, 4096)), dim3(256), 0, (hipStream_t)stream, *t, prev, next);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(redist_changes_k, dim3(grid_for(t->n_labels, 256, 1024)), dim3(256), 0, (hipStream_t)stream, prev, next, t->n_labels, t->misc + 3);
+    return (int)hipGetLastError();
+}

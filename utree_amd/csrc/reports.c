@@ -1,5 +1,5 @@
-/* reports.c -- the opt-in reports of one whole-file search (reports.h): a profile (profile.c) and / or a coverage handle (coverage.c) per
- * device handle, fed chunk by chunk, merged and written when the search has succeeded. */
+/* reports.c -- the opt-in reports of one whole-file search (reports.h): a profile (profile.c), a coverage handle (coverage.c) and / or a
+ * redistribution handle (redist.c) per device handle, fed chunk by chunk, merged and written when the search has succeeded. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -9,23 +9,29 @@
 
 struct utree_reports {
     int n_dev;
-    const char *profile_path, *coverage_path;
-    struct { utree_profile *prof; utree_coverage *cov; } dev[];      /* NULL: the search writes no such report */
+    const char *profile_path, *coverage_path, *redist_path;
+    uint32_t redist_passes;
+    struct { utree_profile *prof; utree_coverage *cov; utree_redist *rd; } dev[];      /* NULL: the search writes no such report */
 };
 
 int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *profile_path, const char *coverage_path,
-                         utree_reports **out) {
+                         const char *redist_path, uint32_t redist_passes, utree_reports **out) {
     *out = NULL;
-    if (!profile_path && !coverage_path) return UTREE_OK;
+    if (!profile_path && !coverage_path && !redist_path) return UTREE_OK;
+    if (redist_path && redist_passes > 1000) return UTREE_E_ARG;
     if (!ctr || !devs || n_dev < 1) return UTREE_E_ARG;
     utree_reports *rep = (utree_reports *)calloc(1, sizeof *rep + (size_t)n_dev * sizeof rep->dev[0]);
     if (!rep) return UTREE_E_NOMEM;
-    rep->n_dev = n_dev; rep->profile_path = profile_path; rep->coverage_path = coverage_path;
+    rep->n_dev = n_dev; rep->profile_path = profile_path; rep->coverage_path = coverage_path; rep->redist_path = redist_path;
+    rep->redist_passes = redist_passes ? redist_passes : UTREE_REDIST_DEFAULT_PASSES;
     const char *e = getenv("UTREE_PROFILE_CAPACITY");
     const uint32_t cap = e && atoll(e) >= 1 && atoll(e) <= (1ll << 30) ? (uint32_t)atoll(e) : UTREE_PROFILE_DEFAULT_CAPACITY;
     int rc = UTREE_OK;
     for (int g = 0; profile_path && g < n_dev && !rc; ++g) rc = utree_profile_create(devs[g], cap, &rep->dev[g].prof);
     for (int g = 0; coverage_path && g < n_dev && !rc; ++g) rc = utree_coverage_create(ctr, devs[g], NULL, NULL, &rep->dev[g].cov);
+    const char *er = getenv("UTREE_REDIST_CAPACITY");
+    const uint32_t rcap = er && atoll(er) >= 1 && atoll(er) <= (1ll << 28) ? (uint32_t)atoll(er) : UTREE_REDIST_DEFAULT_CAPACITY;
+    for (int g = 0; redist_path && g < n_dev && !rc; ++g) rc = utree_redist_create(devs[g], rcap, &rep->dev[g].rd);
     if (rc) { utree_reports_free(rep); return rc; }
     *out = rep;
     return UTREE_OK;
@@ -35,6 +41,7 @@ void utree_reports_free(utree_reports *rep) {
     if (!rep) return;
     for (int g = 0; g < rep->n_dev; ++g) utree_profile_free(rep->dev[g].prof);
     for (int g = 0; g < rep->n_dev; ++g) utree_coverage_free(rep->dev[g].cov);
+    for (int g = 0; g < rep->n_dev; ++g) utree_redist_free(rep->dev[g].rd);
     free(rep);
 }
 
@@ -42,7 +49,17 @@ int utree_reports_reset(utree_reports *rep) {
     int rc = UTREE_OK;
     for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].prof) rc = utree_profile_reset(rep->dev[g].prof);
     for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].cov) rc = utree_coverage_reset(rep->dev[g].cov);
+    for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].rd) rc = utree_redist_reset(rep->dev[g].rd);
     return rc;
+}
+
+int utree_reports_classify(utree_reports *rep, int g, utree_dev *dev, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                           uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace,
+                           size_t workspace_bytes, void *stream) {
+    if (rep && rep->dev[g].rd)
+        return utree_redist_classify_batch(rep->dev[g].rd, dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace,
+                                           workspace_bytes, stream);
+    return utree_classify_batch(dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream);
 }
 
 int utree_reports_add(utree_reports *rep, int g, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
@@ -108,9 +125,40 @@ static int write_coverage(const utree_reports *rep, const utree_ctr *ctr, uint64
     return rc;
 }
 
+/* merges the devices' handles into the first, checks that n_reads_expected reads were added (else UTREE_E_DEVICE), solves and writes the file */
+static int write_redist(const utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads_expected) {
+    const char *path = rep->redist_path;
+    int rc = UTREE_OK;
+    size_t k = 0;
+    uint64_t reads = 0, ambiguous = 0;
+    uint32_t passes = 0;
+    utree_redist_entry *e = (utree_redist_entry *)malloc(((size_t)ctr->info.n_labels + 1) * sizeof *e);
+    if (!e) return UTREE_E_NOMEM;
+    for (int g = 1; g < rep->n_dev && !rc; ++g) rc = utree_redist_merge(rep->dev[0].rd, rep->dev[g].rd);
+    if (!rc) rc = utree_redist_reads(rep->dev[0].rd, &reads);
+    char msg[400];
+    if (rc == UTREE_E_DEVICE) snprintf(msg, sizeof msg, "redistribution %s: %s", path, utree_last_hip_error());
+    else if (rc) snprintf(msg, sizeof msg, "redistribution %s: the sets could not be merged and read back (%s)", path, utree_strerror(rc));
+    else if (reads != n_reads_expected) {                          /* every read added exactly once, or no file */
+        snprintf(msg, sizeof msg, "redistribution %s: %llu reads added, the search read %llu", path, (unsigned long long)reads,
+                 (unsigned long long)n_reads_expected);
+        rc = UTREE_E_DEVICE;
+    } else if ((rc = utree_redist_solve(rep->dev[0].rd, rep->redist_passes, e, ctr->info.n_labels, &k, &passes, &ambiguous)))
+        snprintf(msg, sizeof msg, "redistribution %s: the passes failed (%s)", path, utree_strerror(rc));
+    else if ((rc = utree_redist_write(ctr, e, k, reads, ambiguous, passes, path)))
+        snprintf(msg, sizeof msg, "redistribution %s: cannot write the file (%s)", path, utree_strerror(rc));
+    if (rc) utree_set_error_text(msg);
+    free(e);
+    return rc;
+}
+
 int utree_reports_write(utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads) {
     if (!rep) return UTREE_OK;
     const int ce = rep->coverage_path ? write_coverage(rep, ctr, n_reads) : UTREE_OK;
+    char keep[512];
+    const int re = rep->redist_path ? write_redist(rep, ctr, n_reads) : UTREE_OK;
+    if (re) snprintf(keep, sizeof keep, "%s", utree_last_hip_error());
     if (rep->profile_path && write_profile(rep, ctr, n_reads)) return UTREE_E_PROFILE;
+    if (re) { utree_set_error_text(keep); return UTREE_E_PROFILE; }      /* (no code of its own; a profile that was written sets no text) */
     return ce ? UTREE_E_COVERAGE : UTREE_OK;      /* (a profile that was written sets no text: the coverage's stands) */
 }

@@ -426,8 +426,8 @@ static void *gpu_main(void *arg) {
                 if (e) { set_error(P, e); return NULL; }
                 c->want_total = total;
                 HIPOK(hipMemcpyAsync(&s->h_meta[g], c->d_meta, sizeof(utree_pairs_meta), hipMemcpyDeviceToHost, c->stream));
-                e = utree_classify_batch(c->dev, c->d_joined, c->d_joff, c->d_jlen, (uint32_t)count, total, mx, P->do_rc, c->d_out, c->d_ws,
-                                         c->ws_bytes, c->stream);
+                e = utree_reports_classify(P->rep, (int)g, c->dev, c->d_joined, c->d_joff, c->d_jlen, (uint32_t)count, total, mx, P->do_rc, c->d_out,
+                                           c->d_ws, c->ws_bytes, c->stream);
                 if (e) { set_error(P, e); return NULL; }
                 e = utree_reports_add(P->rep, (int)g, c->d_joined, c->d_joff, c->d_jlen, c->d_out, (uint32_t)count, P->do_rc, 0, c->stream);
                 if (e) { set_error(P, e); return NULL; }
@@ -446,8 +446,8 @@ static void *gpu_main(void *arg) {
             HIPOK(hipMemcpyAsync(c->d_len, s->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
             int e = P->rank ? utree_rank_batch(c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
                                                P->rank, c->d_out, c->d_ws, c->ws_bytes, c->stream)
-                            : utree_classify_batch(c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
-                                                   c->d_out, c->d_ws, c->ws_bytes, c->stream);
+                            : utree_reports_classify(P->rep, (int)g, c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
+                                                     c->d_out, c->d_ws, c->ws_bytes, c->stream);
             if (e) { set_error(P, e); return NULL; }
             e = utree_reports_add(P->rep, (int)g, c->d_buf, c->d_off, c->d_len, c->d_out, (uint32_t)count, P->do_rc, P->rank != NULL, c->stream);
             if (e) { set_error(P, e); return NULL; }
@@ -734,14 +734,16 @@ done:
 /* One whole-file search as every public entry point asks for it.  rank: NULL = the GG search over n_dev device handles; else XT_doSearch32(utree,
  * in, out, 0, speed, doRC) (itree.c:1376 without DO_GG): the same pipeline, the batches to ONE device in file order because each read's vote
  * depends on the reads before it (rank.c).  profile_path / coverage_path: NULL, or the report to feed while searching and to write when the
- * search has succeeded (the search's own codes stay its own). */
+ * search has succeeded (the search's own codes stay its own); redist_path: the same for the redistribution (GG search only). */
 static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int paired,
                           const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format,
-                          const char *profile_path, const char *coverage_path, utree_search_stats *stats) {
+                          const char *profile_path, const char *coverage_path, const char *redist_path, uint32_t redist_passes,
+                          utree_search_stats *stats) {
     utree_reports *rep = NULL;
     utree_search_stats st;
     memset(&st, 0, sizeof st);
-    int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, &rep);
+    if (rank && redist_path) return UTREE_E_ARG;                   /* (another vote: no candidate sets) */
+    int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, redist_path, redist_passes, &rep);
     if (!rc && !rep) return search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, NULL, stats);   /* no report asked for */
     if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, rep, &st);
     if (!rc) rc = utree_reports_write(rep, ctr, st.n_reads);
@@ -752,20 +754,20 @@ static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, con
 
 int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
                       int do_rc, int host_threads, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, stats);
+    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, NULL, 0, stats);
 }
 int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
                            int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, NULL, 0, stats);
 }
 int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                               int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, NULL, 0, stats);
 }
 int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                                int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                                utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, NULL, 0, stats);
 }
 
 /* pairs: both mates of a pair cast one vote (include/utree_amd.h) */
@@ -773,7 +775,16 @@ int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, c
                             int do_rc, int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                             utree_search_stats *stats) {
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : PAIRS_INTERLEAVED, out_path, do_rc, NULL,
-                          host_threads, input_format, profile_path, coverage_path, stats);
+                          host_threads, input_format, profile_path, coverage_path, NULL, 0, stats);
+}
+
+int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                                   int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
+                                   const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
+                                   utree_search_stats *stats) {
+    if (mates_path && interleaved) return UTREE_E_ARG;
+    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, stats);
 }
 
 int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_off1, const uint32_t *d_len1, const uint8_t *d_bases2,
@@ -804,5 +815,5 @@ int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const c
     if (!dev || !params) return UTREE_E_ARG;
     int rc = utree_rank_reset(dev);
     if (rc) return rc;
-    return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, stats);
+    return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, NULL, 0, stats);
 }

@@ -78,6 +78,16 @@ class CoverageEntry(C.Structure):
     _fields_ = [("label", C.c_uint32), ("pad", C.c_uint32), ("db_kmers", C.c_uint64), ("covered", C.c_uint64), ("hits", C.c_uint64)]
 
 
+class RedistSet(C.Structure):
+    """utree_redist_set: a distinct candidate set -- `reads` reads, labels [first, first + n) of the flat label array."""
+    _fields_ = [("reads", C.c_uint64), ("first", C.c_uint64), ("n", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class RedistEntry(C.Structure):
+    """utree_redist_entry: per label, the reads assigned to it after the passes and the reads whose only candidate it is."""
+    _fields_ = [("label", C.c_uint32), ("pad", C.c_uint32), ("assigned", C.c_uint64), ("unique", C.c_uint64)]
+
+
 class PairsMeta(C.Structure):
     """utree_pairs_meta: what the device join of a batch of pairs reports (error 0, 1 joined buffer too small, 2 a pair too long)."""
     _fields_ = [("total_bases", C.c_uint64), ("max_len", C.c_uint32), ("error", C.c_uint32)]
@@ -171,6 +181,19 @@ SYMBOLS = {
     "utree_coverage_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_char_p]),
     "utree_search_file_coverage": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                              C.c_int, C.c_char_p, C.c_char_p, C.POINTER(SearchStats)]),
+    "utree_redist_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "utree_redist_reset": (C.c_int, [C.c_void_p]),
+    "utree_redist_free": (None, [C.c_void_p]),
+    "utree_redist_classify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                              C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "utree_redist_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "utree_redist_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "utree_redist_solve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint64)]),
+    "utree_redist_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p]),
+    "utree_search_file_redistribute": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
+                                                 C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(SearchStats)]),
     "utree_pairs_join": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                    C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "utree_search_pairs_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int,

@@ -9,6 +9,7 @@
     tree.join_pairs(...)             the device join in front of classify(): mate 1 + 'N' + mate 2 per pair
     tree.profile(capacity)           per-taxon read counts of classified batches (no counterpart in the reference)
     tree.coverage()                  per-taxon database k-mers, distinct ones hit, hits (no counterpart in the reference)
+    tree.redistribution()            candidate sets of ambiguous reads, redistributed among their tied labels (as xtree does)
 
 torch is used only for device memory and streams (plumbing); every computation happens in the HIP kernels
 behind libutree_amd.so.  Nothing here falls back to the CPU.
@@ -27,6 +28,8 @@ RESULT_DTYPE = np.dtype([("label", "<u4"), ("cut", "<i4"), ("found", "<u4"), ("u
                          ("ol", "<u4")])
 PROFILE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("cut", "<i4"), ("reads", "<u8")])
 COVERAGE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("pad", "<u4"), ("db_kmers", "<u8"), ("covered", "<u8"), ("hits", "<u8")])
+REDIST_SET_DTYPE = np.dtype([("reads", "<u8"), ("first", "<u8"), ("n", "<u4"), ("pad", "<u4")])
+REDIST_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("pad", "<u4"), ("assigned", "<u8"), ("unique", "<u8")])
 
 
 class CtrDB:
@@ -363,6 +366,10 @@ class DeviceTree:
         bin table and node dump (they are copied), or neither to stream the dump from the .ctr / the host copy."""
         return Coverage(self, d_binix, d_records)
 
+    def redistribution(self, capacity: int = 1 << 22) -> "Redistribution":
+        """A redistribution handle on this device (utree_redist_create); `capacity` = slots for distinct multi-label candidate sets."""
+        return Redistribution(self, capacity)
+
     def close(self):
         if self._h:
             _lib.load().utree_dev_free(self._h)
@@ -503,6 +510,100 @@ class Coverage:
             pass
 
 
+class Redistribution:
+    """Candidate sets of ambiguous reads on one device and their redistribution (utree_redist_*): classify() is DeviceTree.classify()
+    that also adds the batch's sets, sets() reads every distinct set back, solve() runs the passes, write() writes the file."""
+
+    def __init__(self, tree: DeviceTree, capacity: int = 1 << 22):
+        self.tree = tree
+        self._ws = None
+        h = C.c_void_p()
+        _lib.check(_lib.load().utree_redist_create(tree._h, capacity, C.byref(h)), "utree_redist_create")
+        self._h = h
+
+    def classify(self, bases, off, length, rc: bool = False, total_bases: Optional[int] = None, max_len: Optional[int] = None, out=None,
+                 workspace=None):
+        """As DeviceTree.classify (the same results, bit for bit); the candidate sets of the batch are added on the way.  Asynchronous on
+        torch's current stream; any number of streams may add at once (give each its own workspace)."""
+        import torch
+        n = off.numel()
+        dev = bases.device
+        if total_bases is None:
+            total_bases = int(length.sum().item())
+        if max_len is None:
+            max_len = int(length.max().item()) if n else 0
+        if out is None:
+            out = torch.empty((n, 6), dtype=torch.int32, device=dev)
+        need = self.tree.workspace_bytes(n, total_bases, max_len, rc)
+        if workspace is None:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = self._ws
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().utree_redist_classify_batch(self._h, self.tree._h, bases.data_ptr(), off.data_ptr(), length.data_ptr(), n,
+                                                           total_bases, max_len, int(rc), out.data_ptr(), workspace.data_ptr(),
+                                                           workspace.numel(), stream), "utree_redist_classify_batch")
+        return out
+
+    def sets(self):
+        """(sets, n_reads, n_classified): sets = {sorted tuple of file-order label indices: reads}, single-label sets included.  Raises
+        UtreeError(E_DEVICE) when the table or the arena was too small."""
+        L = _lib.load()
+        ns, nl, nr, nc = C.c_size_t(0), C.c_size_t(0), C.c_uint64(0), C.c_uint64(0)
+        code = L.utree_redist_read(self._h, None, 0, None, 0, C.byref(ns), C.byref(nl), C.byref(nr), C.byref(nc))
+        if code not in (_lib.OK, _lib.E_ARG):
+            _lib.check(code, "utree_redist_read")
+        s = np.zeros(max(ns.value, 1), dtype=REDIST_SET_DTYPE)
+        lab = np.zeros(max(nl.value, 1), dtype=np.uint32)
+        _lib.check(L.utree_redist_read(self._h, s.ctypes.data, ns.value, lab.ctypes.data, nl.value, C.byref(ns), C.byref(nl), C.byref(nr),
+                                       C.byref(nc)), "utree_redist_read")
+        out = {}
+        for reads, first, n, _ in s[:ns.value].tolist():
+            key = tuple(sorted(lab[first:first + n].tolist()))
+            out[key] = out.get(key, 0) + reads
+        return out, nr.value, nc.value
+
+    def merge(self, other: "Redistribution"):
+        """self += other (sets re-inserted, counters added); the handles may be on different devices."""
+        _lib.check(_lib.load().utree_redist_merge(self._h, other._h), "utree_redist_merge")
+
+    def solve(self, max_passes: int = 100):
+        """(entries, passes, ambiguous): entries a numpy array of REDIST_ENTRY_DTYPE (label, assigned, unique), labels with a figure only."""
+        cap = self.tree.db.info.n_labels
+        buf = np.zeros(max(cap, 1), dtype=REDIST_ENTRY_DTYPE)
+        n, p, a = C.c_size_t(0), C.c_uint32(0), C.c_uint64(0)
+        _lib.check(_lib.load().utree_redist_solve(self._h, max_passes, buf.ctypes.data, cap, C.byref(n), C.byref(p), C.byref(a)),
+                   "utree_redist_solve")
+        return buf[:n.value].copy(), p.value, a.value
+
+    def write(self, path: str, max_passes: int = 100):
+        e, p, a = self.solve(max_passes)
+        _, nr, _ = self.sets()
+        write_redistribution(self.tree.db, e, nr, a, p, path)
+
+    def reset(self):
+        _lib.check(_lib.load().utree_redist_reset(self._h), "utree_redist_reset")
+
+    def close(self):
+        if self._h:
+            _lib.load().utree_redist_free(self._h)
+            self._h = None
+            self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_redistribution(db: CtrDB, entries: np.ndarray, n_reads: int, ambiguous: int, passes: int, path: str):
+    """utree_redist_write: entries (REDIST_ENTRY_DTYPE, from any number of solves) merged by text, rolled up, written."""
+    e = np.ascontiguousarray(entries, dtype=REDIST_ENTRY_DTYPE)
+    _lib.check(_lib.load().utree_redist_write(db._h, e.ctypes.data if len(e) else None, len(e), n_reads, ambiguous, passes, path.encode()),
+               "utree_redist_write")
+
+
 def write_coverage(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
     """utree_coverage_write: entries (COVERAGE_ENTRY_DTYPE; all labels of the database) merged by text, rolled up, written."""
     e = np.ascontiguousarray(entries, dtype=COVERAGE_ENTRY_DTYPE)
@@ -512,18 +613,27 @@ def write_coverage(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
 
 def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: bool = False, threads: int = 0,
               input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None,
-              mates: Optional[str] = None, interleaved: bool = False):
+              mates: Optional[str] = None, interleaved: bool = False, redistribute: Optional[str] = None, redist_passes: int = 100):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
     FASTA / gzip input.  profile: also write the per-taxon read counts there; coverage: also write the per-taxon k-mer
     coverage there (utree_search_file_coverage; None: no such report).
     Paired-end reads (utree_search_pairs_file): mates = the file of second mates, or interleaved=True when `fasta` holds records 2i and
     2i+1 of pair i.  A pair is searched as mate 1 + "N" + mate 2, named by mate 1 (mate names are not compared); stats.n_reads counts
-    pairs; unequal record counts return E_PAIRS after the complete pairs were written."""
+    pairs; unequal record counts return E_PAIRS after the complete pairs were written.
+    redistribute: also write the reads redistributed among the labels each hit most often there (utree_search_file_redistribute), at most
+    redist_passes passes; a redistribution that cannot be written returns E_PROFILE."""
     if mates is not None and interleaved:
         raise ValueError("search_gg: give mates= or interleaved=True, not both")
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     st = _lib.SearchStats()
+    if redistribute is not None:
+        code = _lib.load().utree_search_file_redistribute(db._h, arr, len(trees), fasta.encode(), mates.encode() if mates is not None else None,
+                                                          int(interleaved), out.encode(), int(rc), threads, input_format,
+                                                          profile.encode() if profile is not None else None,
+                                                          coverage.encode() if coverage is not None else None, redistribute.encode(),
+                                                          redist_passes, C.byref(st))
+        return code, st
     if mates is not None or interleaved:
         code = _lib.load().utree_search_pairs_file(db._h, arr, len(trees), fasta.encode(), mates.encode() if mates is not None else None,
                                                    out.encode(), int(rc), threads, input_format,
