@@ -45,9 +45,11 @@ enum {
     UTREE_E_PROFILE = 12,    /* the search itself succeeded, its profile was not written: utree_last_hip_error
                                 says why (utree_search_file_profile)                                            */
     UTREE_E_COVERAGE = 13,   /* ... its coverage file was not written (utree_search_file_coverage)              */
-    UTREE_E_PAIRS = 14       /* paired input: one file holds fewer records than the other, or an interleaved file an
+    UTREE_E_PAIRS = 14,      /* paired input: one file holds fewer records than the other, or an interleaved file an
                                 odd number; the complete pairs in front were classified and written, and
                                 utree_last_hip_error names the shorter file (utree_search_pairs_file)            */
+    UTREE_E_HITMAP = 15      /* ... its hit map was not written (utree_search_file_hitmap): utree_last_hip_error says why.
+                                utree_strerror keeps its catch-all text for this code; the cause is in that message */
 };
 
 const char *utree_strerror(int code);
@@ -532,6 +534,53 @@ int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n
                                    int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
                                    const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
                                    utree_search_stats *stats);
+
+/* ------------------------------------------------------------------------------------------------
+ * Per-query k-mer hit map: which label each window of a query hit, in window order (no counterpart in the reference's output: it builds
+ * exactly this list per read -- AllTheKingsHorses[foundUniq-1] = ix, itree.c:935 -- and drops it after the vote).  GG search only: the
+ * rank-specific search examines a hit-dependent subset of windows and has no map.
+ *   Query.  q is the byte string the reference searches: the read as framed; with RC read + 'N' + revcomp(read) (itree.c:891-898); a pair is
+ *     mate1 + 'N' + mate2 (utree_pairs_join) and with RC that joined string + 'N' + its reverse complement.  Positions are positions in q:
+ *     with L the read's (joined pair's) length, window p = 2L+1-k-s of q is the reverse complement of the read's window s.
+ *   Windows.  len(q) >= k: n_windows = len(q) - k + 1, else 0.  Window p has one code: UTREE_HIT_INVALID when some byte of q[p .. p+k) is not
+ *     one of ACGTacgt (the k windows around a joining 'N' are of this kind); the file-order label index ix when XT_getIX32(word) returns
+ *     ix < n_labels (a HIT, itree.c:929); UTREE_HIT_MISS otherwise.  A database of more than 0xFFFFFFFE labels: UTREE_E_UNSUPPORTED.
+ *   Runs.  A query's map is the list of maximal stretches of equal code in window order, (code, count); the counts sum to n_windows, those of
+ *     the hit runs to the read's `found` (column 3 of its output line), and the distinct hit codes number its `uix` (column 4).
+ * ---------------------------------------------------------------------------------------------- */
+#define UTREE_HIT_MISS    0xFFFFFFFFu
+#define UTREE_HIT_INVALID 0xFFFFFFFEu
+typedef struct { uint32_t code, count; } utree_hit_run;
+/* error 0; 1: run_capacity too small (size d_runs for total_runs and call again); 2: total_bases is smaller than the reads' lengths add up to;
+ * 3: a query of 2^32 windows or more (a run's count is 32 bits).  With 2 or 3 there is no map: total_runs = 0 and every offset is 0. */
+typedef struct { uint64_t total_runs, total_windows; uint32_t error, pad; } utree_hitmap_meta;
+/* bytes of d_workspace for a batch: 4 per window of q for the codes, 1/8 for the queries' starts, 32 per 64 windows and per read for the scans */
+size_t utree_hitmap_workspace_bytes(const utree_dev *dev, uint32_t n_reads, uint64_t total_bases, int do_rc);
+/* The maps of a batch, reads given as utree_classify_batch takes them (any lengths, empty reads and reads shorter than k included; pairs:
+ * utree_pairs_join first).  Asynchronous on `stream`.  Read r's runs are d_runs[d_run_off[r] .. d_run_off[r + 1]); d_run_off (n_reads + 1
+ * entries) and *d_meta are always complete; when total_runs > run_capacity, error is 1 and NO element of d_runs at or beyond run_capacity is
+ * written (those below are the map's).  run_capacity = total_windows always suffices.  Every window is looked up once, in the device image;
+ * the call keeps no state outside d_workspace, so any number of streams may run it on one handle at the same time. */
+int utree_hitmap_batch(utree_dev *dev, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads,
+                       uint64_t total_bases, int do_rc, uint64_t *d_run_off /* n_reads + 1 */, utree_hit_run *d_runs,
+                       uint64_t run_capacity, utree_hitmap_meta *d_meta, void *d_workspace, size_t workspace_bytes, void *stream);
+/* Host only: one line for EVERY query, in input order (a query without an output line still has a map):
+ *     name \t n_windows \t found \t tokens \n
+ * tokens = the runs as code:count separated by one space (empty when n_windows == 0); a code prints as the decimal label index for a hit,
+ * '-' for a miss, 'N' for an invalid window.  name = h_buf[name_off[i] .. + name_len[i]), what the output file prints for the query.
+ * h_run_off: n + 1 entries into h_runs.  Returns bytes written, or (size_t)-1 if cap is too small. */
+size_t utree_hitmap_format(const uint8_t *h_buf, const uint64_t *name_off, const uint32_t *name_len, const uint64_t *h_run_off,
+                           const utree_hit_run *h_runs, size_t n, char *h_out, size_t cap);
+/* utree_search_file_redistribute that also writes the search's hit map to `hitmap_path` (NULL: exactly that call -- nothing allocated,
+ * nothing launched) and the label texts to <hitmap_path>.labels, line i (0-based) = label index i.  The map is written in step with the
+ * output: the writer stage commits a chunk's output lines and its map lines together, so after a framing error or UTREE_E_PAIRS both files
+ * hold the same queries.  The per-read output, stdout, the stats and every other report are those of a search without it.  Always the host
+ * framing pipeline (stats.pipeline == 0), as for pairs.  A search that succeeds but whose hit map (or its .labels) cannot be written
+ * returns UTREE_E_HITMAP and utree_last_hip_error says why (a report that failed too keeps its own code). */
+int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                             int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
+                             const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
+                             const char *hitmap_path, utree_search_stats *stats);
 
 /* ------------------------------------------------------------------------------------------------
  * `.ubt` -> `.ctr` = XT_cmp32(filename, outfile) (itree.c:1234-1315; `xtree-compress`), SURVEY.md §8(f) rank 2.

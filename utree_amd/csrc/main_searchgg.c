@@ -31,6 +31,13 @@
  *                           codes as for UTREE_PROFILE, with which and with UTREE_COVERAGE / UTREE_MATES it may be combined.
  *                           UTREE_REDIST_PASSES=<1..1000> caps the passes (default 100; 1: one pass, xtree's fast mode),
  *                           UTREE_REDIST_CAPACITY=<slots> sizes the table of distinct sets (default 2^22).  Unset: nothing of it runs
+ *     UTREE_HITMAP=<path>   opt-in, xtree-searchGG only (xtree-search says so in one line on stderr and ignores it): also write, for EVERY query, which
+ *                           label each of its k-mer windows hit, in window order, as runs "code:count" (include/utree_amd.h: utree_hitmap_format),
+ *                           and the label texts to <path>.labels (line i = label index i).  The map is written in step with the output, so
+ *                           after a malformed record both files hold the same queries; stdout, the output and the other reports are those of a
+ *                           run without it.  May be combined with UTREE_PROFILE, UTREE_COVERAGE, UTREE_REDISTRIBUTE, UTREE_MATES /
+ *                           UTREE_INTERLEAVED and UTREE_INPUT.  A path that cannot be opened: a message on stderr, exit 1, before the search.
+ *                           A map that cannot be written while searching: the usual stdout, a message on stderr, exit 1
  *     UTREE_MATES=<path>    opt-in, xtree-searchGG only: paired-end reads.  fastaToSearch.fa holds the first mates, <path> the second; pair i is
  *                           record i of both.  A pair is searched as ONE query, mate 1 + "N" + mate 2, and prints one line under mate 1's name
  *                           (include/utree_amd.h: utree_search_pairs_file; mate names are not compared); "Searched N queries" and the profile
@@ -117,6 +124,10 @@ int main(int argc, char *argv[]) {
         if (v < 1 || v > 1000) { fputs("ERROR: UTREE_REDIST_PASSES must be 1 .. 1000\n", stderr); exit(1); }
         redist_passes = (unsigned)v;
     }
+    const char *hitmap = getenv("UTREE_HITMAP");
+    if (hitmap && !*hitmap) hitmap = NULL;
+    if (hitmap && !DO_GG) { fputs("[utree_amd] UTREE_HITMAP is ignored: the rank-specific search looks at a hit-dependent subset of windows and has no hit map\n", stderr); hitmap = NULL; }
+    if (hitmap) check_report_path(hitmap, "hit map");
     (void)redist_passes;                                                                  /* (xtree-search: no redistribution) */
 
     utree_ctr *ctr = NULL;
@@ -188,7 +199,8 @@ int main(int argc, char *argv[]) {
     if (getenv("UTREE_TOLERANCE")) prm.tolerance = (uint32_t)atoi(getenv("UTREE_TOLERANCE"));
     rc = utree_rank_search_file_profile(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, &st);   /* (a NULL path: no such report) */
 #else
-    if (redist) rc = utree_search_file_redistribute(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, &st);
+    if (hitmap) rc = utree_search_file_hitmap(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, &st);
+    else if (redist) rc = utree_search_file_redistribute(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, &st);
     else if (mates || interleaved) rc = utree_search_pairs_file(ctr, devs, n_dev, argv[2], mates, argv[3], doRC, threads, fmt, profile, coverage, &st);
     else rc = utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st);   /* (a NULL path: no such report) */
 #endif
@@ -204,15 +216,15 @@ int main(int argc, char *argv[]) {
         exit(2);
     }
     if (rc == UTREE_E_PAIRS) { fprintf(stderr, "ERROR: %s\n", utree_last_hip_error()); exit(2); }   /* the complete pairs are written */
-    if (rc && rc != UTREE_E_PROFILE && rc != UTREE_E_COVERAGE) { fprintf(stderr, "ERROR: %s\n", utree_strerror(rc)); exit(3); }
+    if (rc && rc != UTREE_E_PROFILE && rc != UTREE_E_COVERAGE && rc != UTREE_E_HITMAP) { fprintf(stderr, "ERROR: %s\n", utree_strerror(rc)); exit(3); }
     printf("Good finds: %llu\n", (unsigned long long)st.good_finds);                      /* itree.c:1106 */
     printf("Searched %llu queries\n", (unsigned long long)st.n_reads);                    /* itree.c:1375 */
     fprintf(stderr, "[utree_amd] search %.3f s (%.0f reads/s), GPU batches %.3f s%s\n", st.seconds_total,
             st.seconds_total > 0 ? (double)st.n_reads / st.seconds_total : 0.0, st.seconds_kernels,
             st.pipeline ? " (lane-seconds; framing and formatting on the GPU)" : "");
-    if (rc == UTREE_E_PROFILE || rc == UTREE_E_COVERAGE) fprintf(stderr, "ERROR: %s\n", utree_last_hip_error());    /* the search and its output are complete; the profile / redistribution / coverage file is not */
+    if (rc == UTREE_E_PROFILE || rc == UTREE_E_COVERAGE || rc == UTREE_E_HITMAP) fprintf(stderr, "ERROR: %s\n", utree_last_hip_error());    /* the search and its output are complete; the profile / redistribution / coverage file is not */
     for (int i = n_dev - 1; i >= 0; --i) utree_dev_free(devs[i]);
     if (devs[0] != built) utree_dev_free(built);                                          /* UTREE_RCCL_FORCE: devs[0] was a replica */
     utree_ctr_close(ctr);
-    exit(rc == UTREE_E_PROFILE || rc == UTREE_E_COVERAGE ? 1 : 0);
+    exit(rc == UTREE_E_PROFILE || rc == UTREE_E_COVERAGE || rc == UTREE_E_HITMAP ? 1 : 0);
 }

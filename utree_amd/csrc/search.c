@@ -12,11 +12,15 @@
  * Paired-end input (utree_search_pairs_file) takes the same four stages with a second input: the reader frames both files and commits the
  * pairs both buffers hold, the gpu stage uploads both mates' bytes and joins them on the device (pairs_kernels.hip) in front of the batch
  * kernels; formatter and writer see one query per pair, named by mate 1.
+ *
+ * A hit map (utree_search_file_hitmap) rides the same slots: the gpu stage launches utree_hitmap_batch behind a shard's classify call on the
+ * same device buffers and brings the runs back, the formatter makes the map's lines next to the output's, and the writer commits both.
  */
 #define _FILE_OFFSET_BITS 64
 #define _GNU_SOURCE
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
+#include <errno.h>
 #include <fcntl.h>
 #include <pthread.h>
 #include <stdio.h>
@@ -32,6 +36,7 @@
 #include "search_dev.h"
 #include "reports.h"
 #include "pairs_kernels.h"
+#include "hitmap.h"
 
 #define CHUNK_BYTES ((size_t)96 << 20)        /* must hold two maximal (16 MiB) lines                    */
 #define MAX_READS_PER_BATCH ((size_t)2 << 20)  /* more reads in a chunk (tiny reads) simply take another batch */
@@ -66,10 +71,25 @@ typedef struct {
     uint64_t good;
     mate_t m2;                                 /* paired input only                                         */
     utree_pairs_meta *h_meta;                  /* pinned, one per device: what the join reported            */
+    /* hit map only: per device its shard [hm_first, + hm_count) of the slot, the shard's run offsets (hm_count + 1 of them at h_run_off +
+     * hm_first + g, relative to the shard's first run) and its runs at h_runs + hm_base */
+    utree_hitmap_meta *h_hm_meta;              /* pinned, one per device                                    */
+    uint64_t *h_run_off;                       /* pinned, MAX_READS_PER_BATCH + n_dev                       */
+    utree_hit_run *h_runs; size_t runs_cap;    /* pinned, grows geometrically                               */
+    size_t *hm_first, *hm_count; uint64_t *hm_base;
+    char *hm_buf[FMT_MAX_THREADS];             /* the map's lines, pieces as fmt_buf's                      */
+    size_t hm_cap[FMT_MAX_THREADS], hm_len[FMT_MAX_THREADS];
 } slot_t;
 
-static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev) {
+static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev, int hitmap) {
     if (s->h_buf) return UTREE_OK;
+    if (hitmap) {
+        if (hipHostMalloc((void **)&s->h_hm_meta, (size_t)n_dev * sizeof(utree_hitmap_meta), hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
+        if (hipHostMalloc((void **)&s->h_run_off, (MAX_READS_PER_BATCH + (size_t)n_dev) * 8, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
+        s->hm_first = (size_t *)calloc((size_t)n_dev, sizeof(size_t)); s->hm_count = (size_t *)calloc((size_t)n_dev, sizeof(size_t));
+        s->hm_base = (uint64_t *)calloc((size_t)n_dev, 8);
+        if (!s->hm_first || !s->hm_count || !s->hm_base) return UTREE_E_NOMEM;
+    }
     if (paired) {
         mate_t *m = &s->m2;
         if (paired == PAIRS_TWO_FILES && hipHostMalloc((void **)&m->h_buf, chunk + 64, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
@@ -96,6 +116,8 @@ typedef struct {
     /* paired input: the second mates as uploaded, and the joined batch the kernels see */
     uint8_t *d_buf2, *d_joined; uint64_t *d_off2, *d_joff; uint32_t *d_len2, *d_jlen; utree_pairs_meta *d_meta; size_t joined_cap;
     uint64_t want_total;                        /* joined bytes of the shard in flight, as the host counted them */
+    /* hit map: the shard's run offsets, runs (the worst case: one per window) and meta, and the call's workspace */
+    uint64_t *d_run_off; utree_hit_run *d_runs; uint64_t runs_cap; utree_hitmap_meta *d_hm_meta; void *d_hm_ws; size_t hm_ws_bytes;
 } gpu_ctx;
 
 /* one input file: plain (a team of pread) or, with an opt-in format, through zlib (plain and gzip alike) */
@@ -107,6 +129,9 @@ typedef struct {
     gpu_ctx *G; int n_dev;
     input_t in[2];                              /* input; [1]: the mates file of a paired search             */
     int fo;                                     /* output                                                   */
+    int hm, fh;                                 /* a hit map is made; its file (-1 once writing it has failed: the search goes on) */
+    const char *hm_path;
+    char *hm_msg;                               /* why the map could not be written ("" = it could): the writer's to set            */
     off_t out_pos;
     int paired;                                 /* PAIRS_*                                                  */
     size_t chunk;                               /* bytes per slot and input: CHUNK_BYTES; a paired search honours UTREE_CHUNK_BYTES */
@@ -210,7 +235,7 @@ static void *reader_main(void *arg) {
         slot_t *s = &P->slot[i % NSLOTS];
         if (!wait_state(P, s, S_EMPTY)) return NULL;
         if (i < NSLOTS) {                       /* pinned memory is slow to allocate: do it while earlier chunks are in flight */
-            int arc = slot_alloc(s, P->chunk, PAIRS_NONE, P->n_dev);
+            int arc = slot_alloc(s, P->chunk, PAIRS_NONE, P->n_dev, P->hm);
             if (arc) { set_error(P, arc); return NULL; }
         }
         if (carry) memmove(s->h_buf, carry_src, carry);
@@ -322,7 +347,7 @@ static void *reader_pairs_main(void *arg) {
         mate_t *m = &s->m2;
         if (!wait_state(P, s, S_EMPTY)) return NULL;
         if (i < NSLOTS) {
-            int arc = slot_alloc(s, P->chunk, P->paired, P->n_dev);
+            int arc = slot_alloc(s, P->chunk, P->paired, P->n_dev, P->hm);
             if (arc) { set_error(P, arc); return NULL; }
         }
         uint8_t *buf[2] = {s->h_buf, m->h_buf};
@@ -382,6 +407,50 @@ static void *reader_pairs_main(void *arg) {
 /* ---- stage 2: GPU ---------------------------------------------------------------------------- */
 #define HIPOK(x) do { if ((x) != hipSuccess) { set_error(P, UTREE_E_HIP); return NULL; } } while (0)
 
+/* the hit map of device g's shard, behind its classify call on the same device buffers; meta and offsets come back with the results */
+static int hitmap_launch(pipe_t *P, slot_t *s, size_t g, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, size_t first, size_t count,
+                         uint64_t total) {
+    gpu_ctx *c = &P->G[g];
+    s->hm_first[g] = first; s->hm_count[g] = count;
+    int e = utree_hitmap_batch(c->dev, d_bases, d_off, d_len, (uint32_t)count, total, P->do_rc, c->d_run_off, c->d_runs, c->runs_cap, c->d_hm_meta,
+                               c->d_hm_ws, c->hm_ws_bytes, c->stream);
+    if (e) return e;
+    if (hipMemcpyAsync(&s->h_hm_meta[g], c->d_hm_meta, sizeof(utree_hitmap_meta), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return UTREE_E_HIP;
+    if (hipMemcpyAsync(s->h_run_off + first + g, c->d_run_off, (count + 1) * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return UTREE_E_HIP;
+    return UTREE_OK;
+}
+
+/* once the streams have drained: exactly the runs there are, the shards' one after the other, into the slot's pinned buffer */
+static int hitmap_fetch(pipe_t *P, slot_t *s) {
+    uint64_t runs = 0;
+    for (int g = 0; g < P->n_dev; ++g) {
+        if (!s->hm_count[g]) continue;
+        if (s->h_hm_meta[g].error) {
+            snprintf(P->msg_join, sizeof P->msg_join, "the hit map of a batch reported error %u (%llu runs, %llu windows)", s->h_hm_meta[g].error,
+                     (unsigned long long)s->h_hm_meta[g].total_runs, (unsigned long long)s->h_hm_meta[g].total_windows);
+            return UTREE_E_DEVICE;
+        }
+        s->hm_base[g] = runs; runs += s->h_hm_meta[g].total_runs;
+    }
+    if (runs > s->runs_cap) {
+        size_t cap = s->runs_cap ? s->runs_cap : (size_t)1 << 20;
+        while (cap < runs) cap *= 2;
+        if (s->h_runs) hipHostFree(s->h_runs);
+        s->h_runs = NULL; s->runs_cap = 0;
+        if (hipHostMalloc((void **)&s->h_runs, cap * sizeof(utree_hit_run), hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
+        s->runs_cap = cap;
+    }
+    for (int g = 0; g < P->n_dev; ++g) {
+        if (!s->hm_count[g] || !s->h_hm_meta[g].total_runs) continue;
+        if (hipSetDevice(P->G[g].dev->device) != hipSuccess ||
+            hipMemcpyAsync(s->h_runs + s->hm_base[g], P->G[g].d_runs, s->h_hm_meta[g].total_runs * sizeof(utree_hit_run), hipMemcpyDeviceToHost,
+                           P->G[g].stream) != hipSuccess) return UTREE_E_HIP;
+    }
+    for (int g = 0; g < P->n_dev; ++g)
+        if (s->hm_count[g] && (hipSetDevice(P->G[g].dev->device) != hipSuccess || hipStreamSynchronize(P->G[g].stream) != hipSuccess)) return UTREE_E_HIP;
+    return UTREE_OK;
+}
+
 static void *gpu_main(void *arg) {
     pipe_t *P = (pipe_t *)arg;
     for (int i = 0;; ++i) {
@@ -391,6 +460,7 @@ static void *gpu_main(void *arg) {
         size_t nr = s->nr, n_dev = (size_t)P->n_dev;
         size_t per = (nr + n_dev - 1) / n_dev;
         for (size_t g = 0; g < n_dev && nr && P->paired; ++g) { memset(&s->h_meta[g], 0, sizeof s->h_meta[g]); P->G[g].want_total = 0; }
+        for (size_t g = 0; g < n_dev && P->hm; ++g) { s->hm_first[g] = 0; s->hm_count[g] = 0; s->hm_base[g] = 0; }
         for (size_t g = 0; g < n_dev && nr; ++g) {
             gpu_ctx *c = &P->G[g];
             size_t first = g * per; if (first > nr) first = nr;
@@ -431,6 +501,7 @@ static void *gpu_main(void *arg) {
                 if (e) { set_error(P, e); return NULL; }
                 e = utree_reports_add(P->rep, (int)g, c->d_joined, c->d_joff, c->d_jlen, c->d_out, (uint32_t)count, P->do_rc, 0, c->stream);
                 if (e) { set_error(P, e); return NULL; }
+                if (P->hm && (e = hitmap_launch(P, s, g, c->d_joined, c->d_joff, c->d_jlen, first, count, total))) { set_error(P, e); return NULL; }
                 HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
                 continue;
             }
@@ -451,6 +522,7 @@ static void *gpu_main(void *arg) {
             if (e) { set_error(P, e); return NULL; }
             e = utree_reports_add(P->rep, (int)g, c->d_buf, c->d_off, c->d_len, c->d_out, (uint32_t)count, P->do_rc, P->rank != NULL, c->stream);
             if (e) { set_error(P, e); return NULL; }
+            if (P->hm && (e = hitmap_launch(P, s, g, c->d_buf, c->d_off, c->d_len, first, count, total))) { set_error(P, e); return NULL; }
             HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
         }
         for (size_t g = 0; g < n_dev && nr; ++g) {
@@ -463,6 +535,7 @@ static void *gpu_main(void *arg) {
                 set_error(P, UTREE_E_DEVICE); return NULL;
             }
         }
+        if (P->hm && nr) { int he = hitmap_fetch(P, s); if (he) { set_error(P, he); return NULL; } }
         P->t_gpu += now_s() - t0;
         int last = s->last;
         set_state(P, s, S_DONE);
@@ -500,6 +573,23 @@ static void *format_main(void *arg) {
                                  : utree_format_records(P->ctr, s->h_buf, s->name_off + a, s->name_len + a, s->h_res + a, b - a,
                                                         s->fmt_buf[t], s->fmt_cap[t], &good);
             if (L == (size_t)-1) { fail |= 1; s->fmt_len[t] = 0; } else { s->fmt_len[t] = L; good_total += good; }
+            if (!P->hm) continue;
+            /* the map's lines of [a, b): a line per query; the slice is cut where one device's shard ends and the next one's begins */
+            size_t hneed = 64, hl = 0;
+            for (size_t r = a; r < b; ++r) hneed += (size_t)s->name_len[r] + 48;
+            for (int g = 0; g < P->n_dev; ++g) {
+                const size_t f = s->hm_first[g], e = f + s->hm_count[g], x = a > f ? a : f, y = b < e ? b : e;
+                if (x < y) hneed += 22 * (size_t)(s->h_run_off[y + (size_t)g] - s->h_run_off[x + (size_t)g]);        /* "4294967295:4294967295 " */
+            }
+            if (hneed > s->hm_cap[t]) { free(s->hm_buf[t]); s->hm_buf[t] = (char *)malloc(hneed + hneed / 4); s->hm_cap[t] = s->hm_buf[t] ? hneed + hneed / 4 : 0; }
+            for (int g = 0; g < P->n_dev && s->hm_buf[t] && hl != (size_t)-1; ++g) {
+                const size_t f = s->hm_first[g], e = f + s->hm_count[g], x = a > f ? a : f, y = b < e ? b : e;
+                if (x >= y) continue;
+                const size_t w = utree_hitmap_format(s->h_buf, s->name_off + x, s->name_len + x, s->h_run_off + x + (size_t)g, s->h_runs + s->hm_base[g], y - x,
+                                                     s->hm_buf[t] + hl, s->hm_cap[t] - hl);
+                hl = w == (size_t)-1 ? w : hl + w;
+            }
+            if (!s->hm_buf[t] || hl == (size_t)-1) { fail |= 1; s->hm_len[t] = 0; } else s->hm_len[t] = hl;
         }
         P->t_format += now_s() - t0;
         if (fail) { set_error(P, UTREE_E_NOMEM); break; }
@@ -529,6 +619,18 @@ static void *writer_main(void *arg) {
                 done += (size_t)w;
             }
             P->out_pos += (off_t)s->fmt_len[t];
+        }
+        for (int t = 0; t < s->fmt_T && P->hm && P->fh >= 0; ++t) {                /* the same chunk's map lines: both files hold the same queries */
+            size_t done = 0;
+            while (done < s->hm_len[t]) {
+                ssize_t w = write(P->fh, s->hm_buf[t] + done, s->hm_len[t] - done);
+                if (w <= 0) {                                                     /* the search goes on without its map */
+                    snprintf(P->hm_msg, 512, "hit map %s: cannot write the file (%s)", P->hm_path, strerror(errno));
+                    close(P->fh); P->fh = -1;
+                    break;
+                }
+                done += (size_t)w;
+            }
         }
         P->t_write += now_s() - t1;
         P->st.good_finds += s->good;
@@ -566,6 +668,10 @@ static void free_ctx(gpu_ctx *g) {
     if (g->d_joff) hipFree(g->d_joff);
     if (g->d_jlen) hipFree(g->d_jlen);
     if (g->d_meta) hipFree(g->d_meta);
+    if (g->d_run_off) hipFree(g->d_run_off);
+    if (g->d_runs) hipFree(g->d_runs);
+    if (g->d_hm_meta) hipFree(g->d_hm_meta);
+    if (g->d_hm_ws) hipFree(g->d_hm_ws);
     if (g->stream) hipStreamDestroy(g->stream);
 }
 
@@ -579,12 +685,26 @@ static size_t pairs_chunk_bytes(void) {
     return CHUNK_BYTES;
 }
 
+/* <hitmap_path>.labels: line i (0-based) is the text of label index i, what a hit's code in the map names */
+static int write_labels(const utree_ctr *ctr, const char *hitmap_path, char *msg) {
+    char name[4096];
+    if (snprintf(name, sizeof name, "%s.labels", hitmap_path) >= (int)sizeof name) { snprintf(msg, 512, "hit map %s: the path is too long", hitmap_path); return 1; }
+    FILE *f = fopen(name, "wb");
+    int bad = !f;
+    for (uint32_t i = 0; f && !bad && i < ctr->info.n_labels; ++i)
+        bad = fwrite(ctr->labels[i], 1, ctr->label_len[i], f) != ctr->label_len[i] || fputc('\n', f) == EOF;
+    if (f && fclose(f)) bad = 1;
+    if (bad) snprintf(msg, 512, "hit map %.400s.labels: cannot write the file (%s)", hitmap_path, strerror(errno));
+    return bad;
+}
+
 /* paired: PAIRS_TWO_FILES (mates_path holds the second mates) or PAIRS_INTERLEAVED (fasta_path holds both), GG search only */
 static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *mates_path, int paired,
                        const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format, utree_reports *rep,
-                       utree_search_stats *stats) {
+                       const char *hitmap_path, char *hm_msg, utree_search_stats *stats) {
     if (!ctr || !devs || n_dev < 1 || !fasta_path || !out_path || input_format < 0 || input_format > UTREE_INPUT_AUTO) return UTREE_E_ARG;
     if (paired && (rank || (paired == PAIRS_TWO_FILES) != (mates_path != NULL))) return UTREE_E_ARG;
+    if (hitmap_path && (rank || !hm_msg)) return UTREE_E_ARG;
     int rc = UTREE_OK;
     uint64_t dev_printed = 0;
     utree_search_resume resume;
@@ -592,7 +712,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     /* The GG search on the reference's input format takes the device text pipeline (search_dev.c); it hands back input it
      * does not take -- malformed records, NUL bytes, lines fgets would split -- and the host framing below then reproduces
      * the reference on it case by case.  UTREE_HOST_TEXT=1 forces the host pipeline (tests, A/B). */
-    if (!rank && !paired && input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
+    if (!rank && !paired && !hitmap_path && input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
         rc = utree_search_file_device(ctr, devs, n_dev, fasta_path, out_path, do_rc, host_threads, rep, stats, &dev_printed, &resume);
         if (rc != UTREE_RETRY_HOST) return rc;
         rc = UTREE_OK;
@@ -605,7 +725,8 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     if (!P) { if (resume.fo >= 0) close(resume.fo); return UTREE_E_NOMEM; }
     P->ctr = ctr; P->rep = rep; P->n_dev = n_dev; P->do_rc = do_rc; P->rank = rank; P->input_format = input_format;
     P->progress_printed = dev_printed;
-    P->paired = paired; P->chunk = paired ? pairs_chunk_bytes() : CHUNK_BYTES;
+    P->paired = paired; P->chunk = paired || hitmap_path ? pairs_chunk_bytes() : CHUNK_BYTES;
+    P->hm = hitmap_path != NULL; P->fh = -1; P->hm_path = hitmap_path; P->hm_msg = hm_msg;
     P->path[0] = fasta_path; P->path[1] = mates_path;
     P->in[1].fd = -1;
     P->in[0].fd = open(fasta_path, O_RDONLY);
@@ -632,12 +753,20 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
         free(P);
         return UTREE_E_IO;
     }
+    if (P->hm) {
+        /* a map that cannot be opened, or whose labels cannot be written, does not stop the search: it runs without one and says so at its end */
+        P->fh = open(hitmap_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (P->fh < 0) snprintf(hm_msg, 512, "hit map %s: cannot open the file (%s)", hitmap_path, strerror(errno));
+        else if (write_labels(ctr, hitmap_path, hm_msg)) { close(P->fh); P->fh = -1; }
+        if (P->fh < 0) P->hm = 0;
+    }
     for (int k = 0; k < 2 && input_format != UTREE_INPUT_REFERENCE; ++k) {
         if (P->in[k].fd < 0) continue;
         P->in[k].gz = gzdopen(dup(P->in[k].fd), "rb");
         if (!P->in[k].gz) {
             if (P->in[0].gz) gzclose(P->in[0].gz);
             close(P->in[0].fd); if (P->in[1].fd >= 0) close(P->in[1].fd);
+            if (P->fh >= 0) close(P->fh);
             close(P->fo); free(P);
             return UTREE_E_IO;
         }
@@ -674,6 +803,16 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
             HIPM(hipMalloc((void **)&c->d_jlen, MAX_READS_PER_BATCH * 4));
             HIPM(hipMalloc((void **)&c->d_meta, sizeof(utree_pairs_meta)));
         }
+        if (P->hm) {                                                              /* the worst case of a shard: the slot's reads and bytes, a run per window */
+            const uint64_t tb = paired ? c->joined_cap : P->chunk;
+            c->runs_cap = utk_hitmap_wcap((uint32_t)MAX_READS_PER_BATCH, tb, do_rc);
+            c->hm_ws_bytes = utree_hitmap_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, tb, do_rc);
+            if (!c->hm_ws_bytes) { rc = UTREE_E_ARG; goto done; }
+            HIPM(hipMalloc((void **)&c->d_run_off, (MAX_READS_PER_BATCH + 1) * 8));
+            HIPM(hipMalloc((void **)&c->d_runs, (size_t)(c->runs_cap + 1) * sizeof(utree_hit_run)));
+            HIPM(hipMalloc((void **)&c->d_hm_meta, sizeof(utree_hitmap_meta)));
+            HIPM(hipMalloc(&c->d_hm_ws, c->hm_ws_bytes));
+        }
         c->ws_bytes = rank ? utree_rank_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, CHUNK_BYTES, LINELEN_MAX, do_rc, rank)
                            : utree_classify_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, paired ? c->joined_cap : CHUNK_BYTES, LINELEN_MAX, do_rc);
         if (!c->ws_bytes) { rc = UTREE_E_ARG; goto done; }
@@ -701,6 +840,7 @@ done:
         if (P->in[k].fd >= 0) close(P->in[k].fd);
     }
     if (P->fo >= 0) close(P->fo);
+    if (P->fh >= 0 && close(P->fh) && !hm_msg[0]) snprintf(hm_msg, 512, "hit map %s: cannot write the file (%s)", hitmap_path, strerror(errno));
     if (P->G) { for (int g = 0; g < n_dev; ++g) free_ctx(&P->G[g]); free(P->G); }
     for (int i = 0; i < NSLOTS; ++i) {
         slot_t *s = &P->slot[i];
@@ -713,6 +853,11 @@ done:
         if (s->m2.rel_off) hipHostFree(s->m2.rel_off);
         if (s->m2.seq_len) hipHostFree(s->m2.seq_len);
         if (s->h_meta) hipHostFree(s->h_meta);
+        if (s->h_hm_meta) hipHostFree(s->h_hm_meta);
+        if (s->h_run_off) hipHostFree(s->h_run_off);
+        if (s->h_runs) hipHostFree(s->h_runs);
+        free(s->hm_first); free(s->hm_count); free(s->hm_base);
+        for (int t = 0; t < FMT_MAX_THREADS; ++t) free(s->hm_buf[t]);
         free(s->m2.seq_off); free(s->m2.name_off); free(s->m2.name_len);
         for (int t = 0; t < FMT_MAX_THREADS; ++t) free(s->fmt_buf[t]);
     }
@@ -738,15 +883,18 @@ done:
 static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int paired,
                           const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format,
                           const char *profile_path, const char *coverage_path, const char *redist_path, uint32_t redist_passes,
-                          utree_search_stats *stats) {
+                          const char *hitmap_path, utree_search_stats *stats) {
     utree_reports *rep = NULL;
     utree_search_stats st;
+    char hm_msg[512] = "";                                         /* why the hit map was not written, when it was not */
     memset(&st, 0, sizeof st);
-    if (rank && redist_path) return UTREE_E_ARG;                   /* (another vote: no candidate sets) */
+    if (rank && (redist_path || hitmap_path)) return UTREE_E_ARG;  /* (another vote: no candidate sets; a hit-dependent subset of windows: no map) */
     int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, redist_path, redist_passes, &rep);
-    if (!rc && !rep) return search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, NULL, stats);   /* no report asked for */
-    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, rep, &st);
-    if (!rc) rc = utree_reports_write(rep, ctr, st.n_reads);
+    if (!rc && !rep && !hitmap_path)
+        return search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, NULL, NULL, NULL, stats);   /* no report asked for */
+    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, rep, hitmap_path, hm_msg, &st);
+    if (!rc && rep) rc = utree_reports_write(rep, ctr, st.n_reads);
+    if (!rc && hm_msg[0]) { utree_set_error_text(hm_msg); rc = UTREE_E_HITMAP; }
     utree_reports_free(rep);
     if (stats) *stats = st;
     return rc;
@@ -754,20 +902,20 @@ static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, con
 
 int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
                       int do_rc, int host_threads, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, NULL, 0, stats);
+    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, NULL, 0, NULL, stats);
 }
 int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
                            int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, NULL, 0, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, NULL, 0, NULL, stats);
 }
 int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                               int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, NULL, 0, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, NULL, 0, NULL, stats);
 }
 int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                                int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                                utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, NULL, 0, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, stats);
 }
 
 /* pairs: both mates of a pair cast one vote (include/utree_amd.h) */
@@ -775,7 +923,7 @@ int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, c
                             int do_rc, int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                             utree_search_stats *stats) {
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : PAIRS_INTERLEAVED, out_path, do_rc, NULL,
-                          host_threads, input_format, profile_path, coverage_path, NULL, 0, stats);
+                          host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, stats);
 }
 
 int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
@@ -784,7 +932,16 @@ int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n
                                    utree_search_stats *stats) {
     if (mates_path && interleaved) return UTREE_E_ARG;
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, stats);
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, NULL, stats);
+}
+
+int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int interleaved,
+                             const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
+                             const char *coverage_path, const char *redistribute_path, uint32_t max_passes, const char *hitmap_path,
+                             utree_search_stats *stats) {
+    if (mates_path && interleaved) return UTREE_E_ARG;
+    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, stats);
 }
 
 int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_off1, const uint32_t *d_len1, const uint8_t *d_bases2,
@@ -815,5 +972,5 @@ int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const c
     if (!dev || !params) return UTREE_E_ARG;
     int rc = utree_rank_reset(dev);
     if (rc) return rc;
-    return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, NULL, 0, stats);
+    return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, NULL, 0, NULL, stats);
 }

@@ -17,7 +17,8 @@ BUILD_GG_CLI_PATH = os.path.join(_HERE, "utree-buildGG")
 BUILD_CLI_PATH = os.path.join(_HERE, "utree-build")
 _LIB = None
 
-OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE, E_PAIRS = range(15)
+OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE, E_PAIRS, E_HITMAP = range(16)
+HIT_MISS, HIT_INVALID = 0xFFFFFFFF, 0xFFFFFFFE
 BUILD_E_MAP_EMPTY, BUILD_E_MAP, BUILD_E_FASTA, BUILD_E_NO_KMERS, BUILD_E_NAME = range(1, 6)
 FINE_AUTO = -1
 FANOUT_NONE, FANOUT_BROADCAST, FANOUT_UPLOAD = range(3)
@@ -91,6 +92,16 @@ class RedistEntry(C.Structure):
 class PairsMeta(C.Structure):
     """utree_pairs_meta: what the device join of a batch of pairs reports (error 0, 1 joined buffer too small, 2 a pair too long)."""
     _fields_ = [("total_bases", C.c_uint64), ("max_len", C.c_uint32), ("error", C.c_uint32)]
+
+
+class HitRun(C.Structure):
+    """utree_hit_run: a maximal stretch of windows with one code (a label index, HIT_MISS or HIT_INVALID)."""
+    _fields_ = [("code", C.c_uint32), ("count", C.c_uint32)]
+
+
+class HitmapMeta(C.Structure):
+    """utree_hitmap_meta: error 0, 1 run_capacity too small, 2 total_bases too small, 3 a query of 2^32 windows or more."""
+    _fields_ = [("total_runs", C.c_uint64), ("total_windows", C.c_uint64), ("error", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -198,6 +209,12 @@ SYMBOLS = {
                                    C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "utree_search_pairs_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                           C.c_int, C.c_char_p, C.c_char_p, C.POINTER(SearchStats)]),
+    "utree_hitmap_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_int]),
+    "utree_hitmap_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "utree_hitmap_format": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "utree_search_file_hitmap": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
+                                           C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p, C.POINTER(SearchStats)]),
     "utree_rank_search_file_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RankParams),
                                                  C.c_int, C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
 }
@@ -218,7 +235,7 @@ class UtreeError(RuntimeError):
     def __init__(self, code, what=""):
         self.code = code
         msg = load().utree_strerror(code).decode() if _LIB is not None else str(code)
-        if _LIB is not None and code in (4, 5, 11, 12, 13, 14):    # UTREE_E_NOMEM, UTREE_E_HIP, UTREE_E_DEVICE: which call, and what the runtime said; UTREE_E_PROFILE / UTREE_E_COVERAGE: why; UTREE_E_PAIRS: which file ended first
+        if _LIB is not None and code in (4, 5, 11, 12, 13, 14, 15):    # UTREE_E_HITMAP: why; UTREE_E_NOMEM, UTREE_E_HIP, UTREE_E_DEVICE: which call, and what the runtime said; UTREE_E_PROFILE / UTREE_E_COVERAGE: why; UTREE_E_PAIRS: which file ended first
             hip = (_LIB.utree_last_hip_error() or b"").decode(errors="replace")
             if hip:
                 msg += " [" + hip + "]"

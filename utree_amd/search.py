@@ -304,6 +304,42 @@ class DeviceTree:
         m = _lib.PairsMeta.from_buffer_copy(d_meta.cpu().numpy().tobytes())
         return joined, joff, jlen, dict(total_bases=int(m.total_bases), max_len=int(m.max_len), error=int(m.error))
 
+    def hitmap(self, bases, off, length, rc: bool = False, capacity: Optional[int] = None, total_bases: Optional[int] = None,
+               runs=None, workspace=None, sync: bool = True):
+        """utree_hitmap_batch: which label each k-mer window of each query hit, in window order, as runs.  Reads as classify() takes them
+        (pairs: join_pairs first).  capacity: entries of the runs tensor (default: one per window, which always suffices); runs: a
+        [>= capacity, 2] int32 tensor to write into.  Returns (run_off, runs, meta): int64 [n + 1], int32 [capacity, 2] of (code, count) --
+        read r's runs are runs[run_off[r]:run_off[r + 1]], codes HIT_MISS / HIT_INVALID read as -1 / -2 -- and meta = the dict {total_runs,
+        total_windows, error} read back once the stream has drained (error 1: capacity < total_runs, nothing at or beyond it was written).
+        sync=False: the call returns at once (asynchronous on torch's current stream, workspace= the caller's own) and meta is the int64 [3]
+        device tensor (total_runs, total_windows, error)."""
+        import torch
+        n = off.numel()
+        dev = bases.device
+        if total_bases is None:
+            total_bases = int(length.sum().item()) if n else 0
+        need = _lib.load().utree_hitmap_workspace_bytes(self._h, n, total_bases, int(rc))
+        if not need:
+            raise _lib.UtreeError(_lib.E_ARG, "utree_hitmap_workspace_bytes")
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        if capacity is None:
+            capacity = 2 * total_bases + n if rc else total_bases
+        if runs is None:
+            runs = torch.empty((max(capacity, 1), 2), dtype=torch.int32, device=dev)
+        assert runs.numel() >= 2 * capacity and runs.is_contiguous() and workspace.numel() >= need
+        run_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_meta = torch.zeros(3, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _lib.check(_lib.load().utree_hitmap_batch(self._h, bases.data_ptr(), off.data_ptr(), length.data_ptr(), n, total_bases, int(rc),
+                                                  run_off.data_ptr(), runs.data_ptr(), capacity, d_meta.data_ptr(), workspace.data_ptr(),
+                                                  workspace.numel(), stream.cuda_stream), "utree_hitmap_batch")
+        if not sync:
+            return run_off, runs, d_meta
+        stream.synchronize()
+        m = _lib.HitmapMeta.from_buffer_copy(d_meta.cpu().numpy().tobytes())
+        return run_off, runs, dict(total_runs=int(m.total_runs), total_windows=int(m.total_windows), error=int(m.error))
+
     def poll(self):
         """utree_classify_poll: raises UtreeError(E_DEVICE) if a batch that has finished since the last call found its workspace
         too small (call after the stream has drained; its results are not to be used)."""
@@ -613,7 +649,8 @@ def write_coverage(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
 
 def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: bool = False, threads: int = 0,
               input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None,
-              mates: Optional[str] = None, interleaved: bool = False, redistribute: Optional[str] = None, redist_passes: int = 100):
+              mates: Optional[str] = None, interleaved: bool = False, redistribute: Optional[str] = None, redist_passes: int = 100,
+              hitmap: Optional[str] = None):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
     FASTA / gzip input.  profile: also write the per-taxon read counts there; coverage: also write the per-taxon k-mer
@@ -622,11 +659,19 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
     2i+1 of pair i.  A pair is searched as mate 1 + "N" + mate 2, named by mate 1 (mate names are not compared); stats.n_reads counts
     pairs; unequal record counts return E_PAIRS after the complete pairs were written.
     redistribute: also write the reads redistributed among the labels each hit most often there (utree_search_file_redistribute), at most
-    redist_passes passes; a redistribution that cannot be written returns E_PROFILE."""
+    redist_passes passes; a redistribution that cannot be written returns E_PROFILE.
+    hitmap: also write every query's k-mer hit map there, and the label texts to hitmap + ".labels" (utree_search_file_hitmap); a map that
+    cannot be written returns E_HITMAP."""
     if mates is not None and interleaved:
         raise ValueError("search_gg: give mates= or interleaved=True, not both")
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     st = _lib.SearchStats()
+    if hitmap is not None:
+        enc = lambda p: p.encode() if p is not None else None
+        code = _lib.load().utree_search_file_hitmap(db._h, arr, len(trees), fasta.encode(), enc(mates), int(interleaved), out.encode(), int(rc),
+                                                    threads, input_format, enc(profile), enc(coverage), enc(redistribute), redist_passes,
+                                                    hitmap.encode(), C.byref(st))
+        return code, st
     if redistribute is not None:
         code = _lib.load().utree_search_file_redistribute(db._h, arr, len(trees), fasta.encode(), mates.encode() if mates is not None else None,
                                                           int(interleaved), out.encode(), int(rc), threads, input_format,
