@@ -583,6 +583,79 @@ int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, 
                              const char *hitmap_path, utree_search_stats *stats);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-sample taxon table of multiplexed reads (no counterpart in itree.c, whose users parse the per-read lines in a script).  Pipelines hand
+ * the search ONE combined reads file whose records are named <sample>_<n> (PlateA.well7_1532); what they take away is a taxon x sample matrix.
+ *   Sample id.  Taken from the name the output line prints (a pair: mate 1's name; with an opt-in input format the name that format's framing
+ *     yields): the bytes before the LAST occurrence of the delimiter byte (default '_').  A name without the delimiter is its own id; an id may
+ *     be empty (the name "_7", an empty name).  Ids are compared as byte strings, never by hash alone.
+ *   Figures.  For every (sample, taxon) the number of the sample's reads whose output line prints exactly that taxon -- the profile's `assigned`,
+ *     keyed (label, cut) as the profile's entries and merged by printed text exactly as utree_profile_write merges; per sample all its reads and
+ *     its reads without a line.
+ *   File.  Every line ends in '\n', fields are separated by one TAB:
+ *     # reads\t<N>\tclassified\t<G>\tunclassified\t<N-G>\tsamples\t<S>
+ *     # taxon\t<id_1>\t...\t<id_S>
+ *     # reads\t<n_1>\t...\t<n_S>
+ *     # unclassified\t<u_1>\t...\t<u_S>
+ *     <taxon>\t<c_1>\t...\t<c_S>          one line per taxon some sample assigned a read to
+ *     Samples are in unsigned bytewise order of their raw ids, shorter first, and so are the taxa; the empty taxon is a line that begins with
+ *     the TAB, as in the profile.  There are NO ';'-prefix rows: the matrix holds `assigned`, and a matrix of `assigned` sums to any rank by
+ *     adding the rows below a prefix (the profile's `clade` column is that sum over all samples).  In a printed id a TAB, a CR and a backslash
+ *     appear as \t, \r, \\; nothing else is escaped.  With S = 0 the three '#' lines after the first end right after their first field.
+ *   A reader can check: column j sums to n_j - u_j; a row sums to that taxon's `assigned` in the profile of the same run; the n_j sum to N.
+ * The ids are interned and the cells counted on ONE device while a chunk's text and records are there.
+ * ---------------------------------------------------------------------------------------------- */
+#define UTREE_SAMPLES_DEFAULT_CAPACITY (1u << 16)   /* distinct sample ids of a search's handles; UTREE_SAMPLE_CAPACITY overrides */
+#define UTREE_SAMPLES_DEFAULT_CELLS    (1u << 22)   /* slots of their (sample, taxon) cell tables; UTREE_SAMPLE_CELLS overrides   */
+typedef struct utree_samples utree_samples;
+/* A table on dev's device for dev's labels.  sample_capacity: the most distinct ids (1 .. 2^19; the id table has twice the slots, 28 B of HBM
+ * each, and the ids' bytes an arena of 256 B per sample, 1 MiB at least); cell_capacity: slots of the (sample, label, cut) cell table (rounded
+ * up to a power of two, 16 B each) -- keep it at twice the distinct cells.  delim: the delimiter byte, not TAB, space, CR or LF (else
+ * UTREE_E_ARG).  UTREE_E_UNSUPPORTED for a database of 2^28 labels or more. */
+int utree_samples_create(utree_dev *dev, uint32_t sample_capacity, uint32_t cell_capacity, int delim, utree_samples **out);
+/* Adds n_reads records and their names on `stream`, asynchronously: record r's name is d_text[d_name_off[r] .. + d_name_len[r]), offsets
+ * relative to d_text, which holds text_bytes bytes (a name that leaves them is refused, not read).  Any number of streams may add to one handle
+ * at the same time. */
+int utree_samples_add(utree_samples *s, const uint8_t *d_text, uint64_t text_bytes, const uint32_t *d_name_off, const uint32_t *d_name_len,
+                      const utree_result *d_res, uint32_t n_reads, void *stream);
+/* Empties the table (synchronous: waits for the device first). */
+int utree_samples_reset(utree_samples *s);
+void utree_samples_free(utree_samples *s);
+typedef struct { uint32_t sample, label; int32_t cut; uint32_t pad; uint64_t reads; } utree_samples_cell;   /* (label, cut) as utree_profile_entry */
+/* Synchronous (waits for the device).  Sample i (numbered in the order the device first claimed the ids: another device numbers them otherwise)
+ * has the id h_ids[h_id_off[i] .. h_id_off[i + 1]), h_reads[i] reads of which h_unclassified[i] print no line; the cells with reads > 0 go to
+ * h_cells.  h_id_off has sample_cap + 1 entries, h_reads and h_unclassified sample_cap.  *n_samples, *n_id_bytes, *n_cells are always set when
+ * the device's state is sound: UTREE_E_ARG when one exceeds its capacity (nothing else is written then: size the arrays and call again).
+ * *n_reads (may be NULL) = records added.  UTREE_E_DEVICE when a batch found the id table, the arena or the cell table full, a record named a
+ * label the database lacks, a name lay outside its text, a taxon was longer than 65532 bytes, or the counters do not add up: there is no table
+ * then, and utree_last_hip_error names the cause and the knob. */
+int utree_samples_read(utree_samples *s, uint8_t *h_ids, size_t id_cap, uint64_t *h_id_off, uint64_t *h_reads, uint64_t *h_unclassified,
+                       size_t sample_cap, utree_samples_cell *h_cells, size_t cell_cap, size_t *n_samples, size_t *n_id_bytes, size_t *n_cells,
+                       uint64_t *n_reads);
+/* one handle's read-back, as utree_samples_read fills it */
+typedef struct {
+    const uint8_t *ids; const uint64_t *id_off; const uint64_t *reads, *unclassified; size_t n_samples;
+    const utree_samples_cell *cells; size_t n_cells; uint64_t n_reads;
+} utree_samples_table;
+/* Host only: the read-backs of any number of handles (label indices of ctr) -> one file in the layout above.  Samples are merged by id text and
+ * taxa by printed text, so several devices may number their samples independently.  UTREE_E_ARG when the figures contradict each other (a
+ * sample's reads are not its unclassified reads plus its cells, the samples' reads not n_reads, a cell names no sample or label). */
+int utree_samples_write(const utree_ctr *ctr, const utree_samples_table *tabs, size_t n_tabs, const char *path);
+/* utree_search_file_hitmap that also writes the search's sample table to `samples_path` (NULL: exactly that call -- nothing allocated, uploaded
+ * or launched), ids cut at `delim` (0: '_').  The per-read output, stdout, the stats and every other report are those of a search without it,
+ * and so is the pipeline: a search the device text pipeline takes stays there (stats.pipeline == 1).  The table is written after the
+ * redistribution and before the profile, when the search has succeeded and exactly its reads were added; a table that cannot be written -- the
+ * file, a capacity (UTREE_SAMPLE_CAPACITY, default 2^16 ids; UTREE_SAMPLE_CELLS, default 2^22 cells) -- returns UTREE_E_PROFILE (there is no
+ * code of its own) and utree_last_hip_error names the table's file and the cause; a search that fails leaves the path as it was. */
+int utree_search_file_samples(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                              int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
+                              const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
+                              const char *hitmap_path, const char *samples_path, int delim, utree_search_stats *stats);
+/* utree_rank_search_file_profile with the same two arguments: the rank-specific search's records make the same table. */
+int utree_rank_search_file_samples(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
+                                   const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
+                                   const char *samples_path, int delim, utree_search_stats *stats);
+
+/* ------------------------------------------------------------------------------------------------
  * `.ubt` -> `.ctr` = XT_cmp32(filename, outfile) (itree.c:1234-1315; `xtree-compress`), SURVEY.md §8(f) rank 2.
  * Node dump streamed through `device`; output byte-identical to the reference's, first-bin quirk included.
  * ---------------------------------------------------------------------------------------------- */

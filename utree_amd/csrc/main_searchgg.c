@@ -38,6 +38,14 @@
  *                           run without it.  May be combined with UTREE_PROFILE, UTREE_COVERAGE, UTREE_REDISTRIBUTE, UTREE_MATES /
  *                           UTREE_INTERLEAVED and UTREE_INPUT.  A path that cannot be opened: a message on stderr, exit 1, before the search.
  *                           A map that cannot be written while searching: the usual stdout, a message on stderr, exit 1
+ *     UTREE_SAMPLE_TABLE=<path> opt-in, both binaries: the reads file is a combined one whose records are named <sample>_<n>; also write the taxon x
+ *                           sample matrix of read counts to <path> (include/utree_amd.h: utree_samples_write), the ids interned and the cells
+ *                           counted on the GPU while it searches; stdout, the output, the pipeline and the other reports are those of a run
+ *                           without it.  UTREE_SAMPLE_DELIM=<one byte> is the delimiter in front of <n> (default '_'; not TAB, space, CR or LF:
+ *                           anything else is a message and exit 1), UTREE_SAMPLE_CAPACITY=<ids> (default 2^16) and UTREE_SAMPLE_CELLS=<slots>
+ *                           (default 2^22) size the tables.  May be combined with every other variable.  Path checks as for UTREE_PROFILE.  A
+ *                           file named without the convention (every read its own sample) ends after a complete search: the usual stdout, one
+ *                           line on stderr that names UTREE_SAMPLE_CAPACITY, exit 1.  Unset: nothing is allocated, uploaded or launched
  *     UTREE_MATES=<path>    opt-in, xtree-searchGG only: paired-end reads.  fastaToSearch.fa holds the first mates, <path> the second; pair i is
  *                           record i of both.  A pair is searched as ONE query, mate 1 + "N" + mate 2, and prints one line under mate 1's name
  *                           (include/utree_amd.h: utree_search_pairs_file; mate names are not compared); "Searched N queries" and the profile
@@ -129,6 +137,16 @@ int main(int argc, char *argv[]) {
     if (hitmap && !DO_GG) { fputs("[utree_amd] UTREE_HITMAP is ignored: the rank-specific search looks at a hit-dependent subset of windows and has no hit map\n", stderr); hitmap = NULL; }
     if (hitmap) check_report_path(hitmap, "hit map");
     (void)redist_passes;                                                                  /* (xtree-search: no redistribution) */
+    const char *samples = getenv("UTREE_SAMPLE_TABLE");
+    if (samples && *samples) check_report_path(samples, "sample table"); else samples = NULL;
+    int sample_delim = '_';
+    const char *sd = getenv("UTREE_SAMPLE_DELIM");
+    if (sd) {
+        if (strlen(sd) != 1 || sd[0] == '\t' || sd[0] == ' ' || sd[0] == '\r' || sd[0] == '\n') {
+            fputs("ERROR: UTREE_SAMPLE_DELIM must be one byte, and not TAB, space, CR or LF\n", stderr); exit(1);
+        }
+        sample_delim = (unsigned char)sd[0];
+    }
 
     utree_ctr *ctr = NULL;
     int rc = utree_ctr_open(argv[1], &ctr);
@@ -197,9 +215,10 @@ int main(int argc, char *argv[]) {
     if (getenv("UTREE_SLACK")) prm.slack = (uint32_t)atoi(getenv("UTREE_SLACK"));
     if (getenv("UTREE_SPARSITY")) prm.sparsity = (uint32_t)atoi(getenv("UTREE_SPARSITY"));
     if (getenv("UTREE_TOLERANCE")) prm.tolerance = (uint32_t)atoi(getenv("UTREE_TOLERANCE"));
-    rc = utree_rank_search_file_profile(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, &st);   /* (a NULL path: no such report) */
+    rc = utree_rank_search_file_samples(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, samples, sample_delim, &st);   /* (a NULL path: no such report) */
 #else
-    if (hitmap) rc = utree_search_file_hitmap(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, &st);
+    if (samples) rc = utree_search_file_samples(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, samples, sample_delim, &st);
+    else if (hitmap) rc = utree_search_file_hitmap(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, &st);
     else if (redist) rc = utree_search_file_redistribute(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, &st);
     else if (mates || interleaved) rc = utree_search_pairs_file(ctr, devs, n_dev, argv[2], mates, argv[3], doRC, threads, fmt, profile, coverage, &st);
     else rc = utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st);   /* (a NULL path: no such report) */

@@ -1,5 +1,5 @@
-/* reports.c -- the opt-in reports of one whole-file search (reports.h): a profile (profile.c), a coverage handle (coverage.c) and / or a
- * redistribution handle (redist.c) per device handle, fed chunk by chunk, merged and written when the search has succeeded. */
+/* reports.c -- the opt-in reports of one whole-file search (reports.h): a profile (profile.c), a coverage handle (coverage.c), a redistribution
+ * handle (redist.c) and / or a sample table (samples.c) per device handle, fed chunk by chunk, merged and written when the search has succeeded. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -9,20 +9,21 @@
 
 struct utree_reports {
     int n_dev;
-    const char *profile_path, *coverage_path, *redist_path;
+    const char *profile_path, *coverage_path, *redist_path, *samples_path;
     uint32_t redist_passes;
-    struct { utree_profile *prof; utree_coverage *cov; utree_redist *rd; } dev[];      /* NULL: the search writes no such report */
+    struct { utree_profile *prof; utree_coverage *cov; utree_redist *rd; utree_samples *smp; } dev[];      /* NULL: the search writes no such report */
 };
 
 int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *profile_path, const char *coverage_path,
-                         const char *redist_path, uint32_t redist_passes, utree_reports **out) {
+                         const char *redist_path, uint32_t redist_passes, const char *samples_path, int samples_delim, utree_reports **out) {
     *out = NULL;
-    if (!profile_path && !coverage_path && !redist_path) return UTREE_OK;
+    if (!profile_path && !coverage_path && !redist_path && !samples_path) return UTREE_OK;
     if (redist_path && redist_passes > 1000) return UTREE_E_ARG;
     if (!ctr || !devs || n_dev < 1) return UTREE_E_ARG;
     utree_reports *rep = (utree_reports *)calloc(1, sizeof *rep + (size_t)n_dev * sizeof rep->dev[0]);
     if (!rep) return UTREE_E_NOMEM;
     rep->n_dev = n_dev; rep->profile_path = profile_path; rep->coverage_path = coverage_path; rep->redist_path = redist_path;
+    rep->samples_path = samples_path;
     rep->redist_passes = redist_passes ? redist_passes : UTREE_REDIST_DEFAULT_PASSES;
     const char *e = getenv("UTREE_PROFILE_CAPACITY");
     const uint32_t cap = e && atoll(e) >= 1 && atoll(e) <= (1ll << 30) ? (uint32_t)atoll(e) : UTREE_PROFILE_DEFAULT_CAPACITY;
@@ -32,6 +33,10 @@ int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, cons
     const char *er = getenv("UTREE_REDIST_CAPACITY");
     const uint32_t rcap = er && atoll(er) >= 1 && atoll(er) <= (1ll << 28) ? (uint32_t)atoll(er) : UTREE_REDIST_DEFAULT_CAPACITY;
     for (int g = 0; redist_path && g < n_dev && !rc; ++g) rc = utree_redist_create(devs[g], rcap, &rep->dev[g].rd);
+    const char *es = getenv("UTREE_SAMPLE_CAPACITY"), *ec = getenv("UTREE_SAMPLE_CELLS");
+    const uint32_t scap = es && atoll(es) >= 1 && atoll(es) <= (1ll << 19) ? (uint32_t)atoll(es) : UTREE_SAMPLES_DEFAULT_CAPACITY;
+    const uint32_t ccap = ec && atoll(ec) >= 1 && atoll(ec) <= (1ll << 30) ? (uint32_t)atoll(ec) : UTREE_SAMPLES_DEFAULT_CELLS;
+    for (int g = 0; samples_path && g < n_dev && !rc; ++g) rc = utree_samples_create(devs[g], scap, ccap, samples_delim ? samples_delim : '_', &rep->dev[g].smp);
     if (rc) { utree_reports_free(rep); return rc; }
     *out = rep;
     return UTREE_OK;
@@ -42,6 +47,7 @@ void utree_reports_free(utree_reports *rep) {
     for (int g = 0; g < rep->n_dev; ++g) utree_profile_free(rep->dev[g].prof);
     for (int g = 0; g < rep->n_dev; ++g) utree_coverage_free(rep->dev[g].cov);
     for (int g = 0; g < rep->n_dev; ++g) utree_redist_free(rep->dev[g].rd);
+    for (int g = 0; g < rep->n_dev; ++g) utree_samples_free(rep->dev[g].smp);
     free(rep);
 }
 
@@ -50,6 +56,7 @@ int utree_reports_reset(utree_reports *rep) {
     for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].prof) rc = utree_profile_reset(rep->dev[g].prof);
     for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].cov) rc = utree_coverage_reset(rep->dev[g].cov);
     for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].rd) rc = utree_redist_reset(rep->dev[g].rd);
+    for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].smp) rc = utree_samples_reset(rep->dev[g].smp);
     return rc;
 }
 
@@ -62,10 +69,14 @@ int utree_reports_classify(utree_reports *rep, int g, utree_dev *dev, const uint
     return utree_classify_batch(dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream);
 }
 
+int utree_reports_wants_names(const utree_reports *rep) { return rep && rep->samples_path; }
+
 int utree_reports_add(utree_reports *rep, int g, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
-                      const utree_result *d_res, uint32_t n, int do_rc, int rank, void *stream) {
+                      const utree_result *d_res, uint32_t n, int do_rc, int rank, const uint8_t *d_text, uint64_t text_bytes,
+                      const uint32_t *d_name_off, const uint32_t *d_name_len, void *stream) {
     if (!rep) return UTREE_OK;
     int rc = rep->dev[g].prof ? utree_profile_add(rep->dev[g].prof, d_res, n, stream) : UTREE_OK;
+    if (!rc && rep->dev[g].smp) rc = utree_samples_add(rep->dev[g].smp, d_text, text_bytes, d_name_off, d_name_len, d_res, n, stream);
     if (!rc && rep->dev[g].cov && !rank) rc = utree_coverage_add(rep->dev[g].cov, d_bases, d_off, d_len, n, do_rc, stream);
     return rc;
 }
@@ -152,13 +163,54 @@ static int write_redist(const utree_reports *rep, const utree_ctr *ctr, uint64_t
     return rc;
 }
 
+/* reads every device's table back, checks that n_reads_expected reads were added (else UTREE_E_DEVICE) and writes the merged file */
+static int write_samples(const utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads_expected) {
+    const char *path = rep->samples_path;
+    utree_samples_table *tabs = (utree_samples_table *)calloc((size_t)rep->n_dev, sizeof *tabs);
+    if (!tabs) return UTREE_E_NOMEM;
+    int rc = UTREE_OK;
+    uint64_t reads = 0;
+    for (int g = 0; g < rep->n_dev && !rc; ++g) {
+        size_t ns = 0, nb = 0, nc = 0;
+        rc = utree_samples_read(rep->dev[g].smp, NULL, 0, NULL, NULL, NULL, 0, NULL, 0, &ns, &nb, &nc, NULL);     /* the sizes */
+        if (rc == UTREE_E_ARG) rc = UTREE_OK;
+        if (rc) break;
+        uint8_t *ids = (uint8_t *)malloc(nb ? nb : 1);
+        uint64_t *w = (uint64_t *)malloc((3 * ns + 1) * 8);
+        utree_samples_cell *cells = (utree_samples_cell *)malloc((nc ? nc : 1) * sizeof *cells);
+        tabs[g].ids = ids; tabs[g].id_off = w; tabs[g].reads = w ? w + ns + 1 : NULL; tabs[g].unclassified = w ? w + 2 * ns + 1 : NULL; tabs[g].cells = cells;
+        if (!ids || !w || !cells) { rc = UTREE_E_NOMEM; break; }
+        rc = utree_samples_read(rep->dev[g].smp, ids, nb, w, w + ns + 1, w + 2 * ns + 1, ns, cells, nc, &tabs[g].n_samples, &nb, &tabs[g].n_cells,
+                                &tabs[g].n_reads);
+        reads += tabs[g].n_reads;
+    }
+    char msg[700];
+    if (rc == UTREE_E_DEVICE) {                                    /* (the read-back's text begins "sample table: ") */
+        const char *why = utree_last_hip_error();
+        snprintf(msg, sizeof msg, "sample table %s: %s", path, strncmp(why, "sample table: ", 14) ? why : why + 14);
+    }
+    else if (rc) snprintf(msg, sizeof msg, "sample table %s: the tables could not be read back (%s)", path, utree_strerror(rc));
+    else if (reads != n_reads_expected) {                          /* every read added exactly once, or no file */
+        snprintf(msg, sizeof msg, "sample table %s: %llu reads added, the search read %llu", path, (unsigned long long)reads,
+                 (unsigned long long)n_reads_expected);
+        rc = UTREE_E_DEVICE;
+    } else if ((rc = utree_samples_write(ctr, tabs, (size_t)rep->n_dev, path)))
+        snprintf(msg, sizeof msg, "sample table %s: cannot write the file (%s)", path, utree_strerror(rc));
+    if (rc) utree_set_error_text(msg);
+    for (int g = 0; g < rep->n_dev; ++g) { free((void *)tabs[g].ids); free((void *)tabs[g].id_off); free((void *)tabs[g].cells); }
+    free(tabs);
+    return rc;
+}
+
 int utree_reports_write(utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads) {
     if (!rep) return UTREE_OK;
     const int ce = rep->coverage_path ? write_coverage(rep, ctr, n_reads) : UTREE_OK;
     char keep[512];
     const int re = rep->redist_path ? write_redist(rep, ctr, n_reads) : UTREE_OK;
     if (re) snprintf(keep, sizeof keep, "%s", utree_last_hip_error());
+    const int se = rep->samples_path ? write_samples(rep, ctr, n_reads) : UTREE_OK;
+    if (se && !re) snprintf(keep, sizeof keep, "%s", utree_last_hip_error());          /* (the redistribution's failure wins) */
     if (rep->profile_path && write_profile(rep, ctr, n_reads)) return UTREE_E_PROFILE;
-    if (re) { utree_set_error_text(keep); return UTREE_E_PROFILE; }      /* (no code of its own; a profile that was written sets no text) */
+    if (re || se) { utree_set_error_text(keep); return UTREE_E_PROFILE; }      /* (no code of their own; a profile that was written sets no text) */
     return ce ? UTREE_E_COVERAGE : UTREE_OK;      /* (a profile that was written sets no text: the coverage's stands) */
 }

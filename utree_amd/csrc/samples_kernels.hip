@@ -1,0 +1,224 @@
+// samples_kernels.hip -- per-sample taxon counts of a batch of multiplexed reads (utree_samples_add, samples.c).
+//
+// One pass over a batch's records and names.  A read's sample id is its name up to the LAST delimiter byte (the whole name without one); its
+// taxon is the key (label, cut) of its record, as in profile_kernels.hip.  The state lives on the device for the whole search (samples.h):
+//   ids / arena      open-addressed table of the distinct ids; a slot's key points at the id's bytes in the arena.  A sample IS its slot here:
+//                    every counter is indexed by the slot, so no lane ever needs a number another lane has yet to publish
+//   index            the dense index a claim took from the counter of distinct ids (the read-back's numbering; the counter is the capacity check)
+//   reads / uncl     per sample: all its reads, its reads without a line
+//   cells            open-addressed {key, reads} slots, key = sample slot | label | cut packed into 64 bits
+//
+// Interning takes over redist_kernels.hip's insert, which has no lane waiting for another: probe read-only and compare WHOLE ids; on a miss
+// write the bytes to arena space reserved with one atomic and claim the free slot with one compare-and-swap (release); whoever loses that race
+// compares against the winner's bytes -- complete, they were written before the claim -- and probes on, keeping its copy for the next free
+// slot.  A combined file is a concatenation of samples, so ids arrive in long runs: a lane first compares its id with its predecessor lane's
+// (length, then bytes) and then with the one it had 1024 records before; only a lane that begins a run in both senses goes to the table, and the
+// lanes behind it take its slot from a wavefront shuffle.
+//
+// Counting is profile_add_k's: one workgroup per CU, a hash table of cells in LDS, runs of equal keys carried in registers, and at the end one
+// no-return atomic per non-zero LDS slot into the device tables.  Unclassified reads are a cell of their own in LDS only (cut =
+// UTK_SAMPLES_CUT_UNCL) and leave it for uncl[]; every flushed count also goes to reads[], so the read-back can check reads = uncl + cells per
+// sample.  Nothing is dropped silently: a full id table or arena, a full cell table, a label the database lacks, a name outside the text and a
+// taxon too long for the packed key each set a bit of the error word, and the read-back then fails.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "samples.h"
+
+#define SM_BLOCK 1024
+#define SM_HSLOTS 8192u                    // LDS hash slots: 64 KiB of keys + 32 KiB of counts
+#define SM_LDS_PROBES 32u
+#define SM_DEV_PROBES 4096u
+#define SM_UNROLL 4
+#define SM_KEY_FREE (~0ull)                // an unused cell slot (and "no run yet")
+#define SM_ID_FREE 0ull                    // an unused id slot: a key's low word is the id's length + 1
+#define SM_NONE 0xFFFFFFFFu                // no sample: the error word says why
+
+__device__ __forceinline__ uint64_t sm_mix(uint64_t k) {
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+    return k ^ (k >> 33);
+}
+__device__ __forceinline__ void sm_add(unsigned long long *p, unsigned long long v) {
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void sm_flag(const utk_samples_tab &t, unsigned long long f) {
+    (void)__hip_atomic_fetch_or(t.misc + 1, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint64_t sm_key(uint32_t slot, uint32_t label, uint32_t cut16) {
+    return (uint64_t)slot << (UTK_SAMPLES_LABEL_BITS + 16u) | (uint64_t)label << 16 | cut16;
+}
+
+// bytes of the name in front of its last delimiter; the whole name when it has none
+__device__ __forceinline__ uint32_t sm_id_len(const uint8_t *__restrict__ name, uint32_t len, uint32_t delim) {
+    for (uint32_t i = len; i > 0; --i) if (name[i - 1] == delim) return i - 1;
+    return len;
+}
+__device__ __forceinline__ bool sm_same(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) if (a[i] != b[i]) return false;
+    return true;
+}
+
+// the slot of the id's n bytes, claimed when no slot holds them yet; SM_NONE (and a flag) when the table or the arena has no room
+__device__ uint32_t sm_intern(const utk_samples_tab &t, const uint8_t *__restrict__ id, uint32_t n) {
+    uint32_t h = 0x811C9DC5u;
+    for (uint32_t i = 0; i < n; ++i) h = (h ^ id[i]) * 0x01000193u;
+    h ^= h >> 15; h *= 0x85EBCA77u; h ^= h >> 13;
+    unsigned long long mine = SM_ID_FREE;                  // the key of this lane's own arena copy, once written
+    const uint32_t probes = t.id_mask + 1 < SM_DEV_PROBES ? t.id_mask + 1 : SM_DEV_PROBES;
+    for (uint32_t p = 0; p < probes; ++p) {
+        const uint32_t s = (h + p) & t.id_mask;
+        unsigned long long *slot = t.ids + s;
+        unsigned long long k = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == SM_ID_FREE) {
+            if (mine == SM_ID_FREE) {
+                const unsigned long long at = __hip_atomic_fetch_add(t.misc + 2, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (at + n > t.arena_cap) { sm_flag(t, UTK_SAMPLES_F_ARENA); return SM_NONE; }
+                for (uint32_t i = 0; i < n; ++i) t.arena[at + i] = id[i];
+                mine = at << 32 | (n + 1u);
+            }
+            unsigned long long expect = SM_ID_FREE;
+            if (__hip_atomic_compare_exchange_strong(slot, &expect, mine, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) {
+                const unsigned long long c = __hip_atomic_fetch_add(t.misc + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (c >= t.sample_cap) { sm_flag(t, UTK_SAMPLES_F_TABLE); return SM_NONE; }
+                t.index[s] = (uint32_t)c;
+                return s;
+            }
+            k = expect;                                    // somebody else's id, complete: compare like any occupied slot
+        }
+        if ((uint32_t)k != n + 1u) continue;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // the bytes behind a key that has been seen
+        const uint8_t *a = t.arena + (k >> 32);
+        bool same = true;
+        for (uint32_t i = 0; i < n && same; ++i) same = __hip_atomic_load(a + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == id[i];
+        if (same) return s;
+    }
+    sm_flag(t, UTK_SAMPLES_F_TABLE);
+    return SM_NONE;
+}
+
+// cnt reads of a cell into the device tables: the sample's reads, then its unclassified reads or the cell's slot (or the full flag)
+__device__ void sm_global_add(const utk_samples_tab &t, uint64_t key, uint32_t cnt) {
+    const uint32_t slot = (uint32_t)(key >> (UTK_SAMPLES_LABEL_BITS + 16u));
+    sm_add(t.reads + slot, cnt);
+    if ((uint32_t)(key & 0xFFFFu) == UTK_SAMPLES_CUT_UNCL) { sm_add(t.uncl + slot, cnt); return; }
+    const uint32_t h = (uint32_t)sm_mix(key);
+    const uint32_t probes = t.cell_mask + 1 < SM_DEV_PROBES ? t.cell_mask + 1 : SM_DEV_PROBES;
+    for (uint32_t p = 0; p < probes; ++p) {
+        unsigned long long *c = t.cells + 2 * (size_t)((h + p) & t.cell_mask);
+        unsigned long long k = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == SM_KEY_FREE) {
+            k = SM_KEY_FREE;
+            __hip_atomic_compare_exchange_strong(c, &k, (unsigned long long)key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (k == SM_KEY_FREE) k = key;     // we claimed it
+        }
+        if (k == key) { sm_add(c + 1, cnt); return; }
+    }
+    sm_flag(t, UTK_SAMPLES_F_CELLS);
+}
+
+struct SmLds {
+    unsigned long long key[SM_HSLOTS];
+    uint32_t cnt[SM_HSLOTS];
+    uint32_t flags;
+};
+
+__device__ void sm_lds_add(SmLds &s, const utk_samples_tab &t, uint64_t key, uint32_t cnt) {
+    if (!cnt) return;
+    const uint32_t h = (uint32_t)sm_mix(key);
+    for (uint32_t p = 0; p < SM_LDS_PROBES; ++p) {
+        const uint32_t i = (h + p) & (SM_HSLOTS - 1);
+        unsigned long long k = s.key[i];
+        if (k == SM_KEY_FREE) {
+            k = atomicCAS(&s.key[i], SM_KEY_FREE, (unsigned long long)key);
+            if (k == SM_KEY_FREE) k = key;
+        }
+        if (k == key) { atomicAdd(&s.cnt[i], cnt); return; }
+    }
+    sm_global_add(t, key, cnt);
+}
+
+__global__ void __launch_bounds__(SM_BLOCK) samples_add_k(utk_samples_tab t, const uint8_t *__restrict__ text, uint64_t text_bytes,
+                                                          const uint32_t *__restrict__ name_off, const uint32_t *__restrict__ name_len,
+                                                          const utree_result *__restrict__ res, uint32_t n, uint32_t per_block) {
+    __shared__ SmLds s;
+    for (uint32_t i = threadIdx.x; i < SM_HSLOTS; i += SM_BLOCK) { s.key[i] = SM_KEY_FREE; s.cnt[i] = 0; }
+    if (threadIdx.x == 0) s.flags = 0;
+    __syncthreads();
+
+    const uint64_t begin = (uint64_t)blockIdx.x * per_block;
+    const uint64_t end = begin + per_block < n ? begin + per_block : n;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t run = SM_KEY_FREE;
+    uint32_t run_n = 0, flags = 0;
+    uint32_t pv_off = 0, pv_idl = 0, pv_slot = SM_NONE;    // the id this thread had one round before, and its slot
+    bool pv_ok = false;
+    for (uint64_t b0 = begin; b0 < end; b0 += (uint64_t)SM_UNROLL * SM_BLOCK) {       // (the same trips in every lane: the shuffles below need them all)
+        uint32_t off[SM_UNROLL], nlen[SM_UNROLL], lab[SM_UNROLL], fnd[SM_UNROLL];
+        int32_t cut[SM_UNROLL];
+        bool ok[SM_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SM_UNROLL; ++u) {                        // all loads first: four records in flight per thread
+            const uint64_t r = b0 + (uint64_t)u * SM_BLOCK + threadIdx.x;
+            ok[u] = r < end; off[u] = 0; nlen[u] = 0; lab[u] = 0; cut[u] = -4; fnd[u] = 0;
+            if (ok[u]) { off[u] = name_off[r]; nlen[u] = name_len[r]; lab[u] = res[r].label; cut[u] = res[r].cut; fnd[u] = res[r].found; }
+        }
+#pragma unroll
+        for (int u = 0; u < SM_UNROLL; ++u) {
+            bool valid = ok[u];
+            if (valid && ((uint64_t)off[u] > text_bytes || (uint64_t)nlen[u] > text_bytes - off[u])) { flags |= (uint32_t)UTK_SAMPLES_F_NAME; valid = false; }
+            const uint8_t *id = text + (valid ? off[u] : 0u);
+            const uint32_t idl = valid ? sm_id_len(id, nlen[u], t.delim) : 0u;
+            // the predecessor in record order is the lane below
+            const uint32_t p_off = (uint32_t)__shfl_up((int)off[u], 1), p_idl = (uint32_t)__shfl_up((int)idl, 1);
+            const int p_valid = __shfl_up((int)valid, 1);
+            bool head = valid;
+            if (valid && lane > 0 && p_valid && p_idl == idl && sm_same(id, text + p_off, idl)) head = false;
+            uint32_t slot = SM_NONE;
+            if (head) {
+                if (pv_ok && pv_idl == idl && sm_same(id, text + pv_off, idl)) slot = pv_slot;
+                else slot = sm_intern(t, id, idl);
+            }
+            // every lane takes the slot of the nearest head at or below it (a valid lane 0 is one; lanes beyond the batch's end follow no valid lane)
+            const uint64_t heads = __ballot(head);
+            const uint64_t below = heads & ((2ull << lane) - 1ull);
+            const int src = below ? 63 - __clzll((long long)below) : (int)lane;
+            slot = (uint32_t)__shfl((int)slot, src);
+            if (valid) { pv_off = off[u]; pv_idl = idl; pv_slot = slot; pv_ok = true; }
+            if (valid && slot != SM_NONE) {
+                uint64_t key = SM_KEY_FREE;
+                if (!fnd[u] || cut[u] == -4) key = sm_key(slot, 0, UTK_SAMPLES_CUT_UNCL);
+                else if (cut[u] == -1) key = sm_key(slot, 0, UTK_SAMPLES_CUT_EMPTY);
+                else if (lab[u] >= t.n_labels) flags |= (uint32_t)UTK_SAMPLES_F_LABEL;      // no line can name it (utree_format_records fails on it too)
+                else if (cut[u] > (int32_t)UTK_SAMPLES_CUT_MAX) flags |= (uint32_t)UTK_SAMPLES_F_CUT;
+                else key = sm_key(slot, lab[u], cut[u] >= 0 ? (uint32_t)cut[u] : UTK_SAMPLES_CUT_WHOLE);
+                if (key != SM_KEY_FREE) {
+                    if (key == run) ++run_n;
+                    else { sm_lds_add(s, t, run, run_n); run = key; run_n = 1; }
+                }
+            }
+        }
+    }
+    sm_lds_add(s, t, run, run_n);
+    if (flags) atomicOr(&s.flags, flags);
+    __syncthreads();
+
+    for (uint32_t i = threadIdx.x; i < SM_HSLOTS; i += SM_BLOCK)
+        if (s.key[i] != SM_KEY_FREE && s.cnt[i]) sm_global_add(t, s.key[i], s.cnt[i]);
+    if (threadIdx.x == 0) {
+        if (blockIdx.x == 0) sm_add(t.misc + 0, n);
+        if (s.flags) sm_flag(t, s.flags);
+    }
+}
+
+extern "C" int utk_samples_add(const utk_samples_tab *t, const uint8_t *d_text, uint64_t text_bytes, const uint32_t *d_name_off,
+                               const uint32_t *d_name_len, const utree_result *d_res, uint32_t n, int n_cu, void *stream) {
+    if (!n) return 0;
+    // one workgroup per CU (the LDS table takes 96 KiB of its 160), each over a contiguous run of records; small batches take fewer
+    uint32_t blocks = (uint32_t)(n_cu > 0 ? n_cu : 256);
+    const uint32_t min_per = 4u * SM_UNROLL * SM_BLOCK;
+    if ((n + min_per - 1) / min_per < blocks) blocks = (n + min_per - 1) / min_per;
+    const uint32_t per = (uint32_t)(((uint64_t)n + blocks - 1) / blocks);
+    hipLaunchKernelGGL(samples_add_k, dim3(blocks), dim3(SM_BLOCK), 0, (hipStream_t)stream, *t, d_text, text_bytes, d_name_off, d_name_len, d_res, n,
+                       per);
+    return (int)hipGetLastError();
+}

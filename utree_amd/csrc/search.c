@@ -79,10 +79,13 @@ typedef struct {
     size_t *hm_first, *hm_count; uint64_t *hm_base;
     char *hm_buf[FMT_MAX_THREADS];             /* the map's lines, pieces as fmt_buf's                      */
     size_t hm_cap[FMT_MAX_THREADS], hm_len[FMT_MAX_THREADS];
+    /* a report that reads the names only: the names' offsets relative to their shard's uploaded span, and their lengths behind them */
+    uint32_t *h_names;                         /* pinned, 2 * MAX_READS_PER_BATCH                           */
 } slot_t;
 
-static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev, int hitmap) {
+static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev, int hitmap, int names) {
     if (s->h_buf) return UTREE_OK;
+    if (names && hipHostMalloc((void **)&s->h_names, 2 * MAX_READS_PER_BATCH * 4, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
     if (hitmap) {
         if (hipHostMalloc((void **)&s->h_hm_meta, (size_t)n_dev * sizeof(utree_hitmap_meta), hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
         if (hipHostMalloc((void **)&s->h_run_off, (MAX_READS_PER_BATCH + (size_t)n_dev) * 8, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
@@ -118,6 +121,7 @@ typedef struct {
     uint64_t want_total;                        /* joined bytes of the shard in flight, as the host counted them */
     /* hit map: the shard's run offsets, runs (the worst case: one per window) and meta, and the call's workspace */
     uint64_t *d_run_off; utree_hit_run *d_runs; uint64_t runs_cap; utree_hitmap_meta *d_hm_meta; void *d_hm_ws; size_t hm_ws_bytes;
+    uint32_t *d_name_off, *d_name_len;          /* a report that reads the names only: relative to d_buf      */
 } gpu_ctx;
 
 /* one input file: plain (a team of pread) or, with an opt-in format, through zlib (plain and gzip alike) */
@@ -129,6 +133,7 @@ typedef struct {
     gpu_ctx *G; int n_dev;
     input_t in[2];                              /* input; [1]: the mates file of a paired search             */
     int fo;                                     /* output                                                   */
+    int names;                                  /* a report reads the names (utree_reports_wants_names): they go up with the shard */
     int hm, fh;                                 /* a hit map is made; its file (-1 once writing it has failed: the search goes on) */
     const char *hm_path;
     char *hm_msg;                               /* why the map could not be written ("" = it could): the writer's to set            */
@@ -235,7 +240,7 @@ static void *reader_main(void *arg) {
         slot_t *s = &P->slot[i % NSLOTS];
         if (!wait_state(P, s, S_EMPTY)) return NULL;
         if (i < NSLOTS) {                       /* pinned memory is slow to allocate: do it while earlier chunks are in flight */
-            int arc = slot_alloc(s, P->chunk, PAIRS_NONE, P->n_dev, P->hm);
+            int arc = slot_alloc(s, P->chunk, PAIRS_NONE, P->n_dev, P->hm, P->names);
             if (arc) { set_error(P, arc); return NULL; }
         }
         if (carry) memmove(s->h_buf, carry_src, carry);
@@ -347,7 +352,7 @@ static void *reader_pairs_main(void *arg) {
         mate_t *m = &s->m2;
         if (!wait_state(P, s, S_EMPTY)) return NULL;
         if (i < NSLOTS) {
-            int arc = slot_alloc(s, P->chunk, P->paired, P->n_dev, P->hm);
+            int arc = slot_alloc(s, P->chunk, P->paired, P->n_dev, P->hm, P->names);
             if (arc) { set_error(P, arc); return NULL; }
         }
         uint8_t *buf[2] = {s->h_buf, m->h_buf};
@@ -451,6 +456,21 @@ static int hitmap_fetch(pipe_t *P, slot_t *s) {
     return UTREE_OK;
 }
 
+/* the names of device g's shard [first, first + count) for the reports that read them: offsets relative to the uploaded span, which begins
+ * at h_buf + lo and holds `span` bytes, on the shard's stream */
+static int names_upload(pipe_t *P, slot_t *s, size_t g, size_t first, size_t count, size_t lo, size_t span) {
+    gpu_ctx *c = &P->G[g];
+    if (span >= ((uint64_t)1 << 32)) return UTREE_E_ARG;
+    uint32_t *rel = s->h_names + first, *len = s->h_names + MAX_READS_PER_BATCH + first;
+    for (size_t r = 0; r < count; ++r) {
+        if (s->name_off[first + r] < lo || s->name_off[first + r] - lo + s->name_len[first + r] > span) return UTREE_E_ARG;   /* (cannot happen: a name precedes its read) */
+        rel[r] = (uint32_t)(s->name_off[first + r] - lo); len[r] = s->name_len[first + r];
+    }
+    if (hipMemcpyAsync(c->d_name_off, rel, count * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) return UTREE_E_HIP;
+    if (hipMemcpyAsync(c->d_name_len, len, count * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) return UTREE_E_HIP;
+    return UTREE_OK;
+}
+
 static void *gpu_main(void *arg) {
     pipe_t *P = (pipe_t *)arg;
     for (int i = 0;; ++i) {
@@ -474,6 +494,7 @@ static void *gpu_main(void *arg) {
                 mate_t *m = &s->m2;
                 size_t lo1 = (size_t)s->seq_off[first], hi1 = (size_t)s->seq_off[last] + s->seq_len[last];
                 size_t lo2 = (size_t)m->seq_off[first], hi2 = (size_t)m->seq_off[last] + m->seq_len[last];
+                if (P->names && (size_t)s->name_off[first] < lo1) lo1 = (size_t)s->name_off[first];   /* the span from mate 1's first name on: the names are read there */
                 if (!two) { hi1 = hi2; lo2 = lo1; }                                        /* interleaved: one span holds both */
                 uint64_t total = 0; uint32_t mx = 0;
                 for (size_t r = first; r <= last; ++r) {
@@ -499,13 +520,16 @@ static void *gpu_main(void *arg) {
                 e = utree_reports_classify(P->rep, (int)g, c->dev, c->d_joined, c->d_joff, c->d_jlen, (uint32_t)count, total, mx, P->do_rc, c->d_out,
                                            c->d_ws, c->ws_bytes, c->stream);
                 if (e) { set_error(P, e); return NULL; }
-                e = utree_reports_add(P->rep, (int)g, c->d_joined, c->d_joff, c->d_jlen, c->d_out, (uint32_t)count, P->do_rc, 0, c->stream);
+                if (P->names && (e = names_upload(P, s, g, first, count, lo1, hi1 - lo1))) { set_error(P, e); return NULL; }
+                e = utree_reports_add(P->rep, (int)g, c->d_joined, c->d_joff, c->d_jlen, c->d_out, (uint32_t)count, P->do_rc, 0, c->d_buf, hi1 - lo1,
+                                      c->d_name_off, c->d_name_len, c->stream);
                 if (e) { set_error(P, e); return NULL; }
                 if (P->hm && (e = hitmap_launch(P, s, g, c->d_joined, c->d_joff, c->d_jlen, first, count, total))) { set_error(P, e); return NULL; }
                 HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
                 continue;
             }
             size_t lo = (size_t)s->seq_off[first], hi = (size_t)s->seq_off[last] + s->seq_len[last];
+            if (P->names && (size_t)s->name_off[first] < lo) lo = (size_t)s->name_off[first];      /* the span from the first name on: the names are read there */
             uint64_t total = 0; uint32_t mx = 0;
             for (size_t r = first; r <= last; ++r) {
                 s->rel_off[r] = s->seq_off[r] - lo; total += s->seq_len[r];
@@ -520,7 +544,9 @@ static void *gpu_main(void *arg) {
                             : utree_reports_classify(P->rep, (int)g, c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
                                                      c->d_out, c->d_ws, c->ws_bytes, c->stream);
             if (e) { set_error(P, e); return NULL; }
-            e = utree_reports_add(P->rep, (int)g, c->d_buf, c->d_off, c->d_len, c->d_out, (uint32_t)count, P->do_rc, P->rank != NULL, c->stream);
+            if (P->names && (e = names_upload(P, s, g, first, count, lo, hi - lo))) { set_error(P, e); return NULL; }
+            e = utree_reports_add(P->rep, (int)g, c->d_buf, c->d_off, c->d_len, c->d_out, (uint32_t)count, P->do_rc, P->rank != NULL, c->d_buf, hi - lo,
+                                  c->d_name_off, c->d_name_len, c->stream);
             if (e) { set_error(P, e); return NULL; }
             if (P->hm && (e = hitmap_launch(P, s, g, c->d_buf, c->d_off, c->d_len, first, count, total))) { set_error(P, e); return NULL; }
             HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
@@ -672,6 +698,8 @@ static void free_ctx(gpu_ctx *g) {
     if (g->d_runs) hipFree(g->d_runs);
     if (g->d_hm_meta) hipFree(g->d_hm_meta);
     if (g->d_hm_ws) hipFree(g->d_hm_ws);
+    if (g->d_name_off) hipFree(g->d_name_off);
+    if (g->d_name_len) hipFree(g->d_name_len);
     if (g->stream) hipStreamDestroy(g->stream);
 }
 
@@ -726,6 +754,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     P->ctr = ctr; P->rep = rep; P->n_dev = n_dev; P->do_rc = do_rc; P->rank = rank; P->input_format = input_format;
     P->progress_printed = dev_printed;
     P->paired = paired; P->chunk = paired || hitmap_path ? pairs_chunk_bytes() : CHUNK_BYTES;
+    P->names = utree_reports_wants_names(rep);
     P->hm = hitmap_path != NULL; P->fh = -1; P->hm_path = hitmap_path; P->hm_msg = hm_msg;
     P->path[0] = fasta_path; P->path[1] = mates_path;
     P->in[1].fd = -1;
@@ -813,6 +842,10 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
             HIPM(hipMalloc((void **)&c->d_hm_meta, sizeof(utree_hitmap_meta)));
             HIPM(hipMalloc(&c->d_hm_ws, c->hm_ws_bytes));
         }
+        if (P->names) {
+            HIPM(hipMalloc((void **)&c->d_name_off, MAX_READS_PER_BATCH * 4));
+            HIPM(hipMalloc((void **)&c->d_name_len, MAX_READS_PER_BATCH * 4));
+        }
         c->ws_bytes = rank ? utree_rank_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, CHUNK_BYTES, LINELEN_MAX, do_rc, rank)
                            : utree_classify_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, paired ? c->joined_cap : CHUNK_BYTES, LINELEN_MAX, do_rc);
         if (!c->ws_bytes) { rc = UTREE_E_ARG; goto done; }
@@ -856,6 +889,7 @@ done:
         if (s->h_hm_meta) hipHostFree(s->h_hm_meta);
         if (s->h_run_off) hipHostFree(s->h_run_off);
         if (s->h_runs) hipHostFree(s->h_runs);
+        if (s->h_names) hipHostFree(s->h_names);
         free(s->hm_first); free(s->hm_count); free(s->hm_base);
         for (int t = 0; t < FMT_MAX_THREADS; ++t) free(s->hm_buf[t]);
         free(s->m2.seq_off); free(s->m2.name_off); free(s->m2.name_len);
@@ -883,13 +917,13 @@ done:
 static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int paired,
                           const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format,
                           const char *profile_path, const char *coverage_path, const char *redist_path, uint32_t redist_passes,
-                          const char *hitmap_path, utree_search_stats *stats) {
+                          const char *hitmap_path, const char *samples_path, int delim, utree_search_stats *stats) {
     utree_reports *rep = NULL;
     utree_search_stats st;
     char hm_msg[512] = "";                                         /* why the hit map was not written, when it was not */
     memset(&st, 0, sizeof st);
     if (rank && (redist_path || hitmap_path)) return UTREE_E_ARG;  /* (another vote: no candidate sets; a hit-dependent subset of windows: no map) */
-    int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, redist_path, redist_passes, &rep);
+    int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, redist_path, redist_passes, samples_path, delim, &rep);
     if (!rc && !rep && !hitmap_path)
         return search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, NULL, NULL, NULL, stats);   /* no report asked for */
     if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, rep, hitmap_path, hm_msg, &st);
@@ -902,20 +936,20 @@ static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, con
 
 int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
                       int do_rc, int host_threads, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, NULL, 0, NULL, stats);
+    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, NULL, 0, NULL, NULL, 0, stats);
 }
 int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
                            int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, NULL, 0, NULL, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, NULL, 0, NULL, NULL, 0, stats);
 }
 int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                               int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, NULL, 0, NULL, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, NULL, 0, NULL, NULL, 0, stats);
 }
 int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                                int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                                utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, NULL, 0, stats);
 }
 
 /* pairs: both mates of a pair cast one vote (include/utree_amd.h) */
@@ -923,7 +957,7 @@ int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, c
                             int do_rc, int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                             utree_search_stats *stats) {
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : PAIRS_INTERLEAVED, out_path, do_rc, NULL,
-                          host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, stats);
+                          host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, NULL, 0, stats);
 }
 
 int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
@@ -932,7 +966,7 @@ int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n
                                    utree_search_stats *stats) {
     if (mates_path && interleaved) return UTREE_E_ARG;
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, NULL, stats);
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, NULL, NULL, 0, stats);
 }
 
 int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int interleaved,
@@ -941,7 +975,19 @@ int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, 
                              utree_search_stats *stats) {
     if (mates_path && interleaved) return UTREE_E_ARG;
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, stats);
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, NULL, 0, stats);
+}
+
+/* a sample table of multiplexed reads next to everything else (include/utree_amd.h) */
+int utree_search_file_samples(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int interleaved,
+                              const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
+                              const char *coverage_path, const char *redistribute_path, uint32_t max_passes, const char *hitmap_path,
+                              const char *samples_path, int delim, utree_search_stats *stats) {
+    if (mates_path && interleaved) return UTREE_E_ARG;
+    if (samples_path && (delim < 0 || delim > 255 || delim == '\t' || delim == ' ' || delim == '\r' || delim == '\n')) return UTREE_E_ARG;
+    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, samples_path,
+                          delim, stats);
 }
 
 int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_off1, const uint32_t *d_len1, const uint8_t *d_bases2,
@@ -969,8 +1015,15 @@ int utree_rank_search_file_opts(const utree_ctr *ctr, utree_dev *dev, const char
 int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
                                    const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
                                    utree_search_stats *stats) {
+    return utree_rank_search_file_samples(ctr, dev, reads_path, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, 0, stats);
+}
+int utree_rank_search_file_samples(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
+                                   const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
+                                   const char *samples_path, int delim, utree_search_stats *stats) {
     if (!dev || !params) return UTREE_E_ARG;
+    if (samples_path && (delim < 0 || delim > 255 || delim == '\t' || delim == ' ' || delim == '\r' || delim == '\n')) return UTREE_E_ARG;
     int rc = utree_rank_reset(dev);
     if (rc) return rc;
-    return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, NULL, 0, NULL, stats);
+    return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, NULL, 0, NULL,
+                          samples_path, delim, stats);
 }

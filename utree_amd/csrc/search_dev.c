@@ -396,8 +396,8 @@ static void *lane_main(void *arg) {
         pthread_cond_broadcast(&P->cv);
         pthread_mutex_unlock(&P->mu);
         /* the chunk is committed (published chunks are never dropped): its records and reads go into the search's reports, on this lane's stream
-         * behind the vote -- d_in, d_seq_off and d_seq_len still hold the chunk */
-        if (nr) { int pe = utree_reports_add(P->rep, L->g, b->d_in, b->d_seq_off, b->d_seq_len, b->d_res, nr, P->do_rc, 0, b->stream); if (pe) { dfail(P, pe); return NULL; } }
+         * behind the vote -- d_in, d_seq_off and d_seq_len still hold the chunk, and d_name_off / d_name_len the names the lines print */
+        if (nr) { int pe = utree_reports_add(P->rep, L->g, b->d_in, b->d_seq_off, b->d_seq_len, b->d_res, nr, P->do_rc, 0, b->d_in, n, b->d_name_off, b->d_name_len, b->stream); if (pe) { dfail(P, pe); return NULL; } }
         double t4 = now_s();
         L->t_wait += t4 - t3;
         LH(hipStreamSynchronize(b->stream));

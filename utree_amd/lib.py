@@ -104,6 +104,17 @@ class HitmapMeta(C.Structure):
     _fields_ = [("total_runs", C.c_uint64), ("total_windows", C.c_uint64), ("error", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class SamplesCell(C.Structure):
+    """utree_samples_cell: reads of sample `sample` whose line prints (label, cut), keyed as ProfileEntry."""
+    _fields_ = [("sample", C.c_uint32), ("label", C.c_uint32), ("cut", C.c_int32), ("pad", C.c_uint32), ("reads", C.c_uint64)]
+
+
+class SamplesTable(C.Structure):
+    """utree_samples_table: one handle's read-back as utree_samples_write takes it."""
+    _fields_ = [("ids", C.c_void_p), ("id_off", C.c_void_p), ("reads", C.c_void_p), ("unclassified", C.c_void_p), ("n_samples", C.c_size_t),
+                ("cells", C.c_void_p), ("n_cells", C.c_size_t), ("n_reads", C.c_uint64)]
+
+
 class Result(C.Structure):
     _fields_ = [("label", C.c_uint32), ("cut", C.c_int32), ("found", C.c_uint32), ("uix", C.c_uint32),
                 ("sl", C.c_uint32), ("ol", C.c_uint32)]
@@ -217,6 +228,18 @@ SYMBOLS = {
                                            C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p, C.POINTER(SearchStats)]),
     "utree_rank_search_file_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RankParams),
                                                  C.c_int, C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
+    "utree_samples_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "utree_samples_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "utree_samples_reset": (C.c_int, [C.c_void_p]),
+    "utree_samples_free": (None, [C.c_void_p]),
+    "utree_samples_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "utree_samples_write": (C.c_int, [C.c_void_p, C.POINTER(SamplesTable), C.c_size_t, C.c_char_p]),
+    "utree_search_file_samples": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
+                                            C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int,
+                                            C.POINTER(SearchStats)]),
+    "utree_rank_search_file_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RankParams),
+                                                 C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(SearchStats)]),
 }
 
 

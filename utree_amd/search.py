@@ -9,6 +9,7 @@
     tree.join_pairs(...)             the device join in front of classify(): mate 1 + 'N' + mate 2 per pair
     tree.profile(capacity)           per-taxon read counts of classified batches (no counterpart in the reference)
     tree.coverage()                  per-taxon database k-mers, distinct ones hit, hits (no counterpart in the reference)
+    tree.samples()                   per-sample taxon table of multiplexed reads, ids interned on the device (no counterpart in the reference)
     tree.redistribution()            candidate sets of ambiguous reads, redistributed among their tied labels (as xtree does)
 
 torch is used only for device memory and streams (plumbing); every computation happens in the HIP kernels
@@ -30,6 +31,7 @@ PROFILE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("cut", "<i4"), ("reads", "<u8
 COVERAGE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("pad", "<u4"), ("db_kmers", "<u8"), ("covered", "<u8"), ("hits", "<u8")])
 REDIST_SET_DTYPE = np.dtype([("reads", "<u8"), ("first", "<u8"), ("n", "<u4"), ("pad", "<u4")])
 REDIST_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("pad", "<u4"), ("assigned", "<u8"), ("unique", "<u8")])
+SAMPLES_CELL_DTYPE = np.dtype([("sample", "<u4"), ("label", "<u4"), ("cut", "<i4"), ("pad", "<u4"), ("reads", "<u8")])
 
 
 class CtrDB:
@@ -406,6 +408,10 @@ class DeviceTree:
         """A redistribution handle on this device (utree_redist_create); `capacity` = slots for distinct multi-label candidate sets."""
         return Redistribution(self, capacity)
 
+    def samples(self, sample_capacity: int = 1 << 16, cell_capacity: int = 1 << 22, delim: bytes = b"_") -> "Samples":
+        """A sample table on this device (utree_samples_create): at most sample_capacity distinct ids, cell_capacity (sample, taxon) slots."""
+        return Samples(self, sample_capacity, cell_capacity, delim)
+
     def close(self):
         if self._h:
             _lib.load().utree_dev_free(self._h)
@@ -478,6 +484,100 @@ def write_profile(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
     e = np.ascontiguousarray(entries, dtype=PROFILE_ENTRY_DTYPE)
     _lib.check(_lib.load().utree_profile_write(db._h, e.ctypes.data if len(e) else None, len(e), n_reads, path.encode()),
                "utree_profile_write")
+
+
+class SamplesReadback:
+    """One handle's read-back (utree_samples_read): ids a list of bytes, reads / unclassified uint64 arrays per sample, cells a
+    SAMPLES_CELL_DTYPE array, n_reads the records added.  Samples are numbered in the order the device first claimed their ids."""
+
+    def __init__(self, ids, reads, unclassified, cells, n_reads):
+        self.ids = list(ids)
+        self.reads = np.ascontiguousarray(reads, dtype=np.uint64)
+        self.unclassified = np.ascontiguousarray(unclassified, dtype=np.uint64)
+        self.cells = np.ascontiguousarray(cells, dtype=SAMPLES_CELL_DTYPE)
+        self.n_reads = int(n_reads)
+
+
+class Samples:
+    """Per-sample taxon table on one device (utree_samples_*): add() batches of records with their names, read() brings the ids, the
+    per-sample counts and the (sample, label, cut) cells back, write() writes the table file."""
+
+    def __init__(self, tree: DeviceTree, sample_capacity: int = 1 << 16, cell_capacity: int = 1 << 22, delim: bytes = b"_"):
+        if not (isinstance(delim, (bytes, bytearray)) and len(delim) == 1):
+            raise ValueError("Samples: delim must be one byte")
+        self.tree = tree
+        h = C.c_void_p()
+        _lib.check(_lib.load().utree_samples_create(tree._h, sample_capacity, cell_capacity, delim[0], C.byref(h)), "utree_samples_create")
+        self._h = h
+
+    def add(self, text, name_off, name_len, results, n: Optional[int] = None):
+        """text: uint8 CUDA tensor; name_off / name_len: int32 CUDA tensors of offsets into text (taken as unsigned) and lengths; results:
+        the int32 [n, 6] tensor of classify() / rank_search().  Asynchronous on torch's current stream."""
+        import torch
+        dev = self.tree.info.device
+        ok = lambda t, dt: isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.is_cuda and t.device.index == dev
+        if not (ok(text, torch.uint8) and ok(name_off, torch.int32) and ok(name_len, torch.int32) and ok(results, torch.int32)
+                and results.dim() == 2 and results.shape[1] == 6):
+            raise ValueError("Samples.add: text uint8, name_off / name_len int32, results int32 [n, 6], all contiguous on cuda:%d" % dev)
+        n = results.shape[0] if n is None else n
+        if not (0 <= n <= results.shape[0] and n <= name_off.numel() and n <= name_len.numel()):
+            raise ValueError("Samples.add: n = %d outside the records or names given" % n)
+        stream = torch.cuda.current_stream(results.device).cuda_stream
+        _lib.check(_lib.load().utree_samples_add(self._h, text.data_ptr(), text.numel(), name_off.data_ptr(), name_len.data_ptr(),
+                                                 results.data_ptr(), n, stream), "utree_samples_add")
+
+    def reset(self):
+        _lib.check(_lib.load().utree_samples_reset(self._h), "utree_samples_reset")
+
+    def read(self) -> SamplesReadback:
+        """Raises UtreeError(E_DEVICE) when a table was too small or a record or name was refused: there is no table then."""
+        L = _lib.load()
+        ns, nb, nc, nr = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+        code = L.utree_samples_read(self._h, None, 0, None, None, None, 0, None, 0, C.byref(ns), C.byref(nb), C.byref(nc), C.byref(nr))
+        if code not in (_lib.OK, _lib.E_ARG):
+            _lib.check(code, "utree_samples_read")
+        S = ns.value
+        ids = np.zeros(max(nb.value, 1), dtype=np.uint8)
+        off = np.zeros(S + 1, dtype=np.uint64)
+        reads = np.zeros(max(S, 1), dtype=np.uint64)
+        uncl = np.zeros(max(S, 1), dtype=np.uint64)
+        cells = np.zeros(max(nc.value, 1), dtype=SAMPLES_CELL_DTYPE)
+        _lib.check(L.utree_samples_read(self._h, ids.ctypes.data, nb.value, off.ctypes.data, reads.ctypes.data, uncl.ctypes.data, S,
+                                        cells.ctypes.data, nc.value, C.byref(ns), C.byref(nb), C.byref(nc), C.byref(nr)), "utree_samples_read")
+        raw = ids.tobytes()
+        return SamplesReadback([raw[int(off[i]):int(off[i + 1])] for i in range(S)], reads[:S], uncl[:S], cells[:nc.value].copy(), nr.value)
+
+    def write(self, path: str):
+        write_samples(self.tree.db, [self.read()], path)
+
+    def close(self):
+        if self._h:
+            _lib.load().utree_samples_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_samples(db: CtrDB, readbacks: Sequence[SamplesReadback], path: str):
+    """utree_samples_write: the read-backs of any number of handles, samples merged by id text and taxa by printed text, written."""
+    tabs = (_lib.SamplesTable * max(len(readbacks), 1))()
+    keep = []
+    for t, rb in zip(tabs, readbacks):
+        ids = np.frombuffer(b"".join(rb.ids) + b"\0", dtype=np.uint8).copy()
+        off = np.zeros(len(rb.ids) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(i) for i in rb.ids], dtype=np.uint64) if rb.ids else []
+        keep.append((ids, off, rb.reads, rb.unclassified, rb.cells))
+        t.ids = ids.ctypes.data; t.id_off = off.ctypes.data
+        t.reads = rb.reads.ctypes.data if len(rb.ids) else None
+        t.unclassified = rb.unclassified.ctypes.data if len(rb.ids) else None
+        t.n_samples = len(rb.ids)
+        t.cells = rb.cells.ctypes.data if len(rb.cells) else None
+        t.n_cells = len(rb.cells); t.n_reads = rb.n_reads
+    _lib.check(_lib.load().utree_samples_write(db._h, tabs, len(readbacks), path.encode()), "utree_samples_write")
 
 
 class Coverage:
@@ -650,7 +750,7 @@ def write_coverage(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
 def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: bool = False, threads: int = 0,
               input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None,
               mates: Optional[str] = None, interleaved: bool = False, redistribute: Optional[str] = None, redist_passes: int = 100,
-              hitmap: Optional[str] = None):
+              hitmap: Optional[str] = None, samples: Optional[str] = None, sample_delim: bytes = b"_"):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
     FASTA / gzip input.  profile: also write the per-taxon read counts there; coverage: also write the per-taxon k-mer
@@ -661,11 +761,21 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
     redistribute: also write the reads redistributed among the labels each hit most often there (utree_search_file_redistribute), at most
     redist_passes passes; a redistribution that cannot be written returns E_PROFILE.
     hitmap: also write every query's k-mer hit map there, and the label texts to hitmap + ".labels" (utree_search_file_hitmap); a map that
-    cannot be written returns E_HITMAP."""
+    cannot be written returns E_HITMAP.
+    samples: the reads are a combined file named <sample><sample_delim><n>; also write the taxon x sample table there
+    (utree_search_file_samples); a table that cannot be written returns E_PROFILE."""
     if mates is not None and interleaved:
         raise ValueError("search_gg: give mates= or interleaved=True, not both")
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     st = _lib.SearchStats()
+    if samples is not None:
+        if not (isinstance(sample_delim, (bytes, bytearray)) and len(sample_delim) == 1):
+            raise ValueError("search_gg: sample_delim must be one byte")
+        enc = lambda p: p.encode() if p is not None else None
+        code = _lib.load().utree_search_file_samples(db._h, arr, len(trees), fasta.encode(), enc(mates), int(interleaved), out.encode(), int(rc),
+                                                     threads, input_format, enc(profile), enc(coverage), enc(redistribute), redist_passes,
+                                                     enc(hitmap), samples.encode(), sample_delim[0], C.byref(st))
+        return code, st
     if hitmap is not None:
         enc = lambda p: p.encode() if p is not None else None
         code = _lib.load().utree_search_file_hitmap(db._h, arr, len(trees), fasta.encode(), enc(mates), int(interleaved), out.encode(), int(rc),
@@ -692,11 +802,19 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
 
 
 def search_rank(db: CtrDB, tree: DeviceTree, fasta: str, out: str, rc: bool = False, slack: int = 2, sparsity: int = 4,
-                tolerance: int = 2, threads: int = 0, input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None):
-    """XT_doSearch32(utree, in, out, 0, speed, doRC): the `xtree-search` binary (itree.c:1376 without DO_GG).  profile: as
-    search_gg's."""
+                tolerance: int = 2, threads: int = 0, input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None,
+                samples: Optional[str] = None, sample_delim: bytes = b"_"):
+    """XT_doSearch32(utree, in, out, 0, speed, doRC): the `xtree-search` binary (itree.c:1376 without DO_GG).  profile, samples,
+    sample_delim: as search_gg's."""
     st = _lib.SearchStats()
     prm = _lib.RankParams(slack, sparsity, tolerance)
+    if samples is not None:
+        if not (isinstance(sample_delim, (bytes, bytearray)) and len(sample_delim) == 1):
+            raise ValueError("search_rank: sample_delim must be one byte")
+        code = _lib.load().utree_rank_search_file_samples(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm), threads, input_format,
+                                                          profile.encode() if profile is not None else None, samples.encode(), sample_delim[0],
+                                                          C.byref(st))
+        return code, st
     code = _lib.load().utree_rank_search_file_profile(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm), threads,
                                                       input_format, profile.encode() if profile is not None else None, C.byref(st))
     return code, st
