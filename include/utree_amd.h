@@ -656,6 +656,98 @@ int utree_rank_search_file_samples(const utree_ctr *ctr, utree_dev *dev, const c
                                    const char *samples_path, int delim, utree_search_stats *stats);
 
 /* ------------------------------------------------------------------------------------------------
+ * Ambiguous reads redistributed PER SAMPLE of a multiplexed file (UTREE_SAMPLE_REDISTRIBUTE; GG search only).  The two reports above do
+ * not compose: the sample table's cells are the vote's `assigned`, and the redistribution takes the whole file for one community, so a taxon
+ * that is rich in sample A pulls sample B's ambiguous reads towards it.  This report is the taxon x sample matrix with every sample's
+ * ambiguous reads redistributed within that sample.
+ *   Sample id.  As the sample table defines it: the printed name before its LAST delimiter byte (default '_'); a name without the delimiter
+ *     is its own id, an id may be empty, a pair takes mate 1's name.  Ids are compared as bytes, never by hash alone.
+ *   Candidate sets.  As utree_redist_* defines them: { l : c[l] == max c } over file-order label indices, none for a read without a hit, no cap.
+ *   Per sample s.  R_s = the sample's reads (a pair counts once), N_s = |R_s|.  The redistribution's definition applies with R_s in the place
+ *     of "the reads searched": T0_s[l] = reads of R_s whose set contains l; win takes the largest T_s, on equal tallies the smallest
+ *     file-order index; pass p runs while p <= max_passes and, after the first, while the previous changes_s > N_s / 100000 (integer
+ *     division).  At least one pass runs; a sample that has stopped stays stopped while the others go on, P_s is its own pass count.
+ *     assigned_s[l] is one more evaluation under T_{P_s}; unique_s[l] = reads whose set is exactly {l}; ambiguous_s = reads with more than one
+ *     candidate.  max_passes (1 .. 1000, default UTREE_REDIST_DEFAULT_PASSES) is the same for every sample.
+ *   File.  Fields are separated by one TAB, every line ends in '\n', samples and taxa in unsigned bytewise order (shorter first), ids escaped
+ *     as the sample table escapes them:
+ *     # reads\t<N>\tclassified\t<G>\tunclassified\t<N-G>\tambiguous\t<A>\tsamples\t<S>
+ *     # taxon\t<id_1>\t...\t<id_S>
+ *     # reads\t<n_1>...
+ *     # unclassified\t<u_1>...
+ *     # ambiguous\t<a_1>...
+ *     # passes\t<P_1>...
+ *     <taxon>\t<assigned_1>\t...\t<assigned_S>     one line per label text with assigned > 0 in some sample
+ *     Labels of equal text are merged at write time; there are no ';'-prefix rows; with S = 0 the '#' lines after the first end after their
+ *     first field.
+ *   A reader can check: column j sums to n_j - u_j; the `# reads` and `# unclassified` rows are the sample table's rows for the same run; for
+ *     a file that holds one sample the column is the `assigned` column (rows with assigned > 0) of the redistribution's file for the same run
+ *     and `# passes` that file's `passes`.
+ * What this is not: no per-read reassignment, no normalisation, no rank-specific search.
+ *
+ * A handle lives on ONE device for one database: an id table and arena as the sample table has them, a table of multi-label sets with its
+ * arena as the redistribution has it, and an open-addressed table of {key, reads} cells, 16 B a slot; a cell is (sample, candidate set)
+ * (DESIGN.md section 7).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct utree_sredist utree_sredist;
+/* sample_capacity: the most distinct ids (1 .. 2^19); set_capacity: slots for distinct multi-label sets (rounded up to a power of two, at most
+ * 2^28); cell_capacity: slots of the cell table (rounded up to a power of two, at most 2^30) -- keep both at twice what a search can produce.
+ * delim as for utree_samples_create.  UTREE_E_ARG beyond those bounds, UTREE_E_UNSUPPORTED for a database of 2^28 labels or more. */
+int utree_sredist_create(utree_dev *dev, uint32_t sample_capacity, uint32_t set_capacity, uint32_t cell_capacity, int delim, utree_sredist **out);
+/* Forgets everything (synchronous: waits for the device first). */
+int utree_sredist_reset(utree_sredist *h);
+void utree_sredist_free(utree_sredist *h);
+/* utree_classify_batch (same arguments, `dev` = the image h was created for; d_out bit for bit the same) that also counts the batch's reads
+ * per (sample, candidate set): one more kernel between the classify kernels and the vote.  Read r's name is d_text[d_name_off[r] .. +
+ * d_name_len[r]) of d_text's text_bytes bytes, as utree_samples_add takes it.  Any number of streams may add to one handle at the same time. */
+int utree_sredist_classify_batch(utree_sredist *h, utree_dev *dev, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                                 uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, const uint8_t *d_text, uint64_t text_bytes,
+                                 const uint32_t *d_name_off, const uint32_t *d_name_len, utree_result *d_out, void *d_workspace,
+                                 size_t workspace_bytes, void *stream);
+/* `reads` reads of sample `sample` whose candidate set is the file-order label indices labels[first .. first + n), n >= 1 */
+typedef struct { uint32_t sample, n; uint64_t first, reads; } utree_sredist_cell;
+/* The read-back (synchronous).  Samples as utree_samples_read returns them (ids, h_id_off with sample_cap + 1 entries, reads, unclassified; numbered
+ * in the order the device first claimed the ids); the cells with reads > 0 into h_cells, their labels into h_labels, single-label sets included.
+ * *n_samples, *n_id_bytes, *n_cells, *n_labels are always set when the device's state is sound: UTREE_E_ARG when one exceeds its capacity
+ * (nothing else is written then: call with zero capacities to size the arrays).  *n_reads (may be NULL) = records added.  UTREE_E_DEVICE when
+ * a batch found the id table or its arena, the set table or its arena or the cell table full, a record named a label the database lacks, a name
+ * lay outside its text, or the counters do not add up: utree_last_hip_error names the cause and the knob. */
+int utree_sredist_read(utree_sredist *h, uint8_t *h_ids, size_t id_cap, uint64_t *h_id_off, uint64_t *h_reads, uint64_t *h_unclassified,
+                       size_t sample_cap, utree_sredist_cell *h_cells, size_t cell_cap, uint32_t *h_labels, size_t label_cap, size_t *n_samples,
+                       size_t *n_id_bytes, size_t *n_cells, size_t *n_labels, uint64_t *n_reads);
+/* The same flat form given on the host and inserted (synchronous): n_samples ids with their reads and unclassified reads, n_cells cells of
+ * those samples, n_reads records.  A sample's reads must be its unclassified reads plus its cells' for the handle to read back. */
+int utree_sredist_insert(utree_sredist *h, const uint8_t *ids, const uint64_t *id_off, const uint64_t *reads, const uint64_t *unclassified,
+                         size_t n_samples, const utree_sredist_cell *cells, size_t n_cells, const uint32_t *labels, size_t n_labels,
+                         uint64_t n_reads);
+/* dst += src: a read of src followed by an insert into dst (the handles may be on different devices, same database). */
+int utree_sredist_merge(utree_sredist *dst, utree_sredist *src);
+typedef struct { uint32_t sample, label; uint64_t assigned, unique; } utree_sredist_entry;
+/* The passes of every sample, on the device (synchronous; max_passes 1 .. 1000): tallies only for the (sample, label) pairs that occur, the
+ * host reads one word per still-active sample per pass.  One entry per (sample, label) with a non-zero figure, by sample (utree_sredist_read's
+ * numbering), then label; *n = their number (UTREE_E_ARG if that exceeds cap; the read-back's *n_labels always suffices).  h_passes[s] = P_s and
+ * h_ambiguous[s] for the *n_samples samples (UTREE_E_ARG if sample_cap is smaller; either array may be NULL).  The handle keeps its state. */
+int utree_sredist_solve(utree_sredist *h, uint32_t max_passes, utree_sredist_entry *e, size_t cap, size_t *n, uint32_t *h_passes,
+                        uint64_t *h_ambiguous, size_t sample_cap, size_t *n_samples);
+/* Host only (runs without a GPU): the samples of a read-back, the figures of a solve (label indices of ctr) -> the file above.  UTREE_E_ARG when
+ * the figures contradict each other (a sample's assigned reads are not its reads minus its unclassified reads, the samples' reads not n_reads,
+ * more ambiguous than classified reads, an entry names no sample or label, two samples with one id, passes outside 1 .. 1000). */
+int utree_sredist_write(const utree_ctr *ctr, const uint8_t *ids, const uint64_t *id_off, const uint64_t *reads, const uint64_t *unclassified,
+                        const uint32_t *passes, const uint64_t *ambiguous, size_t n_samples, const utree_sredist_entry *e, size_t n_entries,
+                        uint64_t n_reads, const char *path);
+/* utree_search_file_samples that also writes this report to `sample_redistribute_path` (NULL: exactly that call -- nothing allocated, uploaded
+ * or launched), ids cut at `delim`, at most max_passes passes per sample (0: the default).  The per-read output, stdout, the stats, the
+ * pipeline and every other report are those of a search without it.  One handle per device handle (UTREE_SAMPLE_CAPACITY ids,
+ * UTREE_REDIST_CAPACITY sets, UTREE_SAMPLE_CELLS cells), merged into the first and solved before the file is written -- after the sample table,
+ * before the profile.  A report that cannot be written returns UTREE_E_PROFILE and utree_last_hip_error names its file and the cause (the
+ * profile's failure wins, then the redistribution's, the sample table's, this report's); a search that fails leaves the path as it was. */
+int utree_search_file_sample_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                                          int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
+                                          const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
+                                          const char *hitmap_path, const char *samples_path, int delim, const char *sample_redistribute_path,
+                                          utree_search_stats *stats);
+
+/* ------------------------------------------------------------------------------------------------
  * `.ubt` -> `.ctr` = XT_cmp32(filename, outfile) (itree.c:1234-1315; `xtree-compress`), SURVEY.md §8(f) rank 2.
  * Node dump streamed through `device`; output byte-identical to the reference's, first-bin quirk included.
  * ---------------------------------------------------------------------------------------------- */

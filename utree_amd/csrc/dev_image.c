@@ -897,6 +897,15 @@ int utree_classify_batch(utree_dev *d, const uint8_t *d_bases, const uint64_t *d
 int utree_classify_batch_redist(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
                                 uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out,
                                 void *d_workspace, size_t workspace_bytes, void *stream, struct utree_redist *rd) {
+    return utree_classify_batch_reports(d, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream, rd,
+                                        NULL, NULL, 0, NULL, NULL);
+}
+
+/* srd: NULL, or the handle the batch's reads are counted in per (sample, candidate set), at the same place and from the same lists (sredist.c) */
+int utree_classify_batch_reports(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                                 uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out,
+                                 void *d_workspace, size_t workspace_bytes, void *stream, struct utree_redist *rd, struct utree_sredist *srd,
+                                 const uint8_t *d_text, uint64_t text_bytes, const uint32_t *d_name_off, const uint32_t *d_name_len) {
     int rc = UTREE_OK;
     if (!d || !d_out || (!d_workspace && n_reads)) return UTREE_E_ARG;
     if (!n_reads) return UTREE_OK;
@@ -977,6 +986,7 @@ int utree_classify_batch_redist(utree_dev *d, const uint8_t *d_bases, const uint
         }
     }
     if (rd && (rc = utree_redist_add_pending(rd, &d->kimg, d_out, &w, n_reads, d->n_cu, st))) goto fail;     /* every path has converged here */
+    if (srd && (rc = utree_sredist_add_pending(srd, &d->kimg, d_out, &w, d_text, text_bytes, d_name_off, d_name_len, n_reads, d->n_cu, st))) goto fail;
     KCHK(utk_vote(&d->kimg, d_out, &w, n_reads, st));
     /* the reads the lane pass left, and the batch's error word, come back behind the kernels without a wait */
     if (ring_post(d, &w, lanes ? n_reads : 0, st)) { (void)hipGetLastError(); }

@@ -45,6 +45,15 @@ int utree_classify_batch_redist(utree_dev *d, const uint8_t *d_bases, const uint
 int utree_redist_add_pending(struct utree_redist *rd, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, uint32_t n_reads,
                              int n_cu, void *stream);
 int utree_redist_reads(struct utree_redist *rd, uint64_t *n_reads);
+/* ... and / or, with the reads' names (as utree_samples_add takes them), counted per (sample, candidate set) in `srd` (NULL: not); sredist.c */
+struct utree_sredist;
+int utree_classify_batch_reports(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads,
+                                 uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace, size_t workspace_bytes,
+                                 void *stream, struct utree_redist *rd, struct utree_sredist *srd, const uint8_t *d_text, uint64_t text_bytes,
+                                 const uint32_t *d_name_off, const uint32_t *d_name_len);
+int utree_sredist_add_pending(struct utree_sredist *h, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, const uint8_t *d_text,
+                              uint64_t text_bytes, const uint32_t *d_name_off, const uint32_t *d_name_len, uint32_t n_reads, int n_cu, void *stream);
+int utree_sredist_reads(struct utree_sredist *h, uint64_t *n_reads);
 
 void utree_dev_set_hip_error(int err, const char *what);
 const char *utree_last_hip_error(void);

@@ -46,6 +46,13 @@
  *                           (default 2^22) size the tables.  May be combined with every other variable.  Path checks as for UTREE_PROFILE.  A
  *                           file named without the convention (every read its own sample) ends after a complete search: the usual stdout, one
  *                           line on stderr that names UTREE_SAMPLE_CAPACITY, exit 1.  Unset: nothing is allocated, uploaded or launched
+ *     UTREE_SAMPLE_REDISTRIBUTE=<path> opt-in, xtree-searchGG only (xtree-search ignores it, as it ignores UTREE_REDISTRIBUTE): also write the taxon x
+ *                           sample matrix with every sample's ambiguous reads redistributed WITHIN that sample (include/utree_amd.h:
+ *                           utree_sredist_write) -- the cells (sample, candidate set) are counted on the GPU while it searches, one more pass
+ *                           per batch, and every sample iterated there after the search.  Sample ids, UTREE_SAMPLE_DELIM, UTREE_SAMPLE_CAPACITY
+ *                           and UTREE_SAMPLE_CELLS as for UTREE_SAMPLE_TABLE, UTREE_REDIST_PASSES and UTREE_REDIST_CAPACITY as for
+ *                           UTREE_REDISTRIBUTE; may be combined with every other variable; path checks and the ending of a file named without
+ *                           the convention as for UTREE_SAMPLE_TABLE.  Unset: nothing is allocated, uploaded or launched
  *     UTREE_MATES=<path>    opt-in, xtree-searchGG only: paired-end reads.  fastaToSearch.fa holds the first mates, <path> the second; pair i is
  *                           record i of both.  A pair is searched as ONE query, mate 1 + "N" + mate 2, and prints one line under mate 1's name
  *                           (include/utree_amd.h: utree_search_pairs_file; mate names are not compared); "Searched N queries" and the profile
@@ -126,8 +133,10 @@ int main(int argc, char *argv[]) {
     if (coverage && *coverage) check_report_path(coverage, "coverage"); else coverage = NULL;
     const char *redist = DO_GG ? getenv("UTREE_REDISTRIBUTE") : NULL;
     if (redist && *redist) check_report_path(redist, "redistribution"); else redist = NULL;
+    const char *sredist = DO_GG ? getenv("UTREE_SAMPLE_REDISTRIBUTE") : NULL;
+    if (sredist && *sredist) check_report_path(sredist, "sample redistribution"); else sredist = NULL;
     unsigned redist_passes = 0;                                                           /* 0: the default */
-    if (redist && getenv("UTREE_REDIST_PASSES")) {
+    if ((redist || sredist) && getenv("UTREE_REDIST_PASSES")) {
         const long v = atol(getenv("UTREE_REDIST_PASSES"));
         if (v < 1 || v > 1000) { fputs("ERROR: UTREE_REDIST_PASSES must be 1 .. 1000\n", stderr); exit(1); }
         redist_passes = (unsigned)v;
@@ -217,7 +226,8 @@ int main(int argc, char *argv[]) {
     if (getenv("UTREE_TOLERANCE")) prm.tolerance = (uint32_t)atoi(getenv("UTREE_TOLERANCE"));
     rc = utree_rank_search_file_samples(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, samples, sample_delim, &st);   /* (a NULL path: no such report) */
 #else
-    if (samples) rc = utree_search_file_samples(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, samples, sample_delim, &st);
+    if (sredist) rc = utree_search_file_sample_redistribute(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, samples, sample_delim, sredist, &st);
+    else if (samples) rc = utree_search_file_samples(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, samples, sample_delim, &st);
     else if (hitmap) rc = utree_search_file_hitmap(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, &st);
     else if (redist) rc = utree_search_file_redistribute(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, &st);
     else if (mates || interleaved) rc = utree_search_pairs_file(ctr, devs, n_dev, argv[2], mates, argv[3], doRC, threads, fmt, profile, coverage, &st);

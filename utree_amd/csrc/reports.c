@@ -1,5 +1,5 @@
 /* reports.c -- the opt-in reports of one whole-file search (reports.h): a profile (profile.c), a coverage handle (coverage.c), a redistribution
- * handle (redist.c) and / or a sample table (samples.c) per device handle, fed chunk by chunk, merged and written when the search has succeeded. */
+ * handle (redist.c), a sample table (samples.c) and / or a per-sample redistribution handle (sredist.c) per device handle, fed chunk by chunk, merged and written when the search has succeeded. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -9,21 +9,22 @@
 
 struct utree_reports {
     int n_dev;
-    const char *profile_path, *coverage_path, *redist_path, *samples_path;
+    const char *profile_path, *coverage_path, *redist_path, *samples_path, *sredist_path;
     uint32_t redist_passes;
-    struct { utree_profile *prof; utree_coverage *cov; utree_redist *rd; utree_samples *smp; } dev[];      /* NULL: the search writes no such report */
+    struct { utree_profile *prof; utree_coverage *cov; utree_redist *rd; utree_samples *smp; utree_sredist *srd; } dev[];      /* NULL: the search writes no such report */
 };
 
 int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *profile_path, const char *coverage_path,
-                         const char *redist_path, uint32_t redist_passes, const char *samples_path, int samples_delim, utree_reports **out) {
+                         const char *redist_path, uint32_t redist_passes, const char *samples_path, int samples_delim, const char *sredist_path,
+                         utree_reports **out) {
     *out = NULL;
-    if (!profile_path && !coverage_path && !redist_path && !samples_path) return UTREE_OK;
-    if (redist_path && redist_passes > 1000) return UTREE_E_ARG;
+    if (!profile_path && !coverage_path && !redist_path && !samples_path && !sredist_path) return UTREE_OK;
+    if ((redist_path || sredist_path) && redist_passes > 1000) return UTREE_E_ARG;
     if (!ctr || !devs || n_dev < 1) return UTREE_E_ARG;
     utree_reports *rep = (utree_reports *)calloc(1, sizeof *rep + (size_t)n_dev * sizeof rep->dev[0]);
     if (!rep) return UTREE_E_NOMEM;
     rep->n_dev = n_dev; rep->profile_path = profile_path; rep->coverage_path = coverage_path; rep->redist_path = redist_path;
-    rep->samples_path = samples_path;
+    rep->samples_path = samples_path; rep->sredist_path = sredist_path;
     rep->redist_passes = redist_passes ? redist_passes : UTREE_REDIST_DEFAULT_PASSES;
     const char *e = getenv("UTREE_PROFILE_CAPACITY");
     const uint32_t cap = e && atoll(e) >= 1 && atoll(e) <= (1ll << 30) ? (uint32_t)atoll(e) : UTREE_PROFILE_DEFAULT_CAPACITY;
@@ -37,6 +38,8 @@ int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, cons
     const uint32_t scap = es && atoll(es) >= 1 && atoll(es) <= (1ll << 19) ? (uint32_t)atoll(es) : UTREE_SAMPLES_DEFAULT_CAPACITY;
     const uint32_t ccap = ec && atoll(ec) >= 1 && atoll(ec) <= (1ll << 30) ? (uint32_t)atoll(ec) : UTREE_SAMPLES_DEFAULT_CELLS;
     for (int g = 0; samples_path && g < n_dev && !rc; ++g) rc = utree_samples_create(devs[g], scap, ccap, samples_delim ? samples_delim : '_', &rep->dev[g].smp);
+    for (int g = 0; sredist_path && g < n_dev && !rc; ++g)
+        rc = utree_sredist_create(devs[g], scap, rcap, ccap, samples_delim ? samples_delim : '_', &rep->dev[g].srd);
     if (rc) { utree_reports_free(rep); return rc; }
     *out = rep;
     return UTREE_OK;
@@ -48,6 +51,7 @@ void utree_reports_free(utree_reports *rep) {
     for (int g = 0; g < rep->n_dev; ++g) utree_coverage_free(rep->dev[g].cov);
     for (int g = 0; g < rep->n_dev; ++g) utree_redist_free(rep->dev[g].rd);
     for (int g = 0; g < rep->n_dev; ++g) utree_samples_free(rep->dev[g].smp);
+    for (int g = 0; g < rep->n_dev; ++g) utree_sredist_free(rep->dev[g].srd);
     free(rep);
 }
 
@@ -57,19 +61,21 @@ int utree_reports_reset(utree_reports *rep) {
     for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].cov) rc = utree_coverage_reset(rep->dev[g].cov);
     for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].rd) rc = utree_redist_reset(rep->dev[g].rd);
     for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].smp) rc = utree_samples_reset(rep->dev[g].smp);
+    for (int g = 0; rep && g < rep->n_dev && !rc; ++g) if (rep->dev[g].srd) rc = utree_sredist_reset(rep->dev[g].srd);
     return rc;
 }
 
 int utree_reports_classify(utree_reports *rep, int g, utree_dev *dev, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
                            uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace,
-                           size_t workspace_bytes, void *stream) {
-    if (rep && rep->dev[g].rd)
-        return utree_redist_classify_batch(rep->dev[g].rd, dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace,
-                                           workspace_bytes, stream);
+                           size_t workspace_bytes, const uint8_t *d_text, uint64_t text_bytes, const uint32_t *d_name_off,
+                           const uint32_t *d_name_len, void *stream) {
+    if (rep && (rep->dev[g].rd || rep->dev[g].srd))       /* (each batch feeds both when both are written) */
+        return utree_classify_batch_reports(dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream,
+                                            rep->dev[g].rd, rep->dev[g].srd, d_text, text_bytes, d_name_off, d_name_len);
     return utree_classify_batch(dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream);
 }
 
-int utree_reports_wants_names(const utree_reports *rep) { return rep && rep->samples_path; }
+int utree_reports_wants_names(const utree_reports *rep) { return rep && (rep->samples_path || rep->sredist_path); }
 
 int utree_reports_add(utree_reports *rep, int g, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
                       const utree_result *d_res, uint32_t n, int do_rc, int rank, const uint8_t *d_text, uint64_t text_bytes,
@@ -202,15 +208,67 @@ static int write_samples(const utree_reports *rep, const utree_ctr *ctr, uint64_
     return rc;
 }
 
+/* merges the devices' handles into the first, checks that n_reads_expected reads were added (else UTREE_E_DEVICE), solves every sample and writes
+ * the file */
+static int write_sredist(const utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads_expected) {
+    const char *path = rep->sredist_path;
+    utree_sredist *h = rep->dev[0].srd;
+    int rc = UTREE_OK;
+    uint64_t reads = 0;
+    size_t ns = 0, nb = 0, nc = 0, nl = 0, k = 0;
+    uint8_t *ids = NULL;
+    uint64_t *w = NULL;
+    uint32_t *passes = NULL;
+    utree_sredist_entry *e = NULL;
+    for (int g = 1; g < rep->n_dev && !rc; ++g) rc = utree_sredist_merge(h, rep->dev[g].srd);
+    if (!rc) rc = utree_sredist_reads(h, &reads);
+    char msg[1100];
+    if (!rc && reads != n_reads_expected) {                        /* every read added exactly once, or no file */
+        snprintf(msg, sizeof msg, "sample redistribution %s: %llu reads added, the search read %llu", path, (unsigned long long)reads,
+                 (unsigned long long)n_reads_expected);
+        utree_set_error_text(msg);
+        return UTREE_E_DEVICE;
+    }
+    if (!rc) {
+        rc = utree_sredist_read(h, NULL, 0, NULL, NULL, NULL, 0, NULL, 0, NULL, 0, &ns, &nb, &nc, &nl, NULL);      /* the sizes */
+        if (rc == UTREE_E_ARG) rc = UTREE_OK;
+    }
+    if (!rc) {
+        ids = (uint8_t *)malloc(nb ? nb : 1);
+        w = (uint64_t *)malloc((4 * ns + 1) * 8);                  /* id_off [ns + 1] | reads | unclassified | ambiguous */
+        passes = (uint32_t *)malloc((ns ? ns : 1) * 4);
+        e = (utree_sredist_entry *)malloc((nl ? nl : 1) * sizeof *e);
+        utree_sredist_cell *cells = (utree_sredist_cell *)malloc((nc ? nc : 1) * sizeof *cells);
+        uint32_t *labels = (uint32_t *)malloc((nl ? nl : 1) * 4);
+        if (!ids || !w || !passes || !e || !cells || !labels) rc = UTREE_E_NOMEM;
+        else rc = utree_sredist_read(h, ids, nb, w, w + ns + 1, w + 2 * ns + 1, ns, cells, nc, labels, nl, &ns, &nb, &nc, &nl, NULL);
+        free(cells); free(labels);
+    }
+    if (rc == UTREE_E_DEVICE) {                                    /* (the read-back's text begins "sample redistribution:") */
+        const char *why = utree_last_hip_error();
+        snprintf(msg, sizeof msg, "sample redistribution %s:%s", path, strncmp(why, "sample redistribution:", 22) ? why : why + 22);
+    }
+    else if (rc) snprintf(msg, sizeof msg, "sample redistribution %s: the tables could not be merged and read back (%s)", path, utree_strerror(rc));
+    else if ((rc = utree_sredist_solve(h, rep->redist_passes, e, nl, &k, passes, w + 3 * ns + 1, ns, NULL)))
+        snprintf(msg, sizeof msg, "sample redistribution %s: the passes failed (%s)", path, utree_strerror(rc));
+    else if ((rc = utree_sredist_write(ctr, ids, w, w + ns + 1, w + 2 * ns + 1, passes, w + 3 * ns + 1, ns, e, k, reads, path)))
+        snprintf(msg, sizeof msg, "sample redistribution %s: cannot write the file (%s)", path, utree_strerror(rc));
+    if (rc) utree_set_error_text(msg);
+    free(ids); free(w); free(passes); free(e);
+    return rc;
+}
+
 int utree_reports_write(utree_reports *rep, const utree_ctr *ctr, uint64_t n_reads) {
     if (!rep) return UTREE_OK;
     const int ce = rep->coverage_path ? write_coverage(rep, ctr, n_reads) : UTREE_OK;
-    char keep[512];
+    char keep[1200];
     const int re = rep->redist_path ? write_redist(rep, ctr, n_reads) : UTREE_OK;
     if (re) snprintf(keep, sizeof keep, "%s", utree_last_hip_error());
     const int se = rep->samples_path ? write_samples(rep, ctr, n_reads) : UTREE_OK;
     if (se && !re) snprintf(keep, sizeof keep, "%s", utree_last_hip_error());          /* (the redistribution's failure wins) */
+    const int sre = rep->sredist_path ? write_sredist(rep, ctr, n_reads) : UTREE_OK;
+    if (sre && !re && !se) snprintf(keep, sizeof keep, "%s", utree_last_hip_error());  /* (... then the sample table's) */
     if (rep->profile_path && write_profile(rep, ctr, n_reads)) return UTREE_E_PROFILE;
-    if (re || se) { utree_set_error_text(keep); return UTREE_E_PROFILE; }      /* (no code of their own; a profile that was written sets no text) */
+    if (re || se || sre) { utree_set_error_text(keep); return UTREE_E_PROFILE; }      /* (no code of their own; a profile that was written sets no text) */
     return ce ? UTREE_E_COVERAGE : UTREE_OK;      /* (a profile that was written sets no text: the coverage's stands) */
 }

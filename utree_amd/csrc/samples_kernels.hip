@@ -23,77 +23,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "samples.h"
+#include "samples_dev.hpp"
 
 #define SM_BLOCK 1024
 #define SM_HSLOTS 8192u                    // LDS hash slots: 64 KiB of keys + 32 KiB of counts
 #define SM_LDS_PROBES 32u
-#define SM_DEV_PROBES 4096u
 #define SM_UNROLL 4
-#define SM_KEY_FREE (~0ull)                // an unused cell slot (and "no run yet")
-#define SM_ID_FREE 0ull                    // an unused id slot: a key's low word is the id's length + 1
-#define SM_NONE 0xFFFFFFFFu                // no sample: the error word says why
 
-__device__ __forceinline__ uint64_t sm_mix(uint64_t k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    return k ^ (k >> 33);
-}
-__device__ __forceinline__ void sm_add(unsigned long long *p, unsigned long long v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void sm_flag(const utk_samples_tab &t, unsigned long long f) {
-    (void)__hip_atomic_fetch_or(t.misc + 1, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ uint64_t sm_key(uint32_t slot, uint32_t label, uint32_t cut16) {
     return (uint64_t)slot << (UTK_SAMPLES_LABEL_BITS + 16u) | (uint64_t)label << 16 | cut16;
-}
-
-// bytes of the name in front of its last delimiter; the whole name when it has none
-__device__ __forceinline__ uint32_t sm_id_len(const uint8_t *__restrict__ name, uint32_t len, uint32_t delim) {
-    for (uint32_t i = len; i > 0; --i) if (name[i - 1] == delim) return i - 1;
-    return len;
-}
-__device__ __forceinline__ bool sm_same(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, uint32_t n) {
-    for (uint32_t i = 0; i < n; ++i) if (a[i] != b[i]) return false;
-    return true;
-}
-
-// the slot of the id's n bytes, claimed when no slot holds them yet; SM_NONE (and a flag) when the table or the arena has no room
-__device__ uint32_t sm_intern(const utk_samples_tab &t, const uint8_t *__restrict__ id, uint32_t n) {
-    uint32_t h = 0x811C9DC5u;
-    for (uint32_t i = 0; i < n; ++i) h = (h ^ id[i]) * 0x01000193u;
-    h ^= h >> 15; h *= 0x85EBCA77u; h ^= h >> 13;
-    unsigned long long mine = SM_ID_FREE;                  // the key of this lane's own arena copy, once written
-    const uint32_t probes = t.id_mask + 1 < SM_DEV_PROBES ? t.id_mask + 1 : SM_DEV_PROBES;
-    for (uint32_t p = 0; p < probes; ++p) {
-        const uint32_t s = (h + p) & t.id_mask;
-        unsigned long long *slot = t.ids + s;
-        unsigned long long k = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == SM_ID_FREE) {
-            if (mine == SM_ID_FREE) {
-                const unsigned long long at = __hip_atomic_fetch_add(t.misc + 2, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (at + n > t.arena_cap) { sm_flag(t, UTK_SAMPLES_F_ARENA); return SM_NONE; }
-                for (uint32_t i = 0; i < n; ++i) t.arena[at + i] = id[i];
-                mine = at << 32 | (n + 1u);
-            }
-            unsigned long long expect = SM_ID_FREE;
-            if (__hip_atomic_compare_exchange_strong(slot, &expect, mine, __ATOMIC_ACQ_REL, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) {
-                const unsigned long long c = __hip_atomic_fetch_add(t.misc + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (c >= t.sample_cap) { sm_flag(t, UTK_SAMPLES_F_TABLE); return SM_NONE; }
-                t.index[s] = (uint32_t)c;
-                return s;
-            }
-            k = expect;                                    // somebody else's id, complete: compare like any occupied slot
-        }
-        if ((uint32_t)k != n + 1u) continue;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // the bytes behind a key that has been seen
-        const uint8_t *a = t.arena + (k >> 32);
-        bool same = true;
-        for (uint32_t i = 0; i < n && same; ++i) same = __hip_atomic_load(a + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == id[i];
-        if (same) return s;
-    }
-    sm_flag(t, UTK_SAMPLES_F_TABLE);
-    return SM_NONE;
 }
 
 // cnt reads of a cell into the device tables: the sample's reads, then its unclassified reads or the cell's slot (or the full flag)
@@ -101,19 +39,7 @@ __device__ void sm_global_add(const utk_samples_tab &t, uint64_t key, uint32_t c
     const uint32_t slot = (uint32_t)(key >> (UTK_SAMPLES_LABEL_BITS + 16u));
     sm_add(t.reads + slot, cnt);
     if ((uint32_t)(key & 0xFFFFu) == UTK_SAMPLES_CUT_UNCL) { sm_add(t.uncl + slot, cnt); return; }
-    const uint32_t h = (uint32_t)sm_mix(key);
-    const uint32_t probes = t.cell_mask + 1 < SM_DEV_PROBES ? t.cell_mask + 1 : SM_DEV_PROBES;
-    for (uint32_t p = 0; p < probes; ++p) {
-        unsigned long long *c = t.cells + 2 * (size_t)((h + p) & t.cell_mask);
-        unsigned long long k = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == SM_KEY_FREE) {
-            k = SM_KEY_FREE;
-            __hip_atomic_compare_exchange_strong(c, &k, (unsigned long long)key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (k == SM_KEY_FREE) k = key;     // we claimed it
-        }
-        if (k == key) { sm_add(c + 1, cnt); return; }
-    }
-    sm_flag(t, UTK_SAMPLES_F_CELLS);
+    sm_cell_add(t, key, cnt);
 }
 
 struct SmLds {

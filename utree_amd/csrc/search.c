@@ -517,10 +517,10 @@ static void *gpu_main(void *arg) {
                 if (e) { set_error(P, e); return NULL; }
                 c->want_total = total;
                 HIPOK(hipMemcpyAsync(&s->h_meta[g], c->d_meta, sizeof(utree_pairs_meta), hipMemcpyDeviceToHost, c->stream));
+                if (P->names && (e = names_upload(P, s, g, first, count, lo1, hi1 - lo1))) { set_error(P, e); return NULL; }   /* (in front of the classify call: a report may read them there) */
                 e = utree_reports_classify(P->rep, (int)g, c->dev, c->d_joined, c->d_joff, c->d_jlen, (uint32_t)count, total, mx, P->do_rc, c->d_out,
-                                           c->d_ws, c->ws_bytes, c->stream);
+                                           c->d_ws, c->ws_bytes, c->d_buf, hi1 - lo1, c->d_name_off, c->d_name_len, c->stream);
                 if (e) { set_error(P, e); return NULL; }
-                if (P->names && (e = names_upload(P, s, g, first, count, lo1, hi1 - lo1))) { set_error(P, e); return NULL; }
                 e = utree_reports_add(P->rep, (int)g, c->d_joined, c->d_joff, c->d_jlen, c->d_out, (uint32_t)count, P->do_rc, 0, c->d_buf, hi1 - lo1,
                                       c->d_name_off, c->d_name_len, c->stream);
                 if (e) { set_error(P, e); return NULL; }
@@ -539,12 +539,13 @@ static void *gpu_main(void *arg) {
             HIPOK(hipMemcpyAsync(c->d_buf, s->h_buf + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
             HIPOK(hipMemcpyAsync(c->d_off, s->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
             HIPOK(hipMemcpyAsync(c->d_len, s->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
-            int e = P->rank ? utree_rank_batch(c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
-                                               P->rank, c->d_out, c->d_ws, c->ws_bytes, c->stream)
-                            : utree_reports_classify(P->rep, (int)g, c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
-                                                     c->d_out, c->d_ws, c->ws_bytes, c->stream);
+            int e = P->names ? names_upload(P, s, g, first, count, lo, hi - lo) : UTREE_OK;
             if (e) { set_error(P, e); return NULL; }
-            if (P->names && (e = names_upload(P, s, g, first, count, lo, hi - lo))) { set_error(P, e); return NULL; }
+            e = P->rank ? utree_rank_batch(c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
+                                           P->rank, c->d_out, c->d_ws, c->ws_bytes, c->stream)
+                        : utree_reports_classify(P->rep, (int)g, c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
+                                                 c->d_out, c->d_ws, c->ws_bytes, c->d_buf, hi - lo, c->d_name_off, c->d_name_len, c->stream);
+            if (e) { set_error(P, e); return NULL; }
             e = utree_reports_add(P->rep, (int)g, c->d_buf, c->d_off, c->d_len, c->d_out, (uint32_t)count, P->do_rc, P->rank != NULL, c->d_buf, hi - lo,
                                   c->d_name_off, c->d_name_len, c->stream);
             if (e) { set_error(P, e); return NULL; }
@@ -913,17 +914,18 @@ done:
 /* One whole-file search as every public entry point asks for it.  rank: NULL = the GG search over n_dev device handles; else XT_doSearch32(utree,
  * in, out, 0, speed, doRC) (itree.c:1376 without DO_GG): the same pipeline, the batches to ONE device in file order because each read's vote
  * depends on the reads before it (rank.c).  profile_path / coverage_path: NULL, or the report to feed while searching and to write when the
- * search has succeeded (the search's own codes stay its own); redist_path: the same for the redistribution (GG search only). */
+ * search has succeeded (the search's own codes stay its own); redist_path, sredist_path: the same for the redistribution and the per-sample
+ * redistribution (GG search only). */
 static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int paired,
                           const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format,
                           const char *profile_path, const char *coverage_path, const char *redist_path, uint32_t redist_passes,
-                          const char *hitmap_path, const char *samples_path, int delim, utree_search_stats *stats) {
+                          const char *hitmap_path, const char *samples_path, int delim, const char *sredist_path, utree_search_stats *stats) {
     utree_reports *rep = NULL;
     utree_search_stats st;
     char hm_msg[512] = "";                                         /* why the hit map was not written, when it was not */
     memset(&st, 0, sizeof st);
-    if (rank && (redist_path || hitmap_path)) return UTREE_E_ARG;  /* (another vote: no candidate sets; a hit-dependent subset of windows: no map) */
-    int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, redist_path, redist_passes, samples_path, delim, &rep);
+    if (rank && (redist_path || hitmap_path || sredist_path)) return UTREE_E_ARG;  /* (another vote: no candidate sets; a hit-dependent subset of windows: no map) */
+    int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, redist_path, redist_passes, samples_path, delim, sredist_path, &rep);
     if (!rc && !rep && !hitmap_path)
         return search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, NULL, NULL, NULL, stats);   /* no report asked for */
     if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, rep, hitmap_path, hm_msg, &st);
@@ -936,20 +938,20 @@ static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, con
 
 int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
                       int do_rc, int host_threads, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, NULL, 0, NULL, NULL, 0, stats);
+    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, NULL, 0, NULL, NULL, 0, NULL, stats);
 }
 int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
                            int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, NULL, 0, NULL, NULL, 0, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, NULL, 0, NULL, NULL, 0, NULL, stats);
 }
 int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                               int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, NULL, 0, NULL, NULL, 0, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, NULL, 0, NULL, NULL, 0, NULL, stats);
 }
 int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                                int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                                utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, NULL, 0, stats);
+    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, NULL, 0, NULL, stats);
 }
 
 /* pairs: both mates of a pair cast one vote (include/utree_amd.h) */
@@ -957,7 +959,7 @@ int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, c
                             int do_rc, int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                             utree_search_stats *stats) {
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : PAIRS_INTERLEAVED, out_path, do_rc, NULL,
-                          host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, NULL, 0, stats);
+                          host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, NULL, 0, NULL, stats);
 }
 
 int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
@@ -966,7 +968,7 @@ int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n
                                    utree_search_stats *stats) {
     if (mates_path && interleaved) return UTREE_E_ARG;
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, NULL, NULL, 0, stats);
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, NULL, NULL, 0, NULL, stats);
 }
 
 int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int interleaved,
@@ -975,7 +977,7 @@ int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, 
                              utree_search_stats *stats) {
     if (mates_path && interleaved) return UTREE_E_ARG;
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, NULL, 0, stats);
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, NULL, 0, NULL, stats);
 }
 
 /* a sample table of multiplexed reads next to everything else (include/utree_amd.h) */
@@ -987,7 +989,21 @@ int utree_search_file_samples(const utree_ctr *ctr, utree_dev **devs, int n_dev,
     if (samples_path && (delim < 0 || delim > 255 || delim == '\t' || delim == ' ' || delim == '\r' || delim == '\n')) return UTREE_E_ARG;
     return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
                           do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, samples_path,
-                          delim, stats);
+                          delim, NULL, stats);
+}
+
+/* ... and the per-sample redistribution (include/utree_amd.h) */
+int utree_search_file_sample_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                                          int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
+                                          const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
+                                          const char *hitmap_path, const char *samples_path, int delim, const char *sample_redistribute_path,
+                                          utree_search_stats *stats) {
+    if (mates_path && interleaved) return UTREE_E_ARG;
+    if ((samples_path || sample_redistribute_path) && (delim < 0 || delim > 255 || delim == '\t' || delim == ' ' || delim == '\r' || delim == '\n'))
+        return UTREE_E_ARG;
+    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
+                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, samples_path,
+                          delim, sample_redistribute_path, stats);
 }
 
 int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_off1, const uint32_t *d_len1, const uint8_t *d_bases2,
@@ -1025,5 +1041,5 @@ int utree_rank_search_file_samples(const utree_ctr *ctr, utree_dev *dev, const c
     int rc = utree_rank_reset(dev);
     if (rc) return rc;
     return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, NULL, 0, NULL,
-                          samples_path, delim, stats);
+                          samples_path, delim, NULL, stats);
 }

@@ -115,6 +115,16 @@ class SamplesTable(C.Structure):
                 ("cells", C.c_void_p), ("n_cells", C.c_size_t), ("n_reads", C.c_uint64)]
 
 
+class SredistCell(C.Structure):
+    """utree_sredist_cell: `reads` reads of sample `sample` whose candidates are labels [first, first + n) of the flat label array."""
+    _fields_ = [("sample", C.c_uint32), ("n", C.c_uint32), ("first", C.c_uint64), ("reads", C.c_uint64)]
+
+
+class SredistEntry(C.Structure):
+    """utree_sredist_entry: per (sample, label), the reads assigned after the sample's passes and the reads whose only candidate it is."""
+    _fields_ = [("sample", C.c_uint32), ("label", C.c_uint32), ("assigned", C.c_uint64), ("unique", C.c_uint64)]
+
+
 class Result(C.Structure):
     _fields_ = [("label", C.c_uint32), ("cut", C.c_int32), ("found", C.c_uint32), ("uix", C.c_uint32),
                 ("sl", C.c_uint32), ("ol", C.c_uint32)]
@@ -240,6 +250,25 @@ SYMBOLS = {
                                             C.POINTER(SearchStats)]),
     "utree_rank_search_file_samples": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(RankParams),
                                                  C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(SearchStats)]),
+    "utree_sredist_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "utree_sredist_reset": (C.c_int, [C.c_void_p]),
+    "utree_sredist_free": (None, [C.c_void_p]),
+    "utree_sredist_classify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
+                                               C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]),
+    "utree_sredist_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                     C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "utree_sredist_insert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_size_t, C.c_uint64]),
+    "utree_sredist_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "utree_sredist_solve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
+    "utree_sredist_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_size_t, C.c_uint64, C.c_char_p]),
+    "utree_search_file_sample_redistribute": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
+                                                        C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p,
+                                                        C.c_char_p, C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
 }
 
 

@@ -10,6 +10,7 @@
     tree.profile(capacity)           per-taxon read counts of classified batches (no counterpart in the reference)
     tree.coverage()                  per-taxon database k-mers, distinct ones hit, hits (no counterpart in the reference)
     tree.samples()                   per-sample taxon table of multiplexed reads, ids interned on the device (no counterpart in the reference)
+    tree.sample_redistribution()     ambiguous reads of multiplexed reads redistributed within each sample (no counterpart in the reference)
     tree.redistribution()            candidate sets of ambiguous reads, redistributed among their tied labels (as xtree does)
 
 torch is used only for device memory and streams (plumbing); every computation happens in the HIP kernels
@@ -31,6 +32,8 @@ PROFILE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("cut", "<i4"), ("reads", "<u8
 COVERAGE_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("pad", "<u4"), ("db_kmers", "<u8"), ("covered", "<u8"), ("hits", "<u8")])
 REDIST_SET_DTYPE = np.dtype([("reads", "<u8"), ("first", "<u8"), ("n", "<u4"), ("pad", "<u4")])
 REDIST_ENTRY_DTYPE = np.dtype([("label", "<u4"), ("pad", "<u4"), ("assigned", "<u8"), ("unique", "<u8")])
+SREDIST_CELL_DTYPE = np.dtype([("sample", "<u4"), ("n", "<u4"), ("first", "<u8"), ("reads", "<u8")])
+SREDIST_ENTRY_DTYPE = np.dtype([("sample", "<u4"), ("label", "<u4"), ("assigned", "<u8"), ("unique", "<u8")])
 SAMPLES_CELL_DTYPE = np.dtype([("sample", "<u4"), ("label", "<u4"), ("cut", "<i4"), ("pad", "<u4"), ("reads", "<u8")])
 
 
@@ -412,6 +415,12 @@ class DeviceTree:
         """A sample table on this device (utree_samples_create): at most sample_capacity distinct ids, cell_capacity (sample, taxon) slots."""
         return Samples(self, sample_capacity, cell_capacity, delim)
 
+    def sample_redistribution(self, sample_capacity: int = 1 << 16, set_capacity: int = 1 << 22, cell_capacity: int = 1 << 22,
+                              delim: bytes = b"_") -> "SampleRedistribution":
+        """A per-sample redistribution handle on this device (utree_sredist_create): at most sample_capacity distinct ids, set_capacity slots
+        for distinct multi-label candidate sets, cell_capacity (sample, candidate set) slots."""
+        return SampleRedistribution(self, sample_capacity, set_capacity, cell_capacity, delim)
+
     def close(self):
         if self._h:
             _lib.load().utree_dev_free(self._h)
@@ -733,6 +742,165 @@ class Redistribution:
             pass
 
 
+class SredistReadback:
+    """One handle's read-back (utree_sredist_read): ids a list of bytes, reads / unclassified uint64 arrays per sample, cells a
+    SREDIST_CELL_DTYPE array into the flat uint32 array labels, n_reads the records added."""
+
+    def __init__(self, ids, reads, unclassified, cells, labels, n_reads):
+        self.ids = list(ids)
+        self.reads = np.ascontiguousarray(reads, dtype=np.uint64)
+        self.unclassified = np.ascontiguousarray(unclassified, dtype=np.uint64)
+        self.cells = np.ascontiguousarray(cells, dtype=SREDIST_CELL_DTYPE)
+        self.labels = np.ascontiguousarray(labels, dtype=np.uint32)
+        self.n_reads = int(n_reads)
+
+    def multisets(self):
+        """{sample id: {sorted tuple of file-order label indices: reads}}, every sample of the read-back a key"""
+        out = {i: {} for i in self.ids}
+        for s, n, first, reads in self.cells.tolist():
+            key = tuple(sorted(self.labels[first:first + n].tolist()))
+            d = out[self.ids[s]]
+            d[key] = d.get(key, 0) + reads
+        return out
+
+
+def _ids_flat(ids):
+    raw = np.frombuffer(b"".join(ids) + b"\0", dtype=np.uint8).copy()
+    off = np.zeros(len(ids) + 1, dtype=np.uint64)
+    if ids:
+        off[1:] = np.cumsum([len(i) for i in ids], dtype=np.uint64)
+    return raw, off
+
+
+class SampleRedistribution:
+    """Candidate sets per sample on one device and every sample's redistribution (utree_sredist_*): classify() is DeviceTree.classify()
+    that also counts the batch's reads per (sample, candidate set), read() brings ids, counts and cells back, insert() adds such a read-back,
+    solve() runs every sample's passes, write() writes the file."""
+
+    def __init__(self, tree: DeviceTree, sample_capacity: int = 1 << 16, set_capacity: int = 1 << 22, cell_capacity: int = 1 << 22,
+                 delim: bytes = b"_"):
+        if not (isinstance(delim, (bytes, bytearray)) and len(delim) == 1):
+            raise ValueError("SampleRedistribution: delim must be one byte")
+        self.tree = tree
+        self._ws = None
+        h = C.c_void_p()
+        _lib.check(_lib.load().utree_sredist_create(tree._h, sample_capacity, set_capacity, cell_capacity, delim[0], C.byref(h)),
+                   "utree_sredist_create")
+        self._h = h
+
+    def classify(self, bases, off, length, text, name_off, name_len, rc: bool = False, total_bases: Optional[int] = None,
+                 max_len: Optional[int] = None, out=None, workspace=None):
+        """As DeviceTree.classify (the same results, bit for bit) with the reads' names as Samples.add takes them: text uint8, name_off /
+        name_len int32 CUDA tensors.  Asynchronous on torch's current stream; any number of streams may add at once (give each its own
+        workspace)."""
+        import torch
+        n = off.numel()
+        dev = bases.device
+        ok = lambda t, dt: isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.is_cuda and t.device == dev
+        if not (ok(text, torch.uint8) and ok(name_off, torch.int32) and ok(name_len, torch.int32) and name_off.numel() >= n and name_len.numel() >= n):
+            raise ValueError("SampleRedistribution.classify: text uint8, name_off / name_len int32 with a name per read, contiguous on the reads' device")
+        if total_bases is None:
+            total_bases = int(length.sum().item())
+        if max_len is None:
+            max_len = int(length.max().item()) if n else 0
+        if out is None:
+            out = torch.empty((n, 6), dtype=torch.int32, device=dev)
+        need = self.tree.workspace_bytes(n, total_bases, max_len, rc)
+        if workspace is None:
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            workspace = self._ws
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().utree_sredist_classify_batch(self._h, self.tree._h, bases.data_ptr(), off.data_ptr(), length.data_ptr(), n,
+                                                            total_bases, max_len, int(rc), text.data_ptr(), text.numel(), name_off.data_ptr(),
+                                                            name_len.data_ptr(), out.data_ptr(), workspace.data_ptr(), workspace.numel(), stream),
+                   "utree_sredist_classify_batch")
+        return out
+
+    def read(self) -> SredistReadback:
+        """Raises UtreeError(E_DEVICE) when a table was too small or a record or name was refused: there is no table then."""
+        L = _lib.load()
+        ns, nb, nc, nl, nr = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+        code = L.utree_sredist_read(self._h, None, 0, None, None, None, 0, None, 0, None, 0, C.byref(ns), C.byref(nb), C.byref(nc), C.byref(nl),
+                                    C.byref(nr))
+        if code not in (_lib.OK, _lib.E_ARG):
+            _lib.check(code, "utree_sredist_read")
+        S = ns.value
+        ids = np.zeros(max(nb.value, 1), dtype=np.uint8)
+        off = np.zeros(S + 1, dtype=np.uint64)
+        reads = np.zeros(max(S, 1), dtype=np.uint64)
+        uncl = np.zeros(max(S, 1), dtype=np.uint64)
+        cells = np.zeros(max(nc.value, 1), dtype=SREDIST_CELL_DTYPE)
+        labels = np.zeros(max(nl.value, 1), dtype=np.uint32)
+        _lib.check(L.utree_sredist_read(self._h, ids.ctypes.data, nb.value, off.ctypes.data, reads.ctypes.data, uncl.ctypes.data, S,
+                                        cells.ctypes.data, nc.value, labels.ctypes.data, nl.value, C.byref(ns), C.byref(nb), C.byref(nc),
+                                        C.byref(nl), C.byref(nr)), "utree_sredist_read")
+        raw = ids.tobytes()
+        return SredistReadback([raw[int(off[i]):int(off[i + 1])] for i in range(S)], reads[:S], uncl[:S], cells[:nc.value].copy(),
+                               labels[:nl.value].copy(), nr.value)
+
+    def insert(self, rb: SredistReadback):
+        """utree_sredist_insert: the ids, counts and cells of a read-back (or of the same form made on the host) added to this handle."""
+        raw, off = _ids_flat(rb.ids)
+        S = len(rb.ids)
+        _lib.check(_lib.load().utree_sredist_insert(self._h, raw.ctypes.data, off.ctypes.data, rb.reads.ctypes.data if S else None,
+                                                    rb.unclassified.ctypes.data if S else None, S, rb.cells.ctypes.data if len(rb.cells) else None,
+                                                    len(rb.cells), rb.labels.ctypes.data if len(rb.labels) else None, len(rb.labels), rb.n_reads),
+                   "utree_sredist_insert")
+
+    def merge(self, other: "SampleRedistribution"):
+        """self += other; the handles may be on different devices."""
+        _lib.check(_lib.load().utree_sredist_merge(self._h, other._h), "utree_sredist_merge")
+
+    def solve(self, max_passes: int = 100, n_samples: Optional[int] = None, n_labels: Optional[int] = None):
+        """(entries, passes, ambiguous): entries a SREDIST_ENTRY_DTYPE array ((sample, label) with a figure only, samples numbered as read()
+        numbers them), passes and ambiguous arrays per sample."""
+        if n_samples is None or n_labels is None:
+            rb = self.read()
+            n_samples, n_labels = len(rb.ids), len(rb.labels)
+        buf = np.zeros(max(n_labels, 1), dtype=SREDIST_ENTRY_DTYPE)
+        p = np.zeros(max(n_samples, 1), dtype=np.uint32)
+        a = np.zeros(max(n_samples, 1), dtype=np.uint64)
+        n, s = C.c_size_t(0), C.c_size_t(0)
+        _lib.check(_lib.load().utree_sredist_solve(self._h, max_passes, buf.ctypes.data, n_labels, C.byref(n), p.ctypes.data, a.ctypes.data,
+                                                   n_samples, C.byref(s)), "utree_sredist_solve")
+        return buf[:n.value].copy(), p[:s.value].copy(), a[:s.value].copy()
+
+    def write(self, path: str, max_passes: int = 100):
+        rb = self.read()
+        e, p, a = self.solve(max_passes, len(rb.ids), len(rb.labels))
+        write_sample_redistribution(self.tree.db, rb.ids, rb.reads, rb.unclassified, p, a, e, rb.n_reads, path)
+
+    def reset(self):
+        _lib.check(_lib.load().utree_sredist_reset(self._h), "utree_sredist_reset")
+
+    def close(self):
+        if self._h:
+            _lib.load().utree_sredist_free(self._h)
+            self._h = None
+            self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_sample_redistribution(db: CtrDB, ids, reads, unclassified, passes, ambiguous, entries, n_reads: int, path: str):
+    """utree_sredist_write (host only): the samples of a read-back and the figures of a solve, labels merged by text, written."""
+    raw, off = _ids_flat(list(ids))
+    S = len(ids)
+    r, u = np.ascontiguousarray(reads, dtype=np.uint64), np.ascontiguousarray(unclassified, dtype=np.uint64)
+    p, a = np.ascontiguousarray(passes, dtype=np.uint32), np.ascontiguousarray(ambiguous, dtype=np.uint64)
+    if not (len(r) == len(u) == len(p) == len(a) == S):
+        raise ValueError("write_sample_redistribution: one figure per sample")
+    e = np.ascontiguousarray(entries, dtype=SREDIST_ENTRY_DTYPE)
+    _lib.check(_lib.load().utree_sredist_write(db._h, raw.ctypes.data, off.ctypes.data, r.ctypes.data if S else None, u.ctypes.data if S else None,
+                                               p.ctypes.data if S else None, a.ctypes.data if S else None, S, e.ctypes.data if len(e) else None,
+                                               len(e), n_reads, path.encode()), "utree_sredist_write")
+
+
 def write_redistribution(db: CtrDB, entries: np.ndarray, n_reads: int, ambiguous: int, passes: int, path: str):
     """utree_redist_write: entries (REDIST_ENTRY_DTYPE, from any number of solves) merged by text, rolled up, written."""
     e = np.ascontiguousarray(entries, dtype=REDIST_ENTRY_DTYPE)
@@ -750,7 +918,8 @@ def write_coverage(db: CtrDB, entries: np.ndarray, n_reads: int, path: str):
 def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: bool = False, threads: int = 0,
               input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None,
               mates: Optional[str] = None, interleaved: bool = False, redistribute: Optional[str] = None, redist_passes: int = 100,
-              hitmap: Optional[str] = None, samples: Optional[str] = None, sample_delim: bytes = b"_"):
+              hitmap: Optional[str] = None, samples: Optional[str] = None, sample_delim: bytes = b"_",
+              sample_redistribute: Optional[str] = None):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
     FASTA / gzip input.  profile: also write the per-taxon read counts there; coverage: also write the per-taxon k-mer
@@ -763,11 +932,22 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
     hitmap: also write every query's k-mer hit map there, and the label texts to hitmap + ".labels" (utree_search_file_hitmap); a map that
     cannot be written returns E_HITMAP.
     samples: the reads are a combined file named <sample><sample_delim><n>; also write the taxon x sample table there
-    (utree_search_file_samples); a table that cannot be written returns E_PROFILE."""
+    (utree_search_file_samples); a table that cannot be written returns E_PROFILE.
+    sample_redistribute: also write the taxon x sample table with every sample's ambiguous reads redistributed within that sample there
+    (utree_search_file_sample_redistribute; ids cut at sample_delim, at most redist_passes passes per sample); E_PROFILE likewise."""
     if mates is not None and interleaved:
         raise ValueError("search_gg: give mates= or interleaved=True, not both")
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     st = _lib.SearchStats()
+    if sample_redistribute is not None:
+        if not (isinstance(sample_delim, (bytes, bytearray)) and len(sample_delim) == 1):
+            raise ValueError("search_gg: sample_delim must be one byte")
+        enc = lambda p: p.encode() if p is not None else None
+        code = _lib.load().utree_search_file_sample_redistribute(db._h, arr, len(trees), fasta.encode(), enc(mates), int(interleaved), out.encode(),
+                                                                 int(rc), threads, input_format, enc(profile), enc(coverage), enc(redistribute),
+                                                                 redist_passes, enc(hitmap), enc(samples), sample_delim[0],
+                                                                 sample_redistribute.encode(), C.byref(st))
+        return code, st
     if samples is not None:
         if not (isinstance(sample_delim, (bytes, bytearray)) and len(sample_delim) == 1):
             raise ValueError("search_gg: sample_delim must be one byte")
