@@ -36,6 +36,9 @@ class RankResult(C.Structure):
                 ("second", C.c_uint32)]
 
 
+RANK_RESULT_DTYPE = np.dtype([("label", "<u4"), ("printed", "<u4"), ("found", "<u4"), ("most", "<u4"), ("second", "<u4")])
+
+
 def build(force: bool = False) -> str:
     so = os.path.join(_HERE, "liboracle.so")
     src = os.path.join(_HERE, "utree_oracle.c")
@@ -80,6 +83,9 @@ def lib():
         L.orc_rank_state_free.argtypes = [C.c_void_p]
         L.orc_rank_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(RankParams),
                                     C.POINTER(RankResult)]
+        L.orc_rank_read_batch.restype = None
+        L.orc_rank_read_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                          C.POINTER(RankParams), C.c_void_p]
         L.orc_rank_format.restype = C.c_size_t
         L.orc_rank_format.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(RankResult), C.c_char_p, C.c_size_t]
         L.orc_rank_search_file.restype = C.c_int
@@ -198,6 +204,16 @@ class RankSearch:
         lib().orc_rank_read(self.db._h, self._st, b.ctypes.data if len(b) else None, len(b), int(rc),
                             C.byref(self.prm), C.byref(r))
         return r
+
+    def read_batch(self, buf, off, length, rc: bool = False) -> np.ndarray:
+        """read() for reads off[i], length[i] of buf in that order; one RANK_RESULT_DTYPE record each."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        length = np.ascontiguousarray(length, dtype=np.uint32)
+        out = np.zeros(len(off), dtype=RANK_RESULT_DTYPE)
+        lib().orc_rank_read_batch(self.db._h, self._st, buf.ctypes.data, off.ctypes.data, length.ctypes.data, len(off),
+                                  int(rc), C.byref(self.prm), out.ctypes.data)
+        return out
 
     def format(self, name: bytes, r: RankResult) -> bytes:
         cap = len(name) + 70000

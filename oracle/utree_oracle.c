@@ -646,6 +646,11 @@ void orc_rank_read(const orc_db *db, orc_rank_state *st, const uint8_t *seq, siz
     res->printed = !((int)most < (int)prm->tolerance || (int)most < (int)(prm->slack * second));   /* 1000 */
 }
 
+void orc_rank_read_batch(const orc_db *db, orc_rank_state *st, const uint8_t *buf, const uint64_t *off,
+                         const uint32_t *len, size_t n, int do_rc, const orc_rank_params *prm, orc_rank_result *res) {
+    for (size_t i = 0; i < n; ++i) orc_rank_read(db, st, buf + off[i], len[i], do_rc, prm, &res[i]);
+}
+
 size_t orc_rank_format(const orc_db *db, const char *name, size_t name_len, const orc_rank_result *r, char *out,
                        size_t cap) {
     if (!r->found || !r->printed) return 0;

@@ -85,6 +85,9 @@ orc_rank_state *orc_rank_state_new(const orc_db *db);
 void orc_rank_state_free(orc_rank_state *st);
 void orc_rank_read(const orc_db *db, orc_rank_state *st, const uint8_t *seq, size_t len, int do_rc,
                    const orc_rank_params *prm, orc_rank_result *res);
+/* orc_rank_read over reads off[i], len[i] of buf, i = 0 .. n-1 in that order: the same calls, one record each */
+void orc_rank_read_batch(const orc_db *db, orc_rank_state *st, const uint8_t *buf, const uint64_t *off,
+                         const uint32_t *len, size_t n, int do_rc, const orc_rank_params *prm, orc_rank_result *res);
 size_t orc_rank_format(const orc_db *db, const char *name, size_t name_len, const orc_rank_result *r, char *out,
                        size_t cap);
 int orc_rank_search_file(const orc_db *db, const char *fasta, const char *out, int do_rc,

@@ -20,7 +20,8 @@ Fixture sets:
   k64ix32 F4  PACKSIZE=64 and IXTYPE=uint32_t together (+RC)
 
 `python tests/golden/make_golden.py reference_runs` writes reference_runs.json: hashes of the reference's results on the
-inputs tests/util.py generates (adversarial labels, byte and framing fuzz, hostile BUILD inputs, irregular PACKSIZE=16 tables).
+inputs tests/util.py and tests/rank_inputs.py generate (adversarial labels, byte and framing fuzz, hostile BUILD inputs, irregular
+PACKSIZE=16 tables, the rank-specific search's depth and vote-split files); `reference_runs rank_depth` adds only the last two.
 """
 import gzip
 import hashlib
@@ -730,7 +731,10 @@ def gen_build(manifest, seed=2025):
     manifest["build_outputs"] = out
 
 
-def gen_reference_runs():
+RANK_DEPTH_BINS = {"xtree-search": "", "xtree-search-p32s1t1": "_p32s1t1", "xtree-search-s1t1": "_s1t1"}
+
+
+def gen_reference_runs(only_rank_depth=False):
     """reference_runs.json: what the genuine binaries did on the inputs tests/util.py generates for the oracle-vs-reference tests
     (tests/test_oracle_golden.py) -- SHA-256 of every input, exit code, SHA-256 of every output file (None where none was written) --
     so that those tests hold the oracle to the reference without the reference at hand."""
@@ -748,6 +752,20 @@ def gen_reference_runs():
     out = {}
     with tempfile.TemporaryDirectory() as td:
         fa, want = os.path.join(td, "r.fa"), os.path.join(td, "ref.txt")
+        # the rank-specific search on the generated files of tests/rank_inputs.py (`rk`): > 2 * 262 144 reads, and the 62 .. 65-hit votes
+        import rank_inputs
+        ctr = util.fixture_ctr("rk")
+        for key, data in (("rank_depth_1", rank_inputs.depth_case(1).data), ("rank_split_1", rank_inputs.vote_split_case(1).data)):
+            open(fa, "wb").write(data)
+            for exe, sfx in RANK_DEPTH_BINS.items():
+                if key == "rank_depth_1" and sfx == "_s1t1":
+                    continue
+                out[key + sfx] = ref_run(exe, {"ctr": ctr, "fa": data}, [ctr, fa, want, "1"], {"out": want})
+        if only_rank_depth:                                   # add these to the recorded runs, leave the others as they are
+            full = json.load(open(os.path.join(HERE, "reference_runs.json")))
+            full.update(out)
+            json.dump(full, open(os.path.join(HERE, "reference_runs.json"), "w"), indent=1, sort_keys=True)
+            return
         for seed, max_depth in [(1, 8), (2, 8), (3, 8), (4, 7), (5, 7), (6, 5)]:
             ctr, data, _ = util.adversarial_vote_case(seed, td, max_depth)
             open(fa, "wb").write(data)
@@ -793,7 +811,7 @@ def main():
     if not os.path.exists(os.path.join(REF, "xtree-searchGG")):
         sys.exit("build the reference first: make -C oracle ref")
     if len(sys.argv) > 1 and sys.argv[1] == "reference_runs":  # add reference_runs.json (the oracle-vs-reference tests' expected results)
-        gen_reference_runs()
+        gen_reference_runs(only_rank_depth=len(sys.argv) > 2 and sys.argv[2] == "rank_depth")
         return
     if len(sys.argv) > 1 and sys.argv[1] == "compress":       # add the COMPRESS fixtures to an existing golden set
         manifest = json.load(open(os.path.join(HERE, "manifest.json")))

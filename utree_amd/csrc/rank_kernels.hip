@@ -221,6 +221,9 @@ __device__ __forceinline__ uint32_t prev_greater(const utk_rank_ws &ws, uint32_t
         uint32_t grp = pick_last_greater(ws.lvl[1], s2 << 6, g1, n, lane);
         if (grp == NONE) {
             uint32_t sup = NONE;
+            // The first pass looks at the 64 entries of lvl[2] that hold s2.  The walk to earlier ones (b -= 64) needs a
+            // batch of more than 64^4 = 16.7 M reads; the file pipeline caps a batch at 2 Mi reads (MAX_READS_PER_BATCH),
+            // so no test gets there (tests/test_gpu_rank_depth.py reaches lvl[2] with batches of > 2 * 262 144 reads).
             for (int64_t b = (int64_t)((s2 >> 6) << 6); b >= 0 && sup == NONE; b -= 64)
                 sup = pick_last_greater(ws.lvl[2], (uint32_t)b, s2, n, lane);
             if (sup == NONE) return NONE;
