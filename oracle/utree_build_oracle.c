@@ -116,7 +116,7 @@ static int by_word(const void *a, const void *b) { u128 x = ((const node *)a)->w
 
 int orc_build_file(const char *fasta, const char *map, const char *out_ubt, int W, int I, int complevel, int gg,
                    uint64_t *n_seqs, uint64_t *n_nodes, uint64_t *n_labels, char *err, size_t errlen) {
-    if ((W != 8 && W != 16) || (I != 2 && I != 4) || complevel < 0) { set_err(err, errlen, "bad W/I/complevel"); return 3; }
+    if ((W != 4 && W != 8 && W != 16) || (I != 2 && I != 4) || complevel < 0) { set_err(err, errlen, "bad W/I/complevel"); return 3; }
     const uint32_t K = 4u * (uint32_t)W, k1 = K - 1, lv = (uint32_t)complevel, kv = k1 + lv;
     const uint32_t BAD = I == 2 ? 0xFFFFu : 0xFFFFFFFFu, EMPTY = BAD - 1;             /* itree.c:105-106 */
     size_t fn = 0, mn = 0;
@@ -190,6 +190,7 @@ int orc_build_file(const char *fasta, const char *map, const char *out_ubt, int 
             }
             if (bad) { i += j - (i - k1) + lv; continue; }                               /* 612: resume right after the bad base */
             if (K == 32) w &= (u128)0xFFFFFFFFFFFFFFFFull;
+            if (K == 16) w &= (u128)0xFFFFFFFFull;                                       /* PACKSIZE 16: a uint32_t word */
             int fresh;
             uint64_t h = km_slot(&km, w, ix, &fresh);
             if (fresh || km.val[h] == ix) continue;                                      /* 262 / 280 */

@@ -21,7 +21,8 @@ Fixture sets:
 
 `python tests/golden/make_golden.py reference_runs` writes reference_runs.json: hashes of the reference's results on the
 inputs tests/util.py and tests/rank_inputs.py generate (adversarial labels, byte and framing fuzz, hostile BUILD inputs, irregular
-PACKSIZE=16 tables, the rank-specific search's depth and vote-split files); `reference_runs rank_depth` adds only the last two.
+PACKSIZE=16 tables, the rank-specific search's depth and vote-split files); `reference_runs rank_depth` adds only the last two,
+`reference_runs build_edges` adds only the BUILD edge inputs of tests/build_inputs.py (those records also keep the reference's stdout lines).
 """
 import gzip
 import hashlib
@@ -807,10 +808,40 @@ def gen_reference_runs(only_rank_depth=False):
     json.dump(out, open(os.path.join(HERE, "reference_runs.json"), "w"), indent=1, sort_keys=True)
 
 
+def gen_build_edges_runs():
+    """Adds the `build_edges_*` keys to reference_runs.json and leaves the others as they are: what the genuine builder of each PACKSIZE
+    (oracle/_ref/utree-build[GG][-k16|-k64], one thread) did on the inputs of tests/build_inputs.py -- exit code, SHA-256 of `.ubt` and log,
+    and every line it printed."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import build_inputs
+    import util
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        fa, mp, ubt = os.path.join(td, "i.fa"), os.path.join(td, "i.map"), os.path.join(td, "o.ubt")
+        for r in build_inputs.runs():
+            case = r.make()
+            open(fa, "wb").write(case.fa)
+            open(mp, "wb").write(case.map)
+            outputs = {"ubt": ubt, "log": ubt + (".gg.log" if r.gg else ".log")}
+            for f in outputs.values():
+                if os.path.exists(f):
+                    os.remove(f)
+            code, so, _ = run([os.path.join(REF, build_inputs.reference_binary(r.W, r.gg)), fa, mp, ubt, "1", str(r.lv)])
+            out[r.key] = {"inputs": {"fa": util.sha256_of(case.fa), "map": util.sha256_of(case.map)}, "exit": code,
+                          "outputs": {k: util.sha256_of(f) for k, f in outputs.items()}, "stdout": so.decode("latin-1").splitlines()}
+    full = json.load(open(os.path.join(HERE, "reference_runs.json")))
+    full = {k: v for k, v in full.items() if not k.startswith("build_edges_")}
+    full.update(out)
+    json.dump(full, open(os.path.join(HERE, "reference_runs.json"), "w"), indent=1, sort_keys=True)
+
+
 def main():
     if not os.path.exists(os.path.join(REF, "xtree-searchGG")):
         sys.exit("build the reference first: make -C oracle ref")
     if len(sys.argv) > 1 and sys.argv[1] == "reference_runs":  # add reference_runs.json (the oracle-vs-reference tests' expected results)
+        if len(sys.argv) > 2 and sys.argv[2] == "build_edges":
+            gen_build_edges_runs()
+            return
         gen_reference_runs(only_rank_depth=len(sys.argv) > 2 and sys.argv[2] == "rank_depth")
         return
     if len(sys.argv) > 1 and sys.argv[1] == "compress":       # add the COMPRESS fixtures to an existing golden set

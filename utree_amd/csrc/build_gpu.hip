@@ -490,7 +490,9 @@ fail:
 int utk_build_phase2(utk_build_state *S, const uint32_t *h_ix_of_u, uint32_t n_u, uint32_t n_labels, int fd, uint64_t *h_per_label) {
     int rc = UTREE_OK;
     uint32_t *d_ix = nullptr; unsigned long long *d_cnt = nullptr; uint8_t *d_out = nullptr; uint8_t *h_out = nullptr;
-    const uint64_t CH = 32ull << 20, rec = (uint64_t)(S->W + S->I);   /* W = 4: a 4-byte uint32_t word + I bytes */
+    uint64_t CH = 32ull << 20;                                        /* records per launch */
+    const uint64_t rec = (uint64_t)(S->W + S->I);                     /* W = 4: a 4-byte uint32_t word + I bytes */
+    { const char *e = getenv("UTREE_TEST_BUILD_CHUNK"); if (e && atoll(e) > 0 && (uint64_t)atoll(e) < CH) CH = (uint64_t)atoll(e); }   /* test hook: several launches per segment */
     if (!dispatch_w(S->W, [](auto) {}) || (S->I != 2 && S->I != 4)) return UTREE_E_ARG;
     HK(hipSetDevice(S->device));
     if (dmalloc(&d_ix, n_u) || dmalloc(&d_cnt, n_labels) || dmalloc(&d_out, CH * rec)) { rc = UTREE_E_NOMEM; goto fail; }

@@ -94,7 +94,8 @@ int utree_compress_file(const char *ubt_path, const char *ctr_path, int device, 
     fo = open(ctr_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
     if (fo < 0) { close(fd); return UTREE_E_IO; }                             /* "Invalid output filename", itree.c:1299 */
     if (hipSetDevice(device) != hipSuccess) { rc = UTREE_E_HIP; goto done; }
-    const size_t chunk = ((size_t)32 << 20) / DR;                             /* records per chunk */
+    size_t chunk = ((size_t)32 << 20) / DR;                                   /* records per chunk */
+    { const char *e = getenv("UTREE_TEST_COMPRESS_CHUNK"); if (e && atoll(e) > 0 && (size_t)atoll(e) < chunk) chunk = (size_t)atoll(e); }   /* test hook: many chunks of a small file */
     for (int i = 0; i < 2; ++i) {
         HIPC(hipHostMalloc(&h_in[i], chunk * DR, hipHostMallocDefault));
         HIPC(hipHostMalloc(&h_out[i], chunk * SZ, hipHostMallocDefault));
