@@ -219,6 +219,40 @@ def test_four_streams_meet_2000_new_ids_at_once(torch_cuda):
     smp.close()
 
 
+@pytest.mark.parametrize("deal", ["sevenths", "runs_1024", "runs_64", "round_robin"])
+def test_several_workgroups_and_rounds(torch_cuda, deal):
+    """20 011 records: two workgroups of 10 006 (the second starts in the middle of a run, not on a multiple of 64), three rounds of 4096 each, a
+    partial last wavefront.  Long runs of one id: a run's boundary inside a wavefront, and the id a thread had 1024 records before is its id again (sevenths);
+    that id is always another sample's (runs_1024); every boundary at lane 0 (runs_64); every lane begins a run (round_robin)."""
+    torch = torch_cuda
+    db, tree = tree_for("toy")
+    n, n_ids = 20_011, 7
+    r = np.arange(n)
+    which = {"sevenths": r * n_ids // n, "runs_1024": r // 1024 % n_ids, "runs_64": r // 64 % n_ids, "round_robin": r % n_ids}[deal]
+    idt = [b"smp%d%s" % (i, b"x" * (i % 3)) for i in range(n_ids)]
+    rng = np.random.default_rng(33)
+    cut = rng.integers(0, 10, n)
+    found = (rng.random(n) < 0.8).astype(np.int32)
+    names = [idt[w] + b"_%d" % k for k, w in enumerate(which.tolist())]
+    ln = np.array([len(x) for x in names], dtype=np.int32)
+    off = (np.concatenate([[0], np.cumsum(ln[:-1] + 1)]) + 1).astype(np.int32)
+    res = np.zeros((n, 6), dtype=np.int32)
+    res[:, 0], res[:, 1], res[:, 2] = 0, cut, found
+    smp = tree.samples(16, 256)
+    smp.add(*to_dev(torch, b">" + b">".join(names), off, ln, res))
+    rb = smp.read()
+    assert rb.n_reads == n and sorted(rb.ids) == sorted(idt)                                   # every id once
+    col = {s: j for j, s in enumerate(rb.ids)}
+    pos = np.array([col[s] for s in idt])[which]
+    assert np.array_equal(rb.reads, np.bincount(pos, minlength=n_ids).astype(np.uint64))
+    assert np.array_equal(rb.unclassified, np.bincount(pos[found == 0], minlength=n_ids).astype(np.uint64))
+    want = np.bincount(pos[found == 1] * 16 + cut[found == 1], minlength=16 * n_ids)
+    got = np.zeros(16 * n_ids, dtype=np.int64)
+    np.add.at(got, rb.cells["sample"].astype(np.int64) * 16 + rb.cells["cut"], rb.cells["reads"].astype(np.int64))
+    assert np.array_equal(got, want) and (rb.cells["label"] == 0).all() and len(rb.cells) == int((want > 0).sum())
+    smp.close()
+
+
 # ---- 4. capacities -----------------------------------------------------------------------------------------------------------------------
 def test_capacities_by_hand(torch_cuda):
     torch = torch_cuda

@@ -101,7 +101,7 @@ def main():
     res["samples_add"] = {}
     for tag, n_samples, shuffled in (("96_blocks", 96, False), ("96_shuffled", 96, True), ("10000_shuffled", 10000, True)):
         text = names_tensor(torch, sample_of(torch, n, n_samples, shuffled, dev), dev).view(-1)
-        smp = sdb.tree.samples()
+        smp = sdb.tree.samples(1 << 16, 1 << 25)                                                  # (10 000 samples: millions of cells)
         first = event_ms(lambda: smp.add(text, name_off, name_len, out))                          # into an empty handle: every id is claimed
         ms = [event_ms(lambda: smp.add(text, name_off, name_len, out)) for _ in range(args.repeats)]
         rb = smp.read()

@@ -93,12 +93,19 @@ int utree_redist_classify_batch(utree_redist *rd, utree_dev *dev, const uint8_t 
 }
 
 /* the handle's error word as a code and a text */
+void utree_redist_flags_text(unsigned long long f, const char *lead, const char *sep, char *msg, size_t cap) {
+    snprintf(msg, cap, "%s%s%s%s%s%s%s%s", f & UTK_REDIST_F_TABLE ? lead : "",
+             f & UTK_REDIST_F_TABLE ? "the table of candidate sets was too small (raise UTREE_REDIST_CAPACITY)" : "", f & UTK_REDIST_F_TABLE ? sep : "",
+             f & UTK_REDIST_F_ARENA ? lead : "",
+             f & UTK_REDIST_F_ARENA ? "the arena of the sets' labels was too small (raise UTREE_REDIST_CAPACITY)" : "", f & UTK_REDIST_F_ARENA ? sep : "",
+             f & UTK_REDIST_F_LABEL ? lead : "", f & UTK_REDIST_F_LABEL ? "a record named a label the database does not have" : "");
+}
+
 static int check_flags(unsigned long long f) {
     if (!f) return UTREE_OK;
     char msg[320];
-    snprintf(msg, sizeof msg, "redistribution: %s%s%s", f & UTK_REDIST_F_TABLE ? "the table of candidate sets was too small (raise UTREE_REDIST_CAPACITY) " : "",
-             f & UTK_REDIST_F_ARENA ? "the arena of the sets' labels was too small (raise UTREE_REDIST_CAPACITY) " : "",
-             f & UTK_REDIST_F_LABEL ? "a record named a label the database does not have" : "");
+    const int at = snprintf(msg, sizeof msg, "redistribution: ");
+    utree_redist_flags_text(f, "", " ", msg + at, sizeof msg - at);
     utree_set_error_text(msg);
     return UTREE_E_DEVICE;
 }

@@ -12,6 +12,8 @@ extern "C" {
 #define UTK_REDIST_F_ARENA 2ull               /* ... the arena is used up */
 #define UTK_REDIST_F_LABEL 4ull               /* ... a record named a label the database does not have */
 #define UTK_REDIST_MISC_WORDS 8u              /* d_misc: {reads, error word, arena cursor, changes, ambiguous reads, -, -, -} */
+/* the error word in words (redist.c): `lead` in front of every phrase, `sep` behind every one but the last of the three */
+void utree_redist_flags_text(unsigned long long f, const char *lead, const char *sep, char *msg, size_t cap);
 
 /* The device side of a handle.  A slot is {key, reads}: key = arena offset << 32 | labels of the set (>= 2), 0 while free; the set's labels are
  * file-order indices at arena[offset ..], complete before the key is published.  single[l] = reads whose only candidate is l. */

@@ -1,5 +1,6 @@
 // redist_dev.hpp -- the device side of the table of candidate sets (redist.h: utk_redist_tab), shared by redist_kernels.hip and
-// sredist_kernels.hip: the tied maximum of a read's (rank, count) list as a sequence of labels, and the insert of such a sequence.
+// sredist_kernels.hip: the scans of a read's (rank, count) list for its tied maximum (rd_scan_listed, rd_scan_tied), that maximum as a sequence
+// of labels, and the insert of such a sequence.
 //
 // Insert: probe read-only and compare WHOLE sets (a hash alone would merge two sets silently); only on a miss write the labels to freshly
 // reserved arena space and claim the free slot with one compare-and-swap of the key (release: the labels are visible before the key).  Whoever
@@ -17,6 +18,7 @@
 #define RD_NO_SLOT 0xFFFFFFFFu             // rd_insert: the set found no slot (the error word says why)
 #define RD_CUT_PENDING (-3)                // as in kernels.hip (vote_k finishes those records)
 #define RD_RANK_PENDING (-4)
+#define RD_UNROLL 4                        // queued reads a thread scans side by side (rd_scan_listed)
 
 __device__ __forceinline__ void rd_add(unsigned long long *p, unsigned long long v) {
     (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -46,6 +48,77 @@ struct FlatSeq {
     __device__ void reset() { pos = 0; }
     __device__ uint32_t next() { return p[pos++]; }
 };
+
+// RD_UNROLL queued reads per thread -- queue entries first, first + BLOCK, ... below qn --, each with a (rank, count) list whose tied maximum is
+// its candidate set.  The four reads' records, list entries and index look-ups are requested side by side: every step of one read's chain is a
+// dependent load, and most listed reads end as a single candidate (one label has the most hits), so the loads are the cost.
+//   decode(i, r, tag)   queue entry i -> the read's record index and whatever else the sinks want of it
+//   one(tag, c)         the read's only candidate is the file-order index c (~0: a rank the database does not have)
+//   many(r, tag)        it has several: onto the second queue
+template <uint32_t BLOCK, class DECODE, class ONE, class MANY>
+__device__ __forceinline__ void rd_scan_listed(const utk_redist_tab &t, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
+                                               const uint64_t *__restrict__ tally, uint32_t first, uint32_t qn, DECODE decode, ONE one, MANY many) {
+    const uint32_t nl = t.n_labels;
+    uint32_t uix[RD_UNROLL], mx[RD_UNROLL], ties[RD_UNROLL], k0[RD_UNROLL], rr[RD_UNROLL], tag[RD_UNROLL], umax = 0;
+    const uint64_t *T[RD_UNROLL];
+#pragma unroll
+    for (int u = 0; u < RD_UNROLL; ++u) {
+        const uint32_t i = first + (uint32_t)u * BLOCK;
+        uix[u] = 0; T[u] = tally; mx[u] = 0; ties[u] = 0; k0[u] = 0; rr[u] = 0; tag[u] = 0;
+        if (i < qn) {
+            decode(i, rr[u], tag[u]);
+            const uint32_t *rec = (const uint32_t *)&res[rr[u]];
+            uix[u] = rec[3];
+            T[u] = tally + ((uint64_t)rec[4] | ((uint64_t)rec[5] << 32));
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < RD_UNROLL; ++u) umax = uix[u] > umax ? uix[u] : umax;
+    for (uint32_t i = 0; i < umax; ++i) {
+        uint64_t e[RD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < RD_UNROLL; ++u) e[u] = i < uix[u] ? T[u][i] : 0ull;
+#pragma unroll
+        for (int u = 0; u < RD_UNROLL; ++u) {
+            if (i >= uix[u]) continue;
+            const uint32_t c = (uint32_t)(e[u] >> 32), rk = (uint32_t)e[u];
+            if (c > mx[u]) { mx[u] = c; ties[u] = 1; k0[u] = rk; }
+            else if (c == mx[u]) ++ties[u];
+        }
+    }
+    uint32_t c0[RD_UNROLL];
+#pragma unroll
+    for (int u = 0; u < RD_UNROLL; ++u) c0[u] = ties[u] == 1 && k0[u] < nl ? rank2ix[k0[u]] : 0xFFFFFFFFu;
+#pragma unroll
+    for (int u = 0; u < RD_UNROLL; ++u) {
+        if (first + (uint32_t)u * BLOCK >= qn) continue;
+        if (!ties[u] || !mx[u]) { rd_flag(t, UTK_REDIST_F_LABEL); continue; }       // (an empty list: the classify kernels write none; never dropped silently)
+        if (ties[u] == 1) one(tag[u], c0[u]);
+        else many(rr[u], tag[u]);                                                   // several candidates: the table, with full wavefronts
+    }
+}
+
+// the list of record r scanned once more, its tied maximum into `seq`; returns how many are tied (below 2: `seq` is not set)
+__device__ __forceinline__ uint32_t rd_scan_tied(const utk_redist_tab &t, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
+                                                 const uint64_t *__restrict__ tally, uint32_t r, TiedSeq &seq) {
+    const uint32_t *rec = (const uint32_t *)&res[r];
+    const uint32_t uix = rec[3], nl = t.n_labels;
+    const uint64_t *T = tally + ((uint64_t)rec[4] | ((uint64_t)rec[5] << 32));
+    uint32_t mx = 0, ties = 0, k0 = 0, k1 = 0, k2 = 0, k3 = 0, pos4 = 0;
+    for (uint32_t i = 0; i < uix; ++i) {
+        const uint64_t e = T[i];
+        const uint32_t c = (uint32_t)(e >> 32), rk = (uint32_t)e;
+        if (c > mx) { mx = c; ties = 1; k0 = rk; }
+        else if (c == mx) {
+            if (ties == 1) k1 = rk; else if (ties == 2) k2 = rk; else if (ties == 3) { k3 = rk; pos4 = i + 1; }
+            ++ties;
+        }
+    }
+    if (ties < 2) return ties;
+    seq = {T, rank2ix, mx, uix, nl, k0 < nl ? rank2ix[k0] : 0xFFFFFFFFu, k1 < nl ? rank2ix[k1] : 0xFFFFFFFFu,
+           ties > 2 && k2 < nl ? rank2ix[k2] : 0xFFFFFFFFu, ties > 3 && k3 < nl ? rank2ix[k3] : 0xFFFFFFFFu, pos4, 0, 0};
+    return ties;
+}
 
 // `reads` reads whose candidate set is the n (>= 2) labels of `seq`; returns the set's slot, RD_NO_SLOT when it has none
 template <class SEQ>

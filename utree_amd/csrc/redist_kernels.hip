@@ -24,7 +24,6 @@
 
 #define RD_TILE 4096u                      // reads a workgroup takes per round = the capacity of its queue of listed reads
 #define RD_Q2 8192u                        // capacity of its queue of reads with several candidates, emptied when a further round might not fit
-#define RD_UNROLL 4
 struct RdLds { uint32_t dense[RD_DENSE]; uint32_t q[RD_TILE]; uint32_t q2[RD_Q2]; uint32_t qn, q2n; };
 
 __device__ __forceinline__ void rd_single(const utk_redist_tab &t, RdLds &s, uint32_t n_dense, uint32_t one) {
@@ -33,70 +32,21 @@ __device__ __forceinline__ void rd_single(const utk_redist_tab &t, RdLds &s, uin
     else rd_add(t.single + one, 1ull);
 }
 
-// RD_UNROLL queued reads per thread, each with a (rank, count) list whose tied maximum is its candidate set.  The four reads' records, list
-// entries and index look-ups are requested side by side: every step of one read's chain is a dependent load, and most listed reads end as
-// a single candidate (one label has the most hits), so the loads are the cost.
+// RD_UNROLL queued reads per thread (redist_dev.hpp: rd_scan_listed): one candidate is counted, several go on the second queue
 __device__ void rd_listed(const utk_redist_tab &t, RdLds &s, uint32_t n_dense, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
                           const uint64_t *__restrict__ tally, uint32_t first, uint32_t qn) {
-    const uint32_t nl = t.n_labels;
-    uint32_t uix[RD_UNROLL], mx[RD_UNROLL], ties[RD_UNROLL], k0[RD_UNROLL], rr[RD_UNROLL], umax = 0;
-    const uint64_t *T[RD_UNROLL];
-#pragma unroll
-    for (int u = 0; u < RD_UNROLL; ++u) {
-        const uint32_t i = first + (uint32_t)u * RD_BLOCK;
-        uix[u] = 0; T[u] = tally; mx[u] = 0; ties[u] = 0; k0[u] = 0; rr[u] = 0;
-        if (i < qn) {
-            rr[u] = s.q[i];
-            const uint32_t *rec = (const uint32_t *)&res[rr[u]];
-            uix[u] = rec[3];
-            T[u] = tally + ((uint64_t)rec[4] | ((uint64_t)rec[5] << 32));
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < RD_UNROLL; ++u) umax = uix[u] > umax ? uix[u] : umax;
-    for (uint32_t i = 0; i < umax; ++i) {
-        uint64_t e[RD_UNROLL];
-#pragma unroll
-        for (int u = 0; u < RD_UNROLL; ++u) e[u] = i < uix[u] ? T[u][i] : 0ull;
-#pragma unroll
-        for (int u = 0; u < RD_UNROLL; ++u) {
-            if (i >= uix[u]) continue;
-            const uint32_t c = (uint32_t)(e[u] >> 32), rk = (uint32_t)e[u];
-            if (c > mx[u]) { mx[u] = c; ties[u] = 1; k0[u] = rk; }
-            else if (c == mx[u]) ++ties[u];
-        }
-    }
-    uint32_t c0[RD_UNROLL];
-#pragma unroll
-    for (int u = 0; u < RD_UNROLL; ++u) c0[u] = ties[u] == 1 && k0[u] < nl ? rank2ix[k0[u]] : 0xFFFFFFFFu;
-#pragma unroll
-    for (int u = 0; u < RD_UNROLL; ++u) {
-        if (first + (uint32_t)u * RD_BLOCK >= qn) continue;
-        if (!ties[u] || !mx[u]) { rd_flag(t, UTK_REDIST_F_LABEL); continue; }       // (an empty list: the classify kernels write none; never dropped silently)
-        if (ties[u] == 1) rd_single(t, s, n_dense, c0[u]);
-        else s.q2[atomicAdd(&s.q2n, 1u)] = rr[u];                                   // several candidates: the table, with full wavefronts (below)
-    }
+    rd_scan_listed<RD_BLOCK>(t, rank2ix, res, tally, first, qn,
+                             [&](uint32_t i, uint32_t &r, uint32_t &) { r = s.q[i]; },
+                             [&](uint32_t, uint32_t one) { rd_single(t, s, n_dense, one); },
+                             [&](uint32_t r, uint32_t) { s.q2[atomicAdd(&s.q2n, 1u)] = r; });
 }
 
 // a queued read with several candidates: its set into the table
 __device__ void rd_multi(const utk_redist_tab &t, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
                          const uint64_t *__restrict__ tally, uint32_t r) {
-    const uint32_t *rec = (const uint32_t *)&res[r];
-    const uint32_t uix = rec[3], nl = t.n_labels;
-    const uint64_t *T = tally + ((uint64_t)rec[4] | ((uint64_t)rec[5] << 32));
-    uint32_t mx = 0, ties = 0, k0 = 0, k1 = 0, k2 = 0, k3 = 0, pos4 = 0;
-    for (uint32_t i = 0; i < uix; ++i) {
-        const uint64_t e = T[i];
-        const uint32_t c = (uint32_t)(e >> 32), rk = (uint32_t)e;
-        if (c > mx) { mx = c; ties = 1; k0 = rk; }
-        else if (c == mx) {
-            if (ties == 1) k1 = rk; else if (ties == 2) k2 = rk; else if (ties == 3) { k3 = rk; pos4 = i + 1; }
-            ++ties;
-        }
-    }
+    TiedSeq seq;
+    const uint32_t ties = rd_scan_tied(t, rank2ix, res, tally, r, seq);
     if (ties < 2) { rd_flag(t, UTK_REDIST_F_LABEL); return; }     // (rd_listed queued it for having more: never dropped silently)
-    TiedSeq seq = {T, rank2ix, mx, uix, nl, k0 < nl ? rank2ix[k0] : 0xFFFFFFFFu, k1 < nl ? rank2ix[k1] : 0xFFFFFFFFu,
-                   ties > 2 && k2 < nl ? rank2ix[k2] : 0xFFFFFFFFu, ties > 3 && k3 < nl ? rank2ix[k3] : 0xFFFFFFFFu, pos4, 0, 0};
     rd_insert(t, seq, ties, 1ull);
 }
 

@@ -1,5 +1,6 @@
 // samples_dev.hpp -- the device side of the table of sample ids and of the {key, reads} cell table (samples.h: utk_samples_tab), shared by
-// samples_kernels.hip and sredist_kernels.hip.
+// samples_kernels.hip and sredist_kernels.hip: the intern of an id, a batch's names resolved to sample slots a wavefront at a time (sm_resolve),
+// a workgroup's hash table of cells in LDS (SmCells) and the add to the cell table behind it.
 //
 // Interning takes over redist_dev.hpp's insert, which has no lane waiting for another: probe read-only and compare WHOLE ids; on a miss
 // write the bytes to arena space reserved with one atomic and claim the free slot with one compare-and-swap (release); whoever loses that race
@@ -15,6 +16,7 @@
 #define SM_KEY_FREE (~0ull)                // an unused cell slot (and "no run yet")
 #define SM_ID_FREE 0ull                    // an unused id slot: a key's low word is the id's length + 1
 #define SM_NONE 0xFFFFFFFFu                // no sample: the error word says why
+#define SM_LDS_PROBES 32u
 
 __device__ __forceinline__ uint64_t sm_mix(uint64_t k) {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
@@ -76,6 +78,39 @@ __device__ uint32_t sm_intern(const utk_samples_tab &t, const uint8_t *__restric
     return SM_NONE;
 }
 
+// The id a thread resolved one round before, and its slot: a combined file is a concatenation of samples, so it is most often this round's too.
+struct SmPrev { uint32_t off = 0, idl = 0, slot = SM_NONE; bool ok = false; };
+
+// The sample slot of one record per lane: the name is text[off .. off + nlen) (`ok`: the lane has a record), its id the bytes in front of the
+// last delimiter.  A lane compares its id with its predecessor lane's (length, then bytes) and then with `pv`'s; only a lane that begins a run in
+// both senses goes to the table, and the lanes behind it take its slot from a wavefront shuffle.  False: no record, or a name outside the text
+// (UTK_SAMPLES_F_NAME into `flags`); `slot` may still be SM_NONE for a record (the table flagged why).
+// EVERY lane of the workgroup calls this the same number of times, records or not: the shuffles and the ballot need whole wavefronts.
+__device__ __forceinline__ bool sm_resolve(const utk_samples_tab &t, const uint8_t *__restrict__ text, uint64_t text_bytes, uint32_t off, uint32_t nlen,
+                                           bool ok, uint32_t lane, SmPrev &pv, uint32_t &flags, uint32_t &slot) {
+    bool valid = ok;
+    if (valid && ((uint64_t)off > text_bytes || (uint64_t)nlen > text_bytes - off)) { flags |= (uint32_t)UTK_SAMPLES_F_NAME; valid = false; }
+    const uint8_t *id = text + (valid ? off : 0u);
+    const uint32_t idl = valid ? sm_id_len(id, nlen, t.delim) : 0u;
+    // the predecessor in record order is the lane below
+    const uint32_t p_off = (uint32_t)__shfl_up((int)off, 1), p_idl = (uint32_t)__shfl_up((int)idl, 1);
+    const int p_valid = __shfl_up((int)valid, 1);
+    bool head = valid;
+    if (valid && lane > 0 && p_valid && p_idl == idl && sm_same(id, text + p_off, idl)) head = false;
+    slot = SM_NONE;
+    if (head) {
+        if (pv.ok && pv.idl == idl && sm_same(id, text + pv.off, idl)) slot = pv.slot;
+        else slot = sm_intern(t, id, idl);
+    }
+    // every lane takes the slot of the nearest head at or below it (a valid lane 0 is one; lanes beyond the batch's end follow no valid lane)
+    const uint64_t heads = __ballot(head);
+    const uint64_t below = heads & ((2ull << lane) - 1ull);
+    const int src = below ? 63 - __clzll((long long)below) : (int)lane;
+    slot = (uint32_t)__shfl((int)slot, src);
+    if (valid) { pv.off = off; pv.idl = idl; pv.slot = slot; pv.ok = true; }
+    return valid;
+}
+
 // cnt reads into the slot of the cell table that holds `key` (never all ones), claimed when no slot holds it yet; the full flag when there is none
 __device__ void sm_cell_add(const utk_samples_tab &t, uint64_t key, unsigned long long cnt) {
     const uint32_t h = (uint32_t)sm_mix(key);
@@ -92,5 +127,36 @@ __device__ void sm_cell_add(const utk_samples_tab &t, uint64_t key, unsigned lon
     }
     sm_flag(t, UTK_SAMPLES_F_CELLS);
 }
+
+// A workgroup's hash table of cells in LDS: counts gather here and leave for the device tables once, at the end.  SINK (key, cnt) is what takes a
+// count to the device tables -- one that found no room within the probe limit, and every non-zero slot in flush.
+template <uint32_t SLOTS>
+struct SmCells {
+    unsigned long long key[SLOTS];
+    uint32_t cnt[SLOTS];
+    __device__ __forceinline__ void init(uint32_t tid, uint32_t block) {              // (a barrier before the first add)
+        for (uint32_t i = tid; i < SLOTS; i += block) { key[i] = SM_KEY_FREE; cnt[i] = 0; }
+    }
+    template <class SINK>
+    __device__ __forceinline__ void add(uint64_t k0, uint32_t n, SINK sink) {
+        if (!n) return;
+        const uint32_t h = (uint32_t)sm_mix(k0);
+        for (uint32_t p = 0; p < SM_LDS_PROBES; ++p) {
+            const uint32_t i = (h + p) & (SLOTS - 1);
+            unsigned long long k = key[i];
+            if (k == SM_KEY_FREE) {
+                k = atomicCAS(&key[i], SM_KEY_FREE, (unsigned long long)k0);
+                if (k == SM_KEY_FREE) k = k0;
+            }
+            if (k == k0) { atomicAdd(&cnt[i], n); return; }
+        }
+        sink(k0, n);
+    }
+    template <class SINK>
+    __device__ __forceinline__ void flush(uint32_t tid, uint32_t block, SINK sink) {  // (a barrier after the last add)
+        for (uint32_t i = tid; i < SLOTS; i += block)
+            if (key[i] != SM_KEY_FREE && cnt[i]) sink(key[i], cnt[i]);
+    }
+};
 
 #endif

@@ -11,9 +11,8 @@
 // Interning takes over redist_kernels.hip's insert, which has no lane waiting for another: probe read-only and compare WHOLE ids; on a miss
 // write the bytes to arena space reserved with one atomic and claim the free slot with one compare-and-swap (release); whoever loses that race
 // compares against the winner's bytes -- complete, they were written before the claim -- and probes on, keeping its copy for the next free
-// slot.  A combined file is a concatenation of samples, so ids arrive in long runs: a lane first compares its id with its predecessor lane's
-// (length, then bytes) and then with the one it had 1024 records before; only a lane that begins a run in both senses goes to the table, and the
-// lanes behind it take its slot from a wavefront shuffle.
+// slot.  A combined file is a concatenation of samples, so ids arrive in long runs: only a lane whose id differs from its predecessor lane's and
+// from the one it had 1024 records before goes to the table (samples_dev.hpp: sm_resolve).
 //
 // Counting is profile_add_k's: one workgroup per CU, a hash table of cells in LDS, runs of equal keys carried in registers, and at the end one
 // no-return atomic per non-zero LDS slot into the device tables.  Unclassified reads are a cell of their own in LDS only (cut =
@@ -27,7 +26,6 @@
 
 #define SM_BLOCK 1024
 #define SM_HSLOTS 8192u                    // LDS hash slots: 64 KiB of keys + 32 KiB of counts
-#define SM_LDS_PROBES 32u
 #define SM_UNROLL 4
 
 __device__ __forceinline__ uint64_t sm_key(uint32_t slot, uint32_t label, uint32_t cut16) {
@@ -43,31 +41,19 @@ __device__ void sm_global_add(const utk_samples_tab &t, uint64_t key, uint32_t c
 }
 
 struct SmLds {
-    unsigned long long key[SM_HSLOTS];
-    uint32_t cnt[SM_HSLOTS];
+    SmCells<SM_HSLOTS> cells;
     uint32_t flags;
 };
 
 __device__ void sm_lds_add(SmLds &s, const utk_samples_tab &t, uint64_t key, uint32_t cnt) {
-    if (!cnt) return;
-    const uint32_t h = (uint32_t)sm_mix(key);
-    for (uint32_t p = 0; p < SM_LDS_PROBES; ++p) {
-        const uint32_t i = (h + p) & (SM_HSLOTS - 1);
-        unsigned long long k = s.key[i];
-        if (k == SM_KEY_FREE) {
-            k = atomicCAS(&s.key[i], SM_KEY_FREE, (unsigned long long)key);
-            if (k == SM_KEY_FREE) k = key;
-        }
-        if (k == key) { atomicAdd(&s.cnt[i], cnt); return; }
-    }
-    sm_global_add(t, key, cnt);
+    s.cells.add(key, cnt, [&](uint64_t k, uint32_t c) { sm_global_add(t, k, c); });
 }
 
 __global__ void __launch_bounds__(SM_BLOCK) samples_add_k(utk_samples_tab t, const uint8_t *__restrict__ text, uint64_t text_bytes,
                                                           const uint32_t *__restrict__ name_off, const uint32_t *__restrict__ name_len,
                                                           const utree_result *__restrict__ res, uint32_t n, uint32_t per_block) {
     __shared__ SmLds s;
-    for (uint32_t i = threadIdx.x; i < SM_HSLOTS; i += SM_BLOCK) { s.key[i] = SM_KEY_FREE; s.cnt[i] = 0; }
+    s.cells.init(threadIdx.x, SM_BLOCK);
     if (threadIdx.x == 0) s.flags = 0;
     __syncthreads();
 
@@ -76,9 +62,8 @@ __global__ void __launch_bounds__(SM_BLOCK) samples_add_k(utk_samples_tab t, con
     const uint32_t lane = threadIdx.x & 63u;
     uint64_t run = SM_KEY_FREE;
     uint32_t run_n = 0, flags = 0;
-    uint32_t pv_off = 0, pv_idl = 0, pv_slot = SM_NONE;    // the id this thread had one round before, and its slot
-    bool pv_ok = false;
-    for (uint64_t b0 = begin; b0 < end; b0 += (uint64_t)SM_UNROLL * SM_BLOCK) {       // (the same trips in every lane: the shuffles below need them all)
+    SmPrev pv;
+    for (uint64_t b0 = begin; b0 < end; b0 += (uint64_t)SM_UNROLL * SM_BLOCK) {       // (the same trips in every lane: sm_resolve needs them all)
         uint32_t off[SM_UNROLL], nlen[SM_UNROLL], lab[SM_UNROLL], fnd[SM_UNROLL];
         int32_t cut[SM_UNROLL];
         bool ok[SM_UNROLL];
@@ -90,26 +75,8 @@ __global__ void __launch_bounds__(SM_BLOCK) samples_add_k(utk_samples_tab t, con
         }
 #pragma unroll
         for (int u = 0; u < SM_UNROLL; ++u) {
-            bool valid = ok[u];
-            if (valid && ((uint64_t)off[u] > text_bytes || (uint64_t)nlen[u] > text_bytes - off[u])) { flags |= (uint32_t)UTK_SAMPLES_F_NAME; valid = false; }
-            const uint8_t *id = text + (valid ? off[u] : 0u);
-            const uint32_t idl = valid ? sm_id_len(id, nlen[u], t.delim) : 0u;
-            // the predecessor in record order is the lane below
-            const uint32_t p_off = (uint32_t)__shfl_up((int)off[u], 1), p_idl = (uint32_t)__shfl_up((int)idl, 1);
-            const int p_valid = __shfl_up((int)valid, 1);
-            bool head = valid;
-            if (valid && lane > 0 && p_valid && p_idl == idl && sm_same(id, text + p_off, idl)) head = false;
-            uint32_t slot = SM_NONE;
-            if (head) {
-                if (pv_ok && pv_idl == idl && sm_same(id, text + pv_off, idl)) slot = pv_slot;
-                else slot = sm_intern(t, id, idl);
-            }
-            // every lane takes the slot of the nearest head at or below it (a valid lane 0 is one; lanes beyond the batch's end follow no valid lane)
-            const uint64_t heads = __ballot(head);
-            const uint64_t below = heads & ((2ull << lane) - 1ull);
-            const int src = below ? 63 - __clzll((long long)below) : (int)lane;
-            slot = (uint32_t)__shfl((int)slot, src);
-            if (valid) { pv_off = off[u]; pv_idl = idl; pv_slot = slot; pv_ok = true; }
+            uint32_t slot;
+            const bool valid = sm_resolve(t, text, text_bytes, off[u], nlen[u], ok[u], lane, pv, flags, slot);
             if (valid && slot != SM_NONE) {
                 uint64_t key = SM_KEY_FREE;
                 if (!fnd[u] || cut[u] == -4) key = sm_key(slot, 0, UTK_SAMPLES_CUT_UNCL);
@@ -128,8 +95,7 @@ __global__ void __launch_bounds__(SM_BLOCK) samples_add_k(utk_samples_tab t, con
     if (flags) atomicOr(&s.flags, flags);
     __syncthreads();
 
-    for (uint32_t i = threadIdx.x; i < SM_HSLOTS; i += SM_BLOCK)
-        if (s.key[i] != SM_KEY_FREE && s.cnt[i]) sm_global_add(t, s.key[i], s.cnt[i]);
+    s.cells.flush(threadIdx.x, SM_BLOCK, [&](uint64_t k, uint32_t c) { sm_global_add(t, k, c); });
     if (threadIdx.x == 0) {
         if (blockIdx.x == 0) sm_add(t.misc + 0, n);
         if (s.flags) sm_flag(t, s.flags);

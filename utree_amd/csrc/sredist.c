@@ -1,10 +1,11 @@
 /* sredist.c -- ambiguous reads redistributed per sample of a multiplexed file (include/utree_amd.h: utree_sredist_*).
  *
- * The handle keeps, on the device and for a whole search, the id table of a sample table (samples.c), the table of multi-label candidate sets
+ * The handle keeps, on the device and for a whole search, the id table of a sample table (sample_ids.c), the table of multi-label candidate sets
  * of a redistribution (redist.c) and a cell table keyed (sample, candidate set), fed by one pass per batch between the classify kernels and
  * the vote (sredist_kernels.hip).  Here: the handle, the read-back into a flat form, its insert (and so the merge of two handles), the solver's
  * host side -- every sample's labels renumbered in ascending file-order index into one flat tally, so that 65 536 samples x 1 M labels cost
- * what occurs and the tie-break survives; the passes run on the device, a stopped sample's tally frozen -- and the host-only writer.
+ * what occurs and the tie-break survives; the passes run on the device, a stopped sample's tally frozen -- and the host-only writer's checks
+ * (the matrix itself: taxon_table.c).
  */
 #define _GNU_SOURCE
 #define __HIP_PLATFORM_AMD__ 1
@@ -14,72 +15,40 @@
 #include <string.h>
 #include "ctr_host.h"
 #include "dev_image.h"
+#include "sample_ids.h"
 #include "sredist.h"
+#include "taxon_table.h"
 
 struct utree_sredist {
     int device, n_cu;
-    uint32_t id_slots, cell_slots, n_labels;
-    uint8_t *d_mem;                     /* ids | reads | uncl | cells | misc | index | arena, as samples.c lays them out */
-    size_t bytes, counters_bytes;       /* counters_bytes: everything in front of the arena */
-    utk_sredist_tab tab;                /* r.slots, r.arena, r.misc: allocations of their own */
+    uint32_t n_labels;
+    utk_sredist_tab tab;                /* s: one device block (sample_ids.c); r.slots, r.arena, r.misc: allocations of their own */
 };
 
 #define CHK(x) do { if ((x) != hipSuccess) { utree_dev_set_hip_error((int)hipGetLastError(), #x); rc = UTREE_E_HIP; goto fail; } } while (0)
 
-static int check_flags(unsigned long long fs, unsigned long long fr) {
-    if (!fs && !fr) return UTREE_OK;
-    char msg[900];
-    snprintf(msg, sizeof msg, "sample redistribution:%s%s%s%s%s%s%s",
-             fs & UTK_SAMPLES_F_TABLE ? " more distinct sample ids than the table holds (raise UTREE_SAMPLE_CAPACITY; is the delimiter right?);" : "",
-             fs & UTK_SAMPLES_F_ARENA ? " the arena of id bytes is used up (raise UTREE_SAMPLE_CAPACITY; is the delimiter right?);" : "",
-             fs & UTK_SAMPLES_F_CELLS ? " the table of (sample, candidate set) cells is full (raise UTREE_SAMPLE_CELLS);" : "",
-             fs & UTK_SAMPLES_F_NAME ? " a name lies outside its chunk, or a cell names no sample;" : "",
-             fr & UTK_REDIST_F_TABLE ? " the table of candidate sets was too small (raise UTREE_REDIST_CAPACITY);" : "",
-             fr & UTK_REDIST_F_ARENA ? " the arena of the sets' labels was too small (raise UTREE_REDIST_CAPACITY);" : "",
-             fr & UTK_REDIST_F_LABEL ? " a record named a label the database does not have;" : "");
-    const size_t l = strlen(msg);
-    if (l && msg[l - 1] == ';') msg[l - 1] = 0;
-    utree_set_error_text(msg);
-    return UTREE_E_DEVICE;
-}
+static const utree_sample_ids_text TEXT = {"sample redistribution", "tables", "the table of (sample, candidate set) cells is full (raise UTREE_SAMPLE_CELLS)",
+                                           "a name lies outside its chunk, or a cell names no sample"};
 
 int utree_sredist_create(utree_dev *dev, uint32_t sample_capacity, uint32_t set_capacity, uint32_t cell_capacity, int delim, utree_sredist **out) {
     if (!dev || !out) return UTREE_E_ARG;
     *out = NULL;
-    if (!sample_capacity || sample_capacity > (1u << (UTK_SAMPLES_SLOT_BITS - 1)) || !set_capacity || set_capacity > (1u << 28) || !cell_capacity ||
-        cell_capacity > (1u << 30)) return UTREE_E_ARG;
-    if (delim < 0 || delim > 255 || delim == '\t' || delim == ' ' || delim == '\r' || delim == '\n') return UTREE_E_ARG;
-    if (dev->hdr.n_labels >= (1ull << 28)) return UTREE_E_UNSUPPORTED;            /* a set handle has 28 bits for the label */
+    if (!set_capacity || set_capacity > (1u << 28)) return UTREE_E_ARG;
     utree_sredist *h = (utree_sredist *)calloc(1, sizeof *h);
     if (!h) return UTREE_E_NOMEM;
     h->device = dev->device; h->n_cu = dev->n_cu; h->n_labels = (uint32_t)dev->hdr.n_labels;
-    h->id_slots = 16; h->cell_slots = 16;
+    int rc = utree_sample_ids_create(&h->tab.s, h->device, sample_capacity, cell_capacity, delim, dev->hdr.n_labels);
+    if (rc) { free(h); return rc; }
     uint32_t set_slots = 1;
-    while (h->id_slots < 2 * sample_capacity) h->id_slots <<= 1;                  /* at most half full: short probe chains */
-    while (h->cell_slots < cell_capacity) h->cell_slots <<= 1;
     while (set_slots < set_capacity) set_slots <<= 1;
-    uint64_t arena = (uint64_t)sample_capacity * UTK_SAMPLES_ARENA_PER_SAMPLE;
-    if (arena < (1u << 20)) arena = 1u << 20;
-    if (arena > 0xFFFFFF00ull) arena = 0xFFFFFF00ull;                             /* a key holds the offset in 32 bits */
-    const size_t ids = (size_t)h->id_slots * 8, cells = 2 * (size_t)h->cell_slots * 8, misc = UTK_SAMPLES_MISC_WORDS * 8, index = (size_t)h->id_slots * 4;
-    h->counters_bytes = 3 * ids + cells + misc + index;
-    h->bytes = h->counters_bytes + (size_t)arena;
-    utk_samples_tab *t = &h->tab.s;
     utk_redist_tab *r = &h->tab.r;
     r->mask = set_slots - 1; r->n_labels = h->n_labels; r->arena_cap = (uint64_t)set_slots * UTK_REDIST_ARENA_PER_SLOT;
-    if (hipSetDevice(h->device) != hipSuccess) { free(h); return UTREE_E_HIP; }
-    if (hipMalloc((void **)&h->d_mem, h->bytes) != hipSuccess || hipMalloc((void **)&r->slots, (size_t)set_slots * 16) != hipSuccess ||
-        hipMalloc((void **)&r->arena, r->arena_cap * 4) != hipSuccess || hipMalloc((void **)&r->misc, UTK_REDIST_MISC_WORDS * 8) != hipSuccess) {
+    if (hipMalloc((void **)&r->slots, (size_t)set_slots * 16) != hipSuccess || hipMalloc((void **)&r->arena, r->arena_cap * 4) != hipSuccess ||
+        hipMalloc((void **)&r->misc, UTK_REDIST_MISC_WORDS * 8) != hipSuccess) {
         (void)hipGetLastError();
-        utree_sredist_free(h);
-        return UTREE_E_NOMEM;
+        rc = UTREE_E_NOMEM;
     }
-    t->ids = (unsigned long long *)h->d_mem; t->reads = t->ids + h->id_slots; t->uncl = t->reads + h->id_slots;
-    t->cells = t->uncl + h->id_slots; t->misc = t->cells + 2 * (size_t)h->cell_slots;
-    t->index = (uint32_t *)(t->misc + UTK_SAMPLES_MISC_WORDS); t->arena = (uint8_t *)(t->index + h->id_slots);
-    t->arena_cap = arena; t->id_mask = h->id_slots - 1; t->cell_mask = h->cell_slots - 1; t->sample_cap = sample_capacity;
-    t->n_labels = h->n_labels; t->delim = (uint32_t)delim;
-    const int rc = utree_sredist_reset(h);
+    if (!rc) rc = utree_sredist_reset(h);
     if (rc) { utree_sredist_free(h); return rc; }
     *out = h;
     return UTREE_OK;
@@ -88,9 +57,8 @@ int utree_sredist_create(utree_dev *dev, uint32_t sample_capacity, uint32_t set_
 int utree_sredist_reset(utree_sredist *h) {
     if (!h) return UTREE_E_ARG;
     if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return UTREE_E_HIP;   /* adds in flight on any stream */
-    if (hipMemset(h->d_mem, 0, h->counters_bytes) != hipSuccess) return UTREE_E_HIP;                          /* (the arenas are written before they are read) */
-    if (hipMemset(h->tab.s.cells, 0xFF, 2 * (size_t)h->cell_slots * 8) != hipSuccess) return UTREE_E_HIP;     /* every cell key free (all ones) ... */
-    if (hipMemset2D(h->tab.s.cells + 1, 16, 0, 8, h->cell_slots) != hipSuccess) return UTREE_E_HIP;           /* ... and every count zero           */
+    const int rc = utree_sample_ids_reset(&h->tab.s);                                                         /* (the arenas are written before they are read) */
+    if (rc) return rc;
     if (hipMemset(h->tab.r.slots, 0, ((size_t)h->tab.r.mask + 1) * 16) != hipSuccess) return UTREE_E_HIP;     /* set key 0 = free */
     if (hipMemset(h->tab.r.misc, 0, UTK_REDIST_MISC_WORDS * 8) != hipSuccess) return UTREE_E_HIP;
     return hipDeviceSynchronize() == hipSuccess ? UTREE_OK : UTREE_E_HIP;
@@ -100,7 +68,7 @@ void utree_sredist_free(utree_sredist *h) {
     if (!h) return;
     hipSetDevice(h->device);
     hipDeviceSynchronize();
-    if (h->d_mem) hipFree(h->d_mem);
+    utree_sample_ids_free(&h->tab.s);
     if (h->tab.r.slots) hipFree(h->tab.r.slots);
     if (h->tab.r.arena) hipFree(h->tab.r.arena);
     if (h->tab.r.misc) hipFree(h->tab.r.misc);
@@ -142,94 +110,63 @@ static int collect(utree_sredist *h, flat_t *f) {
     memset(f, 0, sizeof *f);
     int rc = UTREE_OK;
     const size_t set_slots = (size_t)h->tab.r.mask + 1;
-    uint8_t *m = (uint8_t *)malloc(h->counters_bytes), *arena = NULL;
     unsigned long long *slots = NULL, rmisc[UTK_REDIST_MISC_WORDS];
-    uint32_t *sarena = NULL, *slot_of = NULL;
-    uint64_t *sum = NULL;
-    if (!m) return UTREE_E_NOMEM;
+    uint32_t *sarena = NULL;
+    char more[320];
+    utree_sample_ids_view v = {0};
     CHK(hipSetDevice(h->device));
     CHK(hipDeviceSynchronize());
-    CHK(hipMemcpy(m, h->d_mem, h->counters_bytes, hipMemcpyDeviceToHost));
     CHK(hipMemcpy(rmisc, h->tab.r.misc, sizeof rmisc, hipMemcpyDeviceToHost));
-    const unsigned long long *ids = (const unsigned long long *)m, *reads = ids + h->id_slots, *uncl = reads + h->id_slots,
-                             *cells = uncl + h->id_slots, *misc = cells + 2 * (size_t)h->cell_slots;
-    const uint32_t *index = (const uint32_t *)(misc + UTK_SAMPLES_MISC_WORDS);
-    f->n_reads = misc[0];
-    if ((rc = check_flags(misc[1], rmisc[1]))) goto fail;
-    const uint64_t S = misc[3], used = misc[2], sused = rmisc[2];
-    if (S > h->tab.s.sample_cap || used > h->tab.s.arena_cap || sused > h->tab.r.arena_cap) {
-        utree_set_error_text("sample redistribution: the counters of the tables are inconsistent"); rc = UTREE_E_DEVICE; goto fail;
-    }
-    slot_of = (uint32_t *)malloc((S ? S : 1) * sizeof *slot_of);
-    arena = (uint8_t *)malloc(used ? used : 1);
+    utree_redist_flags_text(rmisc[1], " ", ";", more, sizeof more);
+    rc = utree_sample_ids_read(&h->tab.s, &TEXT, more, &v);
+    f->n_reads = v.n_reads;
+    if (rc) goto fail;
+    const size_t S = v.S;
+    const uint64_t sused = rmisc[2];
+    if (sused > h->tab.r.arena_cap) { utree_set_error_text("sample redistribution: the counters of the tables are inconsistent"); rc = UTREE_E_DEVICE; goto fail; }
     slots = (unsigned long long *)malloc(set_slots * 16);
     sarena = (uint32_t *)malloc((sused ? sused : 1) * 4);
-    if (!slot_of || !arena || !slots || !sarena) { rc = UTREE_E_NOMEM; goto fail; }
-    if (used) CHK(hipMemcpy(arena, h->tab.s.arena, used, hipMemcpyDeviceToHost));
+    if (!slots || !sarena) { rc = UTREE_E_NOMEM; goto fail; }
     CHK(hipMemcpy(slots, h->tab.r.slots, set_slots * 16, hipMemcpyDeviceToHost));
     if (sused) CHK(hipMemcpy(sarena, h->tab.r.arena, sused * 4, hipMemcpyDeviceToHost));
-    for (uint64_t i = 0; i < S; ++i) slot_of[i] = 0xFFFFFFFFu;
-    uint64_t claimed = 0, id_bytes = 0;
-    for (uint32_t k = 0; k < h->id_slots; ++k) {
-        if (!ids[k]) continue;
-        const uint64_t at = ids[k] >> 32, len = (uint32_t)ids[k] - 1u;
-        if (index[k] >= S || slot_of[index[k]] != 0xFFFFFFFFu || at + len > used) {
-            utree_set_error_text("sample redistribution: a slot of the id table is inconsistent"); rc = UTREE_E_DEVICE; goto fail;
-        }
-        slot_of[index[k]] = k; ++claimed; id_bytes += len;
-    }
-    if (claimed != S) { utree_set_error_text("sample redistribution: the id table holds another number of ids than were claimed"); rc = UTREE_E_DEVICE; goto fail; }
     size_t nc = 0, nl = 0;
-    for (uint32_t c = 0; c < h->cell_slots; ++c) {
-        const unsigned long long key = cells[2 * (size_t)c], cnt = cells[2 * (size_t)c + 1];
+    for (uint32_t c = 0; c < v.cell_slots; ++c) {
+        const unsigned long long key = v.cells[2 * (size_t)c], cnt = v.cells[2 * (size_t)c + 1];
         if (key == ~0ull || !cnt) continue;
-        const uint32_t slot = (uint32_t)(key >> 32), hd = (uint32_t)key;
+        const uint32_t hd = (uint32_t)key;
+        uint32_t sample;
         uint64_t n = 1;
-        if (slot >= h->id_slots || !ids[slot]) { utree_set_error_text("sample redistribution: a cell names no sample"); rc = UTREE_E_DEVICE; goto fail; }
+        if ((rc = utree_sample_ids_count(&TEXT, &v, (uint32_t)(key >> 32), cnt, &sample))) goto fail;
         if (hd & UTK_SREDIST_ONE) { if ((hd & ~UTK_SREDIST_ONE) >= h->n_labels) n = 0; }
         else if (hd >= set_slots || !slots[2 * (size_t)hd] || (slots[2 * (size_t)hd] >> 32) + (uint32_t)slots[2 * (size_t)hd] > sused) n = 0;
         else n = (uint32_t)slots[2 * (size_t)hd];
         if (!n) { utree_set_error_text("sample redistribution: a cell names no candidate set"); rc = UTREE_E_DEVICE; goto fail; }
         ++nc; nl += n;
     }
-    f->S = (size_t)S; f->id_bytes = (size_t)id_bytes; f->n_cells = nc; f->n_labels = nl;
-    f->ids = (uint8_t *)malloc(id_bytes ? id_bytes : 1);
-    f->id_off = (uint64_t *)malloc((S + 1) * 8); f->reads = (uint64_t *)malloc((S ? S : 1) * 8); f->uncl = (uint64_t *)malloc((S ? S : 1) * 8);
+    f->S = S; f->id_bytes = v.id_bytes; f->n_cells = nc; f->n_labels = nl;
     f->cells = (utree_sredist_cell *)malloc((nc ? nc : 1) * sizeof *f->cells);
     f->labels = (uint32_t *)malloc((nl ? nl : 1) * 4);
-    sum = (uint64_t *)calloc(S ? S : 1, 8);
-    if (!f->ids || !f->id_off || !f->reads || !f->uncl || !f->cells || !f->labels || !sum) { rc = UTREE_E_NOMEM; goto fail; }
-    uint64_t w = 0, total = 0;
-    for (uint64_t i = 0; i < S; ++i) {
-        const uint32_t k = slot_of[i];
-        const uint64_t at = ids[k] >> 32, len = (uint32_t)ids[k] - 1u;
-        f->id_off[i] = w;
-        if (len) memcpy(f->ids + w, arena + at, len);
-        w += len;
-        f->reads[i] = reads[k]; f->uncl[i] = uncl[k];
-        total += reads[k];
-    }
-    f->id_off[S] = w;
+    if (!f->cells || !f->labels) { rc = UTREE_E_NOMEM; goto fail; }
     size_t q = 0, li = 0;
-    for (uint32_t c = 0; c < h->cell_slots; ++c) {
-        const unsigned long long key = cells[2 * (size_t)c], cnt = cells[2 * (size_t)c + 1];
+    for (uint32_t c = 0; c < v.cell_slots; ++c) {
+        const unsigned long long key = v.cells[2 * (size_t)c], cnt = v.cells[2 * (size_t)c + 1];
         if (key == ~0ull || !cnt) continue;
         const uint32_t slot = (uint32_t)(key >> 32), hd = (uint32_t)key;
         utree_sredist_cell *e = &f->cells[q++];
-        e->sample = index[slot]; e->first = li; e->reads = cnt;
+        e->sample = v.index[slot]; e->first = li; e->reads = cnt;
         if (hd & UTK_SREDIST_ONE) { e->n = 1; f->labels[li++] = hd & ~UTK_SREDIST_ONE; }
         else {
             e->n = (uint32_t)slots[2 * (size_t)hd];
             memcpy(f->labels + li, sarena + (slots[2 * (size_t)hd] >> 32), (size_t)e->n * 4);
             li += e->n;
         }
-        sum[e->sample] += cnt;
     }
-    for (uint64_t i = 0; i < S && !rc; ++i) if (f->reads[i] != f->uncl[i] + sum[i]) rc = UTREE_E_DEVICE;     /* per sample: reads = unclassified + its cells */
-    if (!rc && total != misc[0]) rc = UTREE_E_DEVICE;
-    if (rc) utree_set_error_text("sample redistribution: the samples' reads do not add up to the records added");
+    if ((rc = utree_sample_ids_check_sums(&TEXT, &v))) goto fail;
+    f->ids = v.ids; f->id_off = v.id_off; f->reads = v.reads; f->uncl = v.uncl;      /* the samples, dense: the flat table's from here on */
+    v.ids = NULL; v.id_off = NULL; v.reads = NULL; v.uncl = NULL;
 fail:
-    free(m); free(arena); free(slots); free(sarena); free(slot_of); free(sum);
+    free(slots); free(sarena);
+    utree_sample_ids_view_free(&v);
     if (rc) { const uint64_t nr = f->n_reads; flat_free(f); f->n_reads = nr; }
     return rc;
 }
@@ -244,7 +181,9 @@ int utree_sredist_reads(utree_sredist *h, uint64_t *n_reads) {
     CHK(hipMemcpy(misc, h->tab.s.misc, sizeof misc, hipMemcpyDeviceToHost));
     CHK(hipMemcpy(rmisc, h->tab.r.misc, sizeof rmisc, hipMemcpyDeviceToHost));
     *n_reads = misc[0];
-    rc = check_flags(misc[1], rmisc[1]);
+    char more[320];
+    utree_redist_flags_text(rmisc[1], " ", ";", more, sizeof more);
+    rc = utree_sample_ids_check_flags(&TEXT, misc[1], more);
 fail:
     return rc;
 }
@@ -410,109 +349,40 @@ fail:
 }
 
 /* ---- host: the samples of a read-back and the figures of a solve -> the file ---------------------------------------------------------------- */
-typedef struct { const uint8_t *s; uint64_t len; uint32_t sample; } col_t;
-typedef struct { const char *s; uint32_t len; uint32_t col; uint64_t reads; } row_t;
-
-static int text_cmp(const void *a, uint64_t la, const void *b, uint64_t lb) {
-    const uint64_t m = la < lb ? la : lb;
-    const int c = m ? memcmp(a, b, m) : 0;
-    if (c) return c;
-    return la < lb ? -1 : la > lb;
-}
-static int col_cmp(const void *a, const void *b) {
-    const col_t *x = (const col_t *)a, *y = (const col_t *)b;
-    return text_cmp(x->s, x->len, y->s, y->len);
-}
-static int row_cmp(const void *a, const void *b) {
-    const row_t *x = (const row_t *)a, *y = (const row_t *)b;
-    const int c = text_cmp(x->s, x->len, y->s, y->len);
-    if (c) return c;
-    return x->col < y->col ? -1 : x->col > y->col;
-}
-static int put_id(FILE *f, const uint8_t *s, uint64_t len) {           /* TAB, CR and backslash escaped, nothing else (the sample table's escapes) */
-    for (uint64_t i = 0; i < len; ++i) {
-        const int c = s[i];
-        const int r = c == '\t' ? fputs("\\t", f) : c == '\r' ? fputs("\\r", f) : c == '\\' ? fputs("\\\\", f) : fputc(c, f);
-        if (r == EOF) return 1;
-    }
-    return 0;
-}
-
 int utree_sredist_write(const utree_ctr *ctr, const uint8_t *ids, const uint64_t *id_off, const uint64_t *reads, const uint64_t *unclassified,
                         const uint32_t *passes, const uint64_t *ambiguous, size_t n_samples, const utree_sredist_entry *e, size_t n_entries,
                         uint64_t n_reads, const char *path) {
     if (!ctr || !path || (n_samples && (!id_off || !reads || !unclassified || !passes || !ambiguous)) || (n_entries && !e)) return UTREE_E_ARG;
     const size_t S = n_samples;
-    col_t *col = (col_t *)calloc(S ? S : 1, sizeof *col);
-    row_t *row = (row_t *)calloc(n_entries ? n_entries : 1, sizeof *row);
-    uint32_t *col_of = (uint32_t *)calloc(S ? S : 1, 4);
-    uint64_t *col_sum = (uint64_t *)calloc(S ? S : 1, 8);
+    utree_matrix_col *col = (utree_matrix_col *)calloc(S ? S : 1, sizeof *col);         /* column i is sample i; two samples with one id are refused by the writer */
+    utree_matrix_cell *row = (utree_matrix_cell *)calloc(n_entries ? n_entries : 1, sizeof *row);
+    uint64_t *passes64 = (uint64_t *)calloc(S ? S : 1, 8);
     int rc = UTREE_OK;
-    FILE *f = NULL;
-    if (!col || !row || !col_of || !col_sum) { rc = UTREE_E_NOMEM; goto done; }
+    if (!col || !row || !passes64) { rc = UTREE_E_NOMEM; goto done; }
     uint64_t total = 0, A = 0, G = 0;
     for (size_t i = 0; i < S; ++i) {
         if (id_off[i + 1] < id_off[i] || (id_off[i + 1] > id_off[i] && !ids)) { rc = UTREE_E_ARG; goto done; }
         col[i].len = id_off[i + 1] - id_off[i];
         col[i].s = col[i].len ? ids + id_off[i] : (const uint8_t *)"";
-        col[i].sample = (uint32_t)i;
+        col[i].reads = reads[i]; col[i].uncl = unclassified[i]; passes64[i] = passes[i];
         if (unclassified[i] > reads[i] || ambiguous[i] > reads[i] - unclassified[i] || passes[i] < 1 || passes[i] > 1000) { rc = UTREE_E_ARG; goto done; }
         total += reads[i]; A += ambiguous[i];
     }
     if (total != n_reads) { rc = UTREE_E_ARG; goto done; }                /* the samples' reads are the reads */
-    qsort(col, S, sizeof *col, col_cmp);                                 /* the columns: unsigned bytewise order, shorter first */
-    for (size_t j = 0; j < S; ++j) {
-        if (j && !col_cmp(&col[j - 1], &col[j])) { rc = UTREE_E_ARG; goto done; }      /* two samples with one id */
-        col_of[col[j].sample] = (uint32_t)j;
-    }
     size_t q = 0;
     for (size_t i = 0; i < n_entries; ++i) {
         if (e[i].sample >= S || e[i].label >= ctr->info.n_labels) { rc = UTREE_E_ARG; goto done; }
         if (!e[i].assigned) continue;
-        row[q].s = ctr->labels[e[i].label]; row[q].len = ctr->label_len[e[i].label]; row[q].col = col_of[e[i].sample]; row[q].reads = e[i].assigned;
-        col_sum[row[q].col] += e[i].assigned; G += e[i].assigned;
+        row[q].s = ctr->labels[e[i].label]; row[q].len = ctr->label_len[e[i].label]; row[q].col = e[i].sample; row[q].reads = e[i].assigned;
+        G += e[i].assigned;
         ++q;
     }
-    for (size_t i = 0; i < S; ++i)
-        if (col_sum[col_of[i]] != reads[i] - unclassified[i]) { rc = UTREE_E_ARG; goto done; }       /* column j sums to n_j - u_j */
-    qsort(row, q, sizeof *row, row_cmp);
-    size_t w = 0;
-    for (size_t i = 0; i < q; ++i) {                                     /* labels of equal text are one row */
-        if (w && !row_cmp(&row[w - 1], &row[i])) row[w - 1].reads += row[i].reads;
-        else row[w++] = row[i];
-    }
-    f = fopen(path, "wb");
-    if (!f) { rc = UTREE_E_IO; goto done; }
-    int bad = fprintf(f, "# reads\t%llu\tclassified\t%llu\tunclassified\t%llu\tambiguous\t%llu\tsamples\t%llu\n", (unsigned long long)n_reads,
-                      (unsigned long long)G, (unsigned long long)(n_reads - G), (unsigned long long)A, (unsigned long long)S) < 0;
-    bad |= fputs("# taxon", f) < 0;
-    for (size_t j = 0; j < S && !bad; ++j) bad = fputc('\t', f) == EOF || put_id(f, col[j].s, col[j].len);
-    bad |= fputs("\n# reads", f) < 0;
-    for (size_t j = 0; j < S && !bad; ++j) bad = fprintf(f, "\t%llu", (unsigned long long)reads[col[j].sample]) < 0;
-    bad |= fputs("\n# unclassified", f) < 0;
-    for (size_t j = 0; j < S && !bad; ++j) bad = fprintf(f, "\t%llu", (unsigned long long)unclassified[col[j].sample]) < 0;
-    bad |= fputs("\n# ambiguous", f) < 0;
-    for (size_t j = 0; j < S && !bad; ++j) bad = fprintf(f, "\t%llu", (unsigned long long)ambiguous[col[j].sample]) < 0;
-    bad |= fputs("\n# passes", f) < 0;
-    for (size_t j = 0; j < S && !bad; ++j) bad = fprintf(f, "\t%u", passes[col[j].sample]) < 0;
-    bad |= fputc('\n', f) == EOF;
-    for (size_t i = 0; i < w && !bad;) {                                 /* a row: the cells of one text, zeros where a sample has none */
-        size_t end = i;
-        while (end < w && !text_cmp(row[i].s, row[i].len, row[end].s, row[end].len)) ++end;
-        if (row[i].len && fwrite(row[i].s, 1, row[i].len, f) != row[i].len) bad = 1;
-        size_t at = i;
-        for (size_t j = 0; j < S && !bad; ++j) {
-            if (at < end && row[at].col == j) bad = fprintf(f, "\t%llu", (unsigned long long)row[at++].reads) < 0;
-            else bad = fputs("\t0", f) < 0;
-        }
-        if (fputc('\n', f) == EOF) bad = 1;
-        i = end;
-    }
-    if (fclose(f) != 0) bad = 1;
-    f = NULL;
-    if (bad) rc = UTREE_E_IO;
+    char header[200];
+    snprintf(header, sizeof header, "# reads\t%llu\tclassified\t%llu\tunclassified\t%llu\tambiguous\t%llu", (unsigned long long)n_reads,
+             (unsigned long long)G, (unsigned long long)(n_reads - G), (unsigned long long)A);
+    const utree_matrix_extra extra[2] = {{"ambiguous", ambiguous}, {"passes", passes64}};
+    rc = utree_sample_matrix_write(header, col, S, 0, extra, 2, row, q, path);          /* labels of equal text are one row */
 done:
-    if (f) fclose(f);
-    free(col); free(row); free(col_of); free(col_sum);
+    free(col); free(row); free(passes64);
     return rc;
 }

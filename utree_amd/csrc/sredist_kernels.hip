@@ -5,10 +5,9 @@
 // in the workspace -- and reads the names samples_add_k reads.  For a read it interns the sample id (samples_dev.hpp), finds the labels tied for
 // the highest count, and counts the cell (sample slot, set handle): the handle of a single candidate is the label itself, several candidates
 // are a set of the table redist_kernels.hip keeps (redist_dev.hpp) and the handle its slot.  What the two kernels learned is kept:
-//   ids      a lane compares its id with its predecessor lane's and with the one it had 1024 records before; only a lane that begins a run in
-//            both senses goes to the id table, the lanes behind it take its slot from a wavefront shuffle
-//   counts   a hash table of cells in the workgroup's LDS, runs of equal keys carried in registers, one no-return atomic per non-zero LDS slot
-//            into the device tables at the end; a read without a hit is a cell of its own there and leaves it for uncl[]
+//   ids      only a lane whose id is neither its predecessor lane's nor the one it had 1024 records before goes to the id table (sm_resolve)
+//   counts   a hash table of cells in the workgroup's LDS (SmCells), runs of equal keys carried in registers; a read without a hit is a cell of its
+//            own there and leaves it for uncl[]
 //   queues   a read with a list goes on the workgroup's queue with its sample slot; that queue is dealt out over all lanes, which find each
 //            list's tied maximum; several candidates put the read on a second queue, dealt out when it may not hold another round's reads: no
 //            wavefront runs the set table's probe chain for a few of its lanes
@@ -25,15 +24,14 @@
 
 #define SR_BLOCK 1024
 #define SR_UNROLL 4
+static_assert(SR_UNROLL == RD_UNROLL, "sredist_add_k deals its queue out in rd_scan_listed's steps");
 #define SR_TILE 4096u                      // reads a workgroup takes per round = the capacity of its queue of listed reads (a 12-bit position)
 #define SR_Q2 8192u                        // capacity of its queue of reads with several candidates
 #define SR_HSLOTS 4096u                    // LDS hash slots: 32 KiB of keys + 16 KiB of counts
-#define SR_LDS_PROBES 32u
 #define SR_UNCL 0xFFFFFFFFu                // the handle of a sample's reads without a hit, in LDS only
 
 struct SrLds {
-    unsigned long long key[SR_HSLOTS];
-    uint32_t cnt[SR_HSLOTS];
+    SmCells<SR_HSLOTS> cells;
     uint32_t q[SR_TILE];                   // position in the round | sample slot << 12
     uint2 q2[SR_Q2];                       // {record, sample slot}
     uint32_t qn, q2n, flags;
@@ -50,18 +48,7 @@ __device__ void sr_global_add(const utk_sredist_tab &t, uint64_t key, uint32_t c
 }
 
 __device__ void sr_lds_add(SrLds &s, const utk_sredist_tab &t, uint64_t key, uint32_t cnt) {
-    if (!cnt) return;
-    const uint32_t h = (uint32_t)sm_mix(key);
-    for (uint32_t p = 0; p < SR_LDS_PROBES; ++p) {
-        const uint32_t i = (h + p) & (SR_HSLOTS - 1);
-        unsigned long long k = s.key[i];
-        if (k == SM_KEY_FREE) {
-            k = atomicCAS(&s.key[i], SM_KEY_FREE, (unsigned long long)key);
-            if (k == SM_KEY_FREE) k = key;
-        }
-        if (k == key) { atomicAdd(&s.cnt[i], cnt); return; }
-    }
-    sr_global_add(t, key, cnt);
+    s.cells.add(key, cnt, [&](uint64_t k, uint32_t c) { sr_global_add(t, k, c); });
 }
 
 // one read of sample `slot` whose only candidate is the file-order index `one`
@@ -70,69 +57,21 @@ __device__ __forceinline__ void sr_single(SrLds &s, const utk_sredist_tab &t, ui
     sr_lds_add(s, t, sr_key(slot, UTK_SREDIST_ONE | one), 1u);
 }
 
-// SR_UNROLL queued reads per thread (rd_listed's loop: the four reads' records, list entries and index look-ups are requested side by side)
+// RD_UNROLL queued reads per thread (redist_dev.hpp: rd_scan_listed), each with the sample slot its queue entry carries
 __device__ void sr_listed(const utk_sredist_tab &t, SrLds &s, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
                           const uint64_t *__restrict__ tally, uint64_t tile, uint32_t first, uint32_t qn) {
-    const uint32_t nl = t.r.n_labels;
-    uint32_t uix[SR_UNROLL], mx[SR_UNROLL], ties[SR_UNROLL], k0[SR_UNROLL], rr[SR_UNROLL], sl[SR_UNROLL], umax = 0;
-    const uint64_t *T[SR_UNROLL];
-#pragma unroll
-    for (int u = 0; u < SR_UNROLL; ++u) {
-        const uint32_t i = first + (uint32_t)u * SR_BLOCK;
-        uix[u] = 0; T[u] = tally; mx[u] = 0; ties[u] = 0; k0[u] = 0; rr[u] = 0; sl[u] = 0;
-        if (i < qn) {
-            const uint32_t e = s.q[i];
-            rr[u] = (uint32_t)(tile + (e & (SR_TILE - 1u))); sl[u] = e >> 12;
-            const uint32_t *rec = (const uint32_t *)&res[rr[u]];
-            uix[u] = rec[3];
-            T[u] = tally + ((uint64_t)rec[4] | ((uint64_t)rec[5] << 32));
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < SR_UNROLL; ++u) umax = uix[u] > umax ? uix[u] : umax;
-    for (uint32_t i = 0; i < umax; ++i) {
-        uint64_t e[SR_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SR_UNROLL; ++u) e[u] = i < uix[u] ? T[u][i] : 0ull;
-#pragma unroll
-        for (int u = 0; u < SR_UNROLL; ++u) {
-            if (i >= uix[u]) continue;
-            const uint32_t c = (uint32_t)(e[u] >> 32), rk = (uint32_t)e[u];
-            if (c > mx[u]) { mx[u] = c; ties[u] = 1; k0[u] = rk; }
-            else if (c == mx[u]) ++ties[u];
-        }
-    }
-    uint32_t c0[SR_UNROLL];
-#pragma unroll
-    for (int u = 0; u < SR_UNROLL; ++u) c0[u] = ties[u] == 1 && k0[u] < nl ? rank2ix[k0[u]] : 0xFFFFFFFFu;
-#pragma unroll
-    for (int u = 0; u < SR_UNROLL; ++u) {
-        if (first + (uint32_t)u * SR_BLOCK >= qn) continue;
-        if (!ties[u] || !mx[u]) { rd_flag(t.r, UTK_REDIST_F_LABEL); continue; }        // (an empty list: the classify kernels write none; never dropped silently)
-        if (ties[u] == 1) sr_single(s, t, sl[u], c0[u]);
-        else s.q2[atomicAdd(&s.q2n, 1u)] = make_uint2(rr[u], sl[u]);                  // several candidates: the table, with full wavefronts
-    }
+    rd_scan_listed<SR_BLOCK>(t.r, rank2ix, res, tally, first, qn,
+                             [&](uint32_t i, uint32_t &r, uint32_t &slot) { const uint32_t e = s.q[i]; r = (uint32_t)(tile + (e & (SR_TILE - 1u))); slot = e >> 12; },
+                             [&](uint32_t slot, uint32_t one) { sr_single(s, t, slot, one); },
+                             [&](uint32_t r, uint32_t slot) { s.q2[atomicAdd(&s.q2n, 1u)] = make_uint2(r, slot); });
 }
 
 // a queued read with several candidates: its set into the table, its cell counted
 __device__ void sr_multi(const utk_sredist_tab &t, SrLds &s, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
                          const uint64_t *__restrict__ tally, uint2 q) {
-    const uint32_t *rec = (const uint32_t *)&res[q.x];
-    const uint32_t uix = rec[3], nl = t.r.n_labels;
-    const uint64_t *T = tally + ((uint64_t)rec[4] | ((uint64_t)rec[5] << 32));
-    uint32_t mx = 0, ties = 0, k0 = 0, k1 = 0, k2 = 0, k3 = 0, pos4 = 0;
-    for (uint32_t i = 0; i < uix; ++i) {
-        const uint64_t e = T[i];
-        const uint32_t c = (uint32_t)(e >> 32), rk = (uint32_t)e;
-        if (c > mx) { mx = c; ties = 1; k0 = rk; }
-        else if (c == mx) {
-            if (ties == 1) k1 = rk; else if (ties == 2) k2 = rk; else if (ties == 3) { k3 = rk; pos4 = i + 1; }
-            ++ties;
-        }
-    }
+    TiedSeq seq;
+    const uint32_t ties = rd_scan_tied(t.r, rank2ix, res, tally, q.x, seq);
     if (ties < 2) { rd_flag(t.r, UTK_REDIST_F_LABEL); return; }       // (sr_listed queued it for having more: never dropped silently)
-    TiedSeq seq = {T, rank2ix, mx, uix, nl, k0 < nl ? rank2ix[k0] : 0xFFFFFFFFu, k1 < nl ? rank2ix[k1] : 0xFFFFFFFFu,
-                   ties > 2 && k2 < nl ? rank2ix[k2] : 0xFFFFFFFFu, ties > 3 && k3 < nl ? rank2ix[k3] : 0xFFFFFFFFu, pos4, 0, 0};
     const uint32_t set = rd_insert(t.r, seq, ties, 0ull);
     if (set != RD_NO_SLOT) sr_lds_add(s, t, sr_key(q.y, set), 1u);
 }
@@ -142,7 +81,7 @@ __global__ void __launch_bounds__(SR_BLOCK) sredist_add_k(utk_sredist_tab t, con
                                                           const uint32_t *__restrict__ name_off, const uint32_t *__restrict__ name_len, uint32_t n,
                                                           uint32_t per_block) {
     __shared__ SrLds s;
-    for (uint32_t i = threadIdx.x; i < SR_HSLOTS; i += SR_BLOCK) { s.key[i] = SM_KEY_FREE; s.cnt[i] = 0; }
+    s.cells.init(threadIdx.x, SR_BLOCK);
     if (threadIdx.x == 0) { s.flags = 0; s.q2n = 0; }
 
     const uint64_t begin = (uint64_t)blockIdx.x * per_block;
@@ -150,9 +89,8 @@ __global__ void __launch_bounds__(SR_BLOCK) sredist_add_k(utk_sredist_tab t, con
     const uint32_t lane = threadIdx.x & 63u;
     uint64_t run = SM_KEY_FREE;
     uint32_t run_n = 0, flags = 0;
-    uint32_t pv_off = 0, pv_idl = 0, pv_slot = SM_NONE;    // the id this thread had 1024 records before, and its slot
-    bool pv_ok = false;
-    for (uint64_t tile = begin; tile < end; tile += SR_TILE) {                     // (the same trips in every lane: the shuffles below need them all)
+    SmPrev pv;
+    for (uint64_t tile = begin; tile < end; tile += SR_TILE) {                     // (the same trips in every lane: sm_resolve needs them all)
         const uint64_t tend = tile + SR_TILE < end ? tile + SR_TILE : end;
         if (threadIdx.x == 0) s.qn = 0;
         __syncthreads();
@@ -167,26 +105,8 @@ __global__ void __launch_bounds__(SR_BLOCK) sredist_add_k(utk_sredist_tab t, con
         }
 #pragma unroll
         for (int u = 0; u < SR_UNROLL; ++u) {
-            bool valid = ok[u];
-            if (valid && ((uint64_t)off[u] > text_bytes || (uint64_t)nlen[u] > text_bytes - off[u])) { flags |= (uint32_t)UTK_SAMPLES_F_NAME; valid = false; }
-            const uint8_t *id = text + (valid ? off[u] : 0u);
-            const uint32_t idl = valid ? sm_id_len(id, nlen[u], t.s.delim) : 0u;
-            // the predecessor in record order is the lane below
-            const uint32_t p_off = (uint32_t)__shfl_up((int)off[u], 1), p_idl = (uint32_t)__shfl_up((int)idl, 1);
-            const int p_valid = __shfl_up((int)valid, 1);
-            bool head = valid;
-            if (valid && lane > 0 && p_valid && p_idl == idl && sm_same(id, text + p_off, idl)) head = false;
-            uint32_t slot = SM_NONE;
-            if (head) {
-                if (pv_ok && pv_idl == idl && sm_same(id, text + pv_off, idl)) slot = pv_slot;
-                else slot = sm_intern(t.s, id, idl);
-            }
-            // every lane takes the slot of the nearest head at or below it (a valid lane 0 is one; lanes beyond the batch's end follow no valid lane)
-            const uint64_t heads = __ballot(head);
-            const uint64_t below = heads & ((2ull << lane) - 1ull);
-            const int src = below ? 63 - __clzll((long long)below) : (int)lane;
-            slot = (uint32_t)__shfl((int)slot, src);
-            if (valid) { pv_off = off[u]; pv_idl = idl; pv_slot = slot; pv_ok = true; }
+            uint32_t slot;
+            const bool valid = sm_resolve(t.s, text, text_bytes, off[u], nlen[u], ok[u], lane, pv, flags, slot);
             uint64_t key = SM_KEY_FREE;
             if (!valid || slot == SM_NONE) {}
             else if (!fnd[u]) key = sr_key(slot, SR_UNCL);
@@ -217,8 +137,7 @@ __global__ void __launch_bounds__(SR_BLOCK) sredist_add_k(utk_sredist_tab t, con
     if (flags) atomicOr(&s.flags, flags);
     __syncthreads();
 
-    for (uint32_t i = threadIdx.x; i < SR_HSLOTS; i += SR_BLOCK)
-        if (s.key[i] != SM_KEY_FREE && s.cnt[i]) sr_global_add(t, s.key[i], s.cnt[i]);
+    s.cells.flush(threadIdx.x, SR_BLOCK, [&](uint64_t k, uint32_t c) { sr_global_add(t, k, c); });
     if (threadIdx.x == 0) {
         if (blockIdx.x == 0) sm_add(t.s.misc + 0, n);
         if (s.flags & 0x7FFFFFFFu) sm_flag(t.s, s.flags & 0x7FFFFFFFu);
