@@ -715,6 +715,8 @@ static uint32_t mid_limit(void) {
 
 /* UTREE_LANE_PASS=0 keeps every batch on the wave-per-read kernels (comparison runs) */
 static int lanes_enabled(void) { const char *e = getenv("UTREE_LANE_PASS"); return !(e && e[0] == '0'); }
+/* UTREE_TALLY_INLINE=0: the lane pass lists every read of two or more labels, none keeps its entries in its pending record (tests, comparison runs) */
+static int tally_inline_enabled(void) { const char *e = getenv("UTREE_TALLY_INLINE"); return !(e && e[0] == '0'); }
 
 static void ring_lock(utree_dev *d) { while (__atomic_test_and_set(&d->ring_busy, __ATOMIC_ACQUIRE)) ; }
 static void ring_unlock(utree_dev *d) { __atomic_clear(&d->ring_busy, __ATOMIC_RELEASE); }
@@ -854,6 +856,7 @@ static void carve(const utree_dev *d, void *ws, uint32_t n_reads, uint64_t total
      * per batch, the workspace's size must not depend on that.) */
     w->pieces = NULL; w->ltab_rank = w->ltab_cnt = w->lflag = w->long_left = NULL; w->n_long_cap = 0; w->ltally_base = 0;
     w->cls_list = NULL; w->cls_stride = 0; w->n_pieces_cap = 0;
+    w->tally_inline = 0;                                               /* (the batch's choice: utree_classify_batch_reports) */
     if (lanes_img && max_len > UTREE_LANES_CAP) {
         w->cls_stride = (n_reads + 63u) & ~63u;
         w->cls_list = (uint32_t *)(b + off); off = align_up(off + (uint64_t)5 * w->cls_stride * 4, 256);
@@ -932,6 +935,8 @@ int utree_classify_batch_reports(utree_dev *d, const uint8_t *d_bases, const uin
         else tslot = -1;
     }
     ring_collect(d);
+    /* packed pending records (CUT_INLINE) are the vote's alone to read: the redistribution passes see lists only */
+    w.tally_inline = !rd && !srd && tally_inline_enabled();
     const int lanes = lanes_enabled() && utk_lanes_image_ok(&d->kimg) && lanes_worth(d);
     if (lanes) {
         /* ---- the lane-per-read pass: a batch of reads of up to 160 bases goes through whole with one lane per read; any other batch is

@@ -384,6 +384,9 @@ constexpr uint32_t TALLY_DIRECT = UTREE_TALLY_CHUNK / 16;   // hit lists this lo
 constexpr int32_t CUT_PENDING = -3;                 // result.cut while a read waits for vote_k
 constexpr int32_t RANK_PENDING = -4;                // one distinct label: result.label holds its RANK until vote_k looks up the
                                                     // label index (a dependent load classify_short_k would otherwise wait for)
+constexpr int32_t CUT_INLINE = -5;                  // two or three distinct labels, from the lane-per-read pass with ws.tally_inline: found = F, uix = 2 or 3, and
+                                                    // label / sl / ol hold the read's tally slot words {rank << CB | count} in ascending rank (the third unused
+                                                    // when uix = 2) -- its whole list, no entry in ws.tally.  Pending records never leave the library.
 
 // SHORT_MIN_WAVES: 8 waves/SIMD for u16-label databases measured faster than 5 even with a few spilled dwords (k = 32: +4 % in r01;
 // k = 64: 932 -> 1020 M reads/s, same-box); with u32 labels the hit list's LDS caps the occupancy at 5-6 anyway.  (Voting inside this kernel, 64 parked reads per
@@ -848,6 +851,30 @@ __device__ __forceinline__ bool v_us(const VRec &v, uint32_t t) { return ((uint3
 __device__ __forceinline__ uint32_t v_len(const VRec &v) { return (uint32_t)(v.w[3] >> 32) & 0xFFu; }   // the label's length
 __device__ __forceinline__ uint32_t v_ix(const VRec &v) { return (uint32_t)(v.w[3] >> 48); }             // its file-order index
 
+// A read's (rank, count) list as the vote walks it: entry(i) = {rank | count << 32} of its i-th label in ascending rank.  The list is either
+// the one in ws.tally that a CUT_PENDING record points to (a = unused, b | c << 32 = its index there), or the two or three tally slot words
+// a, b, c of a CUT_INLINE record themselves, kept in registers and picked with selects (an indexed register array would go to scratch); cb =
+// the count bits of a slot word (lanes_core.hpp: CB).  Such a read's walk starts without a trip to a list: the records of both ends of the
+// list -- of a read of two labels: all it has -- are requested at once, from the record the lane has loaded anyway.
+// (One walk for both forms, which differ inside entry() only: a wavefront holds reads of either, and with a walk per form it ran both, one
+// after the other -- vote_table_k 0.655 ms per 16 M reads where the lists in HBM alone took 0.599.)
+struct TallyList {
+    const uint64_t *tally;
+    uint32_t a, b, c, cb;
+    bool packed;
+    __device__ __forceinline__ uint64_t entry(uint32_t i) const {
+        if (packed) {
+            const uint32_t w = i == 0u ? a : i == 1u ? b : c;
+            return (uint64_t)(w >> cb) | ((uint64_t)(w & ((1u << cb) - 1u)) << 32);
+        }
+        return tally[((uint64_t)b | ((uint64_t)c << 32)) + i];
+    }
+};
+// (res: a record's six words, pending)
+__device__ __forceinline__ TallyList tally_list(const utk_image &im, const utk_workspace &ws, const uint32_t *res) {
+    return TallyList{ws.tally, res[0], res[4], res[5], im.I == 4u ? 13u : 16u, (int32_t)res[1] == CUT_INLINE};
+}
+
 // The vote with the label table (UTREE_F_VOTE_TABLE): the same state machine as below, every byte scan replaced by what the table says
 // about it.  The labels of the active group [st, ed) agree up to byte dv; t is the token that holds byte dv + 1 (0 at the start), the
 // same for all of them.  For a pair (prev, cur) of the group the reference's scan from dv + 1 stops at prev's next terminator e1 =
@@ -857,7 +884,7 @@ __device__ __forceinline__ uint32_t v_ix(const VRec &v) { return (uint32_t)(v.w[
 //        only to tell "less specific" (td = e1 and the byte before is '_': an empty rank like s__) from "differs": unless prev's token
 //        ends in '_' the answer is "differs" wherever td lies.  td itself -- the next dv -- matters only when this pair ends the walk
 //        with the group winning and the descent going on: then, and for tokens ending in '_', the bytes are read (pair_scan).
-__device__ __forceinline__ void vote_table(const utk_image &im, utree_result *out_r, const uint64_t *T, uint32_t F, uint32_t uix) {
+__device__ __forceinline__ void vote_table(const utk_image &im, utree_result *out_r, const TallyList &T, uint32_t F, uint32_t uix) {
     const uint64_t *vt = im.vote_tab;
     const char *blob = im.label_blob;
     const uint32_t *loff = im.label_off;
@@ -868,9 +895,9 @@ __device__ __forceinline__ void vote_table(const utk_image &im, utree_result *ou
     // also the walk's last `cur`, and whatever ends the descent has its record in registers already)
     uint32_t ix_last, n_last, len_last;                                      // the label the result is cut from: file-order index, count, length
     for (;;) {
-        const uint64_t t_st = T[st];
+        const uint64_t t_st = T.entry(st);
         VRec pv = vrec(vt, (uint32_t)t_st);
-        const uint64_t t_ed = ed - 1u == st ? t_st : T[ed - 1u];
+        const uint64_t t_ed = ed - 1u == st ? t_st : T.entry(ed - 1u);
         const VRec lv = ed - 1u == st ? pv : vrec(vt, (uint32_t)t_ed);
         {
             // levels at which the whole group carries one token: the group's first and last label agree through token L - 1, each followed
@@ -887,7 +914,7 @@ __device__ __forceinline__ void vote_table(const utk_image &im, utree_result *ou
         bool stopped = false;
         for (uint32_t z = st + 1; z < ed; ++z) {
             const bool is_last = z == ed - 1u;
-            const uint64_t tz = is_last ? t_ed : T[z];
+            const uint64_t tz = is_last ? t_ed : T.entry(z);
             const uint32_t nz = (uint32_t)(tz >> 32), rc = (uint32_t)tz;
             const VRec cv = is_last ? lv : vrec(vt, rc);
             bool aside = false, stop = false;
@@ -943,67 +970,64 @@ __device__ __forceinline__ void vote_table(const utk_image &im, utree_result *ou
 
 // vote_table_k: vote_k for images with the label table (a kernel of its own: with both in one, the byte scans' registers cost the table path
 // three of its eight wavefronts per SIMD)
-__global__ __launch_bounds__(256) void vote_table_k(utk_image im, utree_result *__restrict__ out, utk_workspace ws, uint32_t n_reads) {
+// (six wavefronts per SIMD, 80 registers, is what the walk over a list in HBM takes by itself; with a record's own words as the other form of the
+// list the allocator asks for 84 and loses a wavefront unless it is told: so told it fits 78, nothing spilled -- 32 bytes per lane go to LDS)
+__global__ __launch_bounds__(256, 6) void vote_table_k(utk_image im, utree_result *__restrict__ out, utk_workspace ws, uint32_t n_reads) {
     // The vote is a per-lane state machine: a wavefront executes the union of its lanes' paths, and a read of two labels takes a fraction of
     // the steps a read of four takes.  The workgroup's 256 reads are therefore dealt out again by what they need: reads of two labels fill the
-    // workgroup's lanes from the bottom, reads of more from the top (the two kinds meet in one wavefront at most); a read of one label or none
-    // is finished where it stands.
-    __shared__ uint32_t s_n[2][4];
+    // workgroup's lanes from the bottom, reads of three follow them, reads of four and more -- the ones whose list is in HBM when the lane pass
+    // packs -- fill them from the top (two kinds meet in one wavefront at two places at most); a read of one label or none is finished where
+    // it stands.  (Three kinds instead of "two" and "more": 0.575 -> 0.550 ms per 16 M reads, profiles/tally_inline_ab.json.)
+    constexpr uint32_t NC = 3;
+    __shared__ uint32_t s_n[NC][4];
     __shared__ uint16_t s_who[256];
     const uint32_t tid = threadIdx.x, wv = tid >> 6, lane = tid & 63u;
     const uint32_t r0 = blockIdx.x * blockDim.x + tid;
-    uint32_t cls = 2;                                      // 0: two labels, 1: more, 2: nothing left to do
+    uint32_t cls = NC;                                     // 0: two labels, 1: three, 2: more, NC: nothing left to do
     if (r0 < n_reads) {
         const uint32_t *res = (const uint32_t *)&out[r0];
         const int32_t cut = (int32_t)res[1];
         if (cut == RANK_PENDING) {                         // one distinct label: only its file-order index is missing
             uint32_t *o = (uint32_t *)&out[r0];
             o[0] = im.rank2ix[res[0]]; o[1] = (uint32_t)-2;
-        } else if (cut == CUT_PENDING) cls = res[3] == 2u ? 0u : 1u;
+        } else if (cut == CUT_PENDING || cut == CUT_INLINE) cls = res[3] == 2u ? 0u : res[3] == 3u ? 1u : 2u;
     }
-    const uint64_t m0 = __builtin_amdgcn_ballot_w64(cls == 0u), m1 = __builtin_amdgcn_ballot_w64(cls == 1u);
+    const uint64_t m0 = __builtin_amdgcn_ballot_w64(cls == 0u), m1 = __builtin_amdgcn_ballot_w64(cls == 1u), m2 = __builtin_amdgcn_ballot_w64(cls == 2u);
     s_who[tid] = 0xFFFFu;
-    if (lane == 0) { s_n[0][wv] = (uint32_t)__popcll(m0); s_n[1][wv] = (uint32_t)__popcll(m1); }
+    if (lane == 0) { s_n[0][wv] = (uint32_t)__popcll(m0); s_n[1][wv] = (uint32_t)__popcll(m1); s_n[2][wv] = (uint32_t)__popcll(m2); }
     __syncthreads();
-    if (cls < 2u) {
+    if (cls < NC) {
         uint32_t before = 0;
         for (uint32_t w = 0; w < wv; ++w) before += s_n[cls][w];
-        before += (uint32_t)__popcll((cls ? m1 : m0) & ((1ull << lane) - 1ull));
-        s_who[cls ? 255u - before : before] = (uint16_t)tid;
+        const uint64_t mine = cls == 0u ? m0 : cls == 1u ? m1 : m2;
+        before += (uint32_t)__popcll(mine & ((1ull << lane) - 1ull));
+        if (cls == 1u) before += s_n[0][0] + s_n[0][1] + s_n[0][2] + s_n[0][3];      // behind the workgroup's reads of two labels
+        s_who[cls == 2u ? 255u - before : before] = (uint16_t)tid;
     }
     __syncthreads();
     const uint32_t who = s_who[tid];
     if (who == 0xFFFFu) return;
     const uint32_t r = blockIdx.x * blockDim.x + who;
     const uint32_t *res = (const uint32_t *)&out[r];
-    vote_table(im, &out[r], ws.tally + ((uint64_t)res[4] | ((uint64_t)res[5] << 32)), res[2], res[3]);
+    const uint32_t F = res[2], uix = res[3];
+    vote_table(im, &out[r], tally_list(im, ws, res), F, uix);
 }
 
-__global__ __launch_bounds__(256) void vote_k(utk_image im, utree_result *__restrict__ out, utk_workspace ws, uint32_t n_reads) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_reads) return;
-    const uint32_t *res = (const uint32_t *)&out[r];
-    if ((int32_t)res[1] == RANK_PENDING) {                 // one distinct label: only its file-order index is missing
-        uint32_t *o = (uint32_t *)&out[r];
-        o[0] = im.rank2ix[res[0]]; o[1] = (uint32_t)-2;
-        return;
-    }
-    if ((int32_t)res[1] != CUT_PENDING) return;            // finished by the classify kernel (no hit, or classify_long_k)
-    const uint32_t F = res[2], uix = res[3];
-    const uint64_t *T = ws.tally + ((uint64_t)res[4] | ((uint64_t)res[5] << 32));
+// the vote from the label bytes (itree.c:1044-1088) over a read's list
+__device__ __forceinline__ void vote_bytes(const utk_image &im, utree_result *out_r, const TallyList &T, uint32_t F, uint32_t uix) {
     const char *blob = im.label_blob;
     const uint32_t *loff = im.label_off;
     uint32_t cutoff = cut_of(F);
     uint32_t st = 0, ed = uix, dv = 0xFFFFFFFFu, orun = F, sl, ol;
     for (;;) {
-        const uint64_t t_st = T[st];
+        const uint64_t t_st = T.entry(st);
         {
             // Levels at which every label of the group [st, ed) carries the same token change nothing but dv (each pair
             // stops at the token's ';' with equal bytes: run ends up as orun, st / ed / cutoff stay): dv moves to that
             // ';'.  The list is in strcmp order, so a prefix the group's first and last label share is shared by all of
             // them: ONE scan of those two labels finds the last ';' they share beyond dv, instead of a pass over all
             // pairs per level.  The level that follows is the first one with something to decide.
-            const char *sa = blob + loff[(uint32_t)t_st], *sz = blob + loff[(uint32_t)T[ed - 1]];
+            const char *sa = blob + loff[(uint32_t)t_st], *sz = blob + loff[(uint32_t)T.entry(ed - 1u)];
             uint32_t base = dv + (dv == 0xFFFFFFFFu), q = 0xFFFFFFFFu;
             bool first = dv != 0xFFFFFFFFu;                                   // then byte `base` (= dv) itself does not count
             for (;;) {
@@ -1036,7 +1060,7 @@ __global__ __launch_bounds__(256) void vote_k(utk_image im, utree_result *__rest
         uint64_t x1_first, y1_first;
         label16(s1, probe, x1_first, y1_first);
         for (uint32_t z = st + 1; z < ed; ++z) {
-            const uint64_t tz = T[z];
+            const uint64_t tz = T.entry(z);
             const uint32_t nz = (uint32_t)(tz >> 32);
             const char *s2 = blob + loff[(uint32_t)tz];
             uint64_t x1 = x1_first, y1 = y1_first;
@@ -1083,17 +1107,32 @@ __global__ __launch_bounds__(256) void vote_k(utk_image im, utree_result *__rest
         sl = run; ol = orun;                                                   // itree.c:1071
         if (run < cutoff) break;                                               // itree.c:1072
         if (st + 1 >= ed) {                                                    // itree.c:1073-1079
-            if ((uint32_t)(T[ed - 1] >> 32) >= cutoff) dv = 0xFFFFFFFEu;
+            if ((uint32_t)(T.entry(ed - 1u) >> 32) >= cutoff) dv = 0xFFFFFFFEu;
             break;
         }
         orun = run; dv = td; cutoff = cut_of(run);                             // itree.c:1082-1085
     }
-    const uint32_t rk = (uint32_t)T[ed - 1];
+    const uint32_t rk = (uint32_t)T.entry(ed - 1u);
     int32_t cut;
     if (dv == 0xFFFFFFFFu) cut = -1;                                           // itree.c:1087
     else if (dv == 0xFFFFFFFEu) cut = -2;
     else { uint32_t Ls = loff[rk + 1] - loff[rk] - 1; cut = (int32_t)(dv < Ls ? dv : Ls); }   // 1088
-    store_result(&out[r], im.rank2ix[rk], cut, F, uix, sl, ol);
+    store_result(out_r, im.rank2ix[rk], cut, F, uix, sl, ol);
+}
+
+__global__ __launch_bounds__(256) void vote_k(utk_image im, utree_result *__restrict__ out, utk_workspace ws, uint32_t n_reads) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const uint32_t *res = (const uint32_t *)&out[r];
+    const int32_t pend = (int32_t)res[1];
+    if (pend == RANK_PENDING) {                            // one distinct label: only its file-order index is missing
+        uint32_t *o = (uint32_t *)&out[r];
+        o[0] = im.rank2ix[res[0]]; o[1] = (uint32_t)-2;
+        return;
+    }
+    if (pend != CUT_PENDING && pend != CUT_INLINE) return; // finished by the classify kernel (no hit, or classify_long_k)
+    const uint32_t F = res[2], uix = res[3];
+    vote_bytes(im, &out[r], tally_list(im, ws, res), F, uix);
 }
 
 template <int W, int I, bool EXC, typename OFF>

@@ -67,6 +67,7 @@ template <int W> struct Geo {
 constexpr uint32_t TSLOTS = 12;                       // distinct labels per read this kernel keeps count of
 constexpr uint32_t T_EMPTY = 0xFFFFFFFFu;             // an unused slot of a tally table (rank 0xFFFF is no label's)
 constexpr int32_t CUT_PENDING = -3, RANK_PENDING = -4;   // as in kernels.hip (vote_k finishes those results)
+constexpr int32_t CUT_INLINE = -5;                       // ... two or three labels: the read's tally slot words, ascending rank, in label / sl / ol
 
 __device__ __forceinline__ uint32_t low_bytes(uint32_t n) { return n >= 4u ? 0xFFFFFFFFu : ((1u << (8u * n)) - 1u); }
 // (the lane mask of a condition as the compare leaves it: __ballot() takes an int and costs a select and a second compare)
@@ -893,26 +894,30 @@ _Pragma("unroll") for (uint32_t x = 0; x < NA; ++x) { A[x] = RA[x]; B[x] = RB[x]
         const uint32_t first_rank = tq[0] >> CB;
         const uint32_t maxnu = uni32(wave_max_u32(nu));
         // space for the (rank, count) lists of the reads with two or more labels: one reservation per wave and TALLY_CHUNK
-        const uint32_t need = nu >= 2u ? nu : 0u;
-        uint32_t incl = need;
+        // (ws.tally_inline: a read of two or three labels keeps its slot words in its own pending record, CUT_INLINE -- the vote has loaded
+        // that record anyway --, and only reads of four or more labels take list space: a grab without one reserves, scans and stores nothing)
+        const bool inl = ws.tally_inline != 0u;                              // (wave-uniform: a scalar branch)
+        const uint32_t need = nu >= (inl ? 4u : 2u) ? nu : 0u;
+        unsigned long long my_base = 0;
+        if (ballot64(need != 0u)) {
+            uint32_t incl = need;
 #pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t t = __shfl_up(incl, dd); if (lane >= (uint32_t)dd) incl += t; }
-        const uint32_t total = uni32((uint32_t)__shfl(incl, 63));
-        if (total > chunk_left) {
-            unsigned long long nb = 0;
-            if (lane == 0) {
-                nb = atomicAdd(&ws.cursors[0], (unsigned long long)UTREE_TALLY_CHUNK);
-                // (the workspace is sized so that this cannot happen, dev_image.c: carve; if it does, the batch is reported as failed
-                // and the wave writes into the first chunk instead of past the end)
-                if (nb + UTREE_TALLY_CHUNK > ws.tally_cap) { ws.cursors[UTREE_CUR_ERROR] = UTREE_DEVERR_TALLY_CAP; nb = 0; }
+            for (int dd = 1; dd < 64; dd <<= 1) { const uint32_t t = __shfl_up(incl, dd); if (lane >= (uint32_t)dd) incl += t; }
+            const uint32_t total = uni32((uint32_t)__shfl(incl, 63));
+            if (total > chunk_left) {
+                unsigned long long nb = 0;
+                if (lane == 0) {
+                    nb = atomicAdd(&ws.cursors[0], (unsigned long long)UTREE_TALLY_CHUNK);
+                    // (the workspace is sized so that this cannot happen, dev_image.c: carve; if it does, the batch is reported as failed
+                    // and the wave writes into the first chunk instead of past the end)
+                    if (nb + UTREE_TALLY_CHUNK > ws.tally_cap) { ws.cursors[UTREE_CUR_ERROR] = UTREE_DEVERR_TALLY_CAP; nb = 0; }
+                }
+                chunk_base = uni64(nb);
+                chunk_left = UTREE_TALLY_CHUNK;
             }
-            chunk_base = uni64(nb);
-            chunk_left = UTREE_TALLY_CHUNK;
-        }
-        const unsigned long long my_base = chunk_base + (incl - need);
-        chunk_base += total; chunk_left -= total;
-        // ascending rank = strcmp order (itree.c:1041): an entry's place is the number of the read's labels below its own
-        if (maxnu >= 2u) {
+            my_base = chunk_base + (incl - need);
+            chunk_base += total; chunk_left -= total;
+            // ascending rank = strcmp order (itree.c:1041): an entry's place is the number of the read's labels below its own
             for (uint32_t i = 0; i < maxnu; ++i) {
                 const uint32_t e = tq[i * RPW];
                 uint32_t place = 0;
@@ -923,6 +928,13 @@ _Pragma("unroll") for (uint32_t x = 0; x < NA; ++x) { A[x] = RA[x]; B[x] = RB[x]
         if (live) {
             if (F == 0) store_result(&out[r], 0, -2, 0, 0, 0, 0);
             else if (nu == 1) store_result(&out[r], first_rank, RANK_PENDING, F, 1, 0, 0);      // (vote_k looks the file-order index up: doing it here is +-0, same box)
+            else if (!need) {
+                // two or three labels, packed: they stand in the read's slots 0 .. 2 (a table fills from slot 0; an unused one is all ones), and a slot
+                // word's top bits are its rank, no two alike: the words in ascending order are the list in ascending rank -- three min / max pairs
+                const uint32_t e0 = tq[0], e1 = tq[RPW], e2 = tq[2u * RPW];
+                const uint32_t lo = umin(e0, e1), hi = e0 ^ e1 ^ lo, m = umin(hi, e2);
+                store_result(&out[r], umin(lo, m), CUT_INLINE, F, nu, lo ^ m ^ umin(lo, m), hi ^ e2 ^ m);
+            }
             else store_result(&out[r], 0, CUT_PENDING, F, nu, (uint32_t)my_base, (uint32_t)(my_base >> 32));
         }
         wave_lds_fence();

@@ -24,6 +24,7 @@ namespace {
 
 constexpr uint32_t LCAP = UTREE_LANES_CAP;            // bases a lane's slot holds
 constexpr int32_t CUT_PENDING = -3, RANK_PENDING = -4;   // as in kernels.hip (vote_k finishes those results)
+[[maybe_unused]] constexpr int32_t CUT_INLINE = -5;      // (lanes_core.hpp writes those; the kernels here list every read they finish)
 __device__ __forceinline__ uint64_t ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 __device__ __forceinline__ void store_result(utree_result *out, uint32_t label, int32_t cut, uint32_t found, uint32_t uix, uint32_t sl, uint32_t ol) {
     uint32_t *o = (uint32_t *)out;

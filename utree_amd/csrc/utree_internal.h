@@ -170,6 +170,8 @@ typedef struct {
     uint32_t *cls_list;              /* [5][cls_stride]; NULL: the batch is not routed                           */
     uint32_t cls_stride;
     uint64_t ltally_base;            /* ws.tally index of the long reads' (rank, count) lists: UTREE_LONG_SLOTS each */
+    uint32_t tally_inline;           /* != 0: the lane-per-read pass keeps a read's two or three (rank, count) entries in its pending record (CUT_INLINE,
+                                      * kernels.hip) instead of a list; set per batch, only when nothing but the vote reads the pending records */
 } utk_workspace;
 
 int utk_classify_short(const utk_image *im, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
