@@ -280,12 +280,13 @@ typedef struct {
     uint64_t bytes_in, bytes_out;
 } utree_search_stats;
 
+/* utree_search_run (below) with reads_path = fasta_path, out_path, do_rc, host_threads set. */
 int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path,
                       const char *out_path, int do_rc, int host_threads, utree_search_stats *stats);
 /* Optional: allocate the search's pinned and device buffers now (they are kept in the device handles and reused by later
  * searches), so that the first search does not pay for them -- "database resident" then includes them. */
 int utree_search_prepare(const utree_ctr *ctr, utree_dev **devs, int n_dev, int do_rc);
-/* Same with an opt-in input format (UTREE_INPUT_*; AUTO looks at the first byte); gzip input is read through zlib. */
+/* ... and input_format. */
 int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path,
                            const char *out_path, int do_rc, int host_threads, int input_format, utree_search_stats *stats);
 
@@ -320,7 +321,7 @@ int utree_rank_reset(utree_dev *dev);
 size_t utree_format_rank_records(const utree_ctr *ctr, const uint8_t *h_buf, const uint64_t *name_off,
                                  const uint32_t *name_len, const utree_result *h_res, size_t n, char *h_out, size_t cap,
                                  uint64_t *good_finds);
-/* Whole file on ONE device image (the reference runs this branch on one thread); resets the carried array first. */
+/* utree_search_run with rank = params on the one handle `dev`, and reads_path, out_path, do_rc, host_threads set; _opts: and input_format. */
 int utree_rank_search_file(const utree_ctr *ctr, utree_dev *dev, const char *fasta_path, const char *out_path,
                            int do_rc, const utree_rank_params *params, int host_threads, utree_search_stats *stats);
 int utree_rank_search_file_opts(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path,
@@ -361,12 +362,7 @@ void utree_profile_free(utree_profile *p);
 /* Host: entries from any number of devices (label indices of ctr) -> merged by text, rolled up, written to `path` in the layout
  * above; classified = the sum of the entries' reads. */
 int utree_profile_write(const utree_ctr *ctr, const utree_profile_entry *e, size_t n, uint64_t n_reads, const char *path);
-/* utree_search_file_opts / utree_rank_search_file_opts that also write the profile of the search to `profile_path` (NULL: no
- * profile, no extra launch).  The per-read output and the stats are those of the plain call, and so is the return code of a search
- * that fails (the profile file is then left as it was).  When the search succeeds but its profile cannot be written -- the file
- * cannot be created or written, the table of truncated taxa was too small, the devices did not count every read once -- the call
- * returns UTREE_E_PROFILE and utree_last_hip_error says which.  Each device handle counts its own reads (truncated-taxon slots:
- * UTREE_PROFILE_CAPACITY, default 2^20). */
+/* utree_search_file_opts / utree_rank_search_file_opts with profile_path set as well. */
 int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
                               int do_rc, int host_threads, int input_format, const char *profile_path, utree_search_stats *stats);
 int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
@@ -411,10 +407,7 @@ int utree_coverage_read(utree_coverage *c, utree_coverage_entry *h, size_t cap, 
 void utree_coverage_free(utree_coverage *c);
 /* Host only: entries (label indices of ctr; several with one label are added up) -> merged by text, rolled up, written to `path`. */
 int utree_coverage_write(const utree_ctr *ctr, const utree_coverage_entry *e, size_t n, uint64_t n_reads, const char *path);
-/* utree_search_file_profile that also writes the coverage of the search to `coverage_path` (NULL: exactly utree_search_file_profile -- no
- * handle, no launch).  One coverage handle per device handle, merged before the file is written.  A search that succeeds but whose coverage
- * cannot be written returns UTREE_E_COVERAGE (utree_last_hip_error says why; a profile that failed too keeps UTREE_E_PROFILE); a search that
- * fails leaves the path as it was. */
+/* utree_search_file_profile with coverage_path set as well. */
 int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
                                int host_threads, int input_format, const char *profile_path, const char *coverage_path,
                                utree_search_stats *stats);
@@ -453,9 +446,7 @@ typedef struct {
 int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_off1, const uint32_t *d_len1, const uint8_t *d_bases2,
                      const uint64_t *d_off2, const uint32_t *d_len2, uint32_t n_pairs, uint8_t *d_joined, uint64_t joined_capacity,
                      uint64_t *d_joff, uint32_t *d_jlen, utree_pairs_meta *d_meta, void *stream);
-/* utree_search_file_coverage over pairs: mates_path = the file of second mates, or NULL when reads_path is interleaved.  Always the host
- * framing pipeline (stats.pipeline == 0), any input_format, plain or -- with a non-reference format -- gzip.  profile_path / coverage_path
- * and their errors exactly as for utree_search_file_coverage; both reports see the joined queries (no window crosses the 'N'). */
+/* utree_search_file_coverage with mates_path set as well, or -- mates_path NULL -- interleaved = 1. */
 int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
                             const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
                             const char *coverage_path, utree_search_stats *stats);
@@ -522,14 +513,7 @@ int utree_redist_solve(utree_redist *rd, uint32_t max_passes, utree_redist_entry
 /* Host only: entries (label indices of ctr; several with one label are added up) -> merged by text, rolled up, written to `path`. */
 int utree_redist_write(const utree_ctr *ctr, const utree_redist_entry *e, size_t n, uint64_t n_reads, uint64_t ambiguous, uint32_t passes,
                        const char *path);
-/* utree_search_pairs_file that also writes the redistribution of the search to `redistribute_path` (NULL: exactly the existing calls -- no
- * handle, no launch).  Single reads: mates_path NULL and interleaved 0 (then the pipelines of utree_search_file_coverage); pairs: mates_path,
- * or interleaved != 0.  One handle per device handle (UTREE_REDIST_CAPACITY slots, default 2^22), merged into the first and solved with
- * max_passes (0: the default) before the file is written -- after the coverage, before the profile.  A search that succeeds but whose
- * redistribution cannot be written -- the file, a table too small, the devices did not add every read once -- returns UTREE_E_PROFILE (there
- * is no code of its own) and utree_last_hip_error names the redistribution file and the cause; a search that fails leaves the path as it was.
- * (A search into a pipe that the host pipeline has to take over half-way cannot take back the sets of the chunks it drops: it ends with this
- * error rather than a wrong table.) */
+/* utree_search_file_coverage with mates_path, interleaved, redistribute_path and max_passes set as well. */
 int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
                                    int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
                                    const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
@@ -571,12 +555,7 @@ int utree_hitmap_batch(utree_dev *dev, const uint8_t *d_bases, const uint64_t *d
  * h_run_off: n + 1 entries into h_runs.  Returns bytes written, or (size_t)-1 if cap is too small. */
 size_t utree_hitmap_format(const uint8_t *h_buf, const uint64_t *name_off, const uint32_t *name_len, const uint64_t *h_run_off,
                            const utree_hit_run *h_runs, size_t n, char *h_out, size_t cap);
-/* utree_search_file_redistribute that also writes the search's hit map to `hitmap_path` (NULL: exactly that call -- nothing allocated,
- * nothing launched) and the label texts to <hitmap_path>.labels, line i (0-based) = label index i.  The map is written in step with the
- * output: the writer stage commits a chunk's output lines and its map lines together, so after a framing error or UTREE_E_PAIRS both files
- * hold the same queries.  The per-read output, stdout, the stats and every other report are those of a search without it.  Always the host
- * framing pipeline (stats.pipeline == 0), as for pairs.  A search that succeeds but whose hit map (or its .labels) cannot be written
- * returns UTREE_E_HITMAP and utree_last_hip_error says why (a report that failed too keeps its own code). */
+/* utree_search_file_redistribute with hitmap_path set as well. */
 int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
                              int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
                              const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
@@ -640,17 +619,12 @@ typedef struct {
  * taxa by printed text, so several devices may number their samples independently.  UTREE_E_ARG when the figures contradict each other (a
  * sample's reads are not its unclassified reads plus its cells, the samples' reads not n_reads, a cell names no sample or label). */
 int utree_samples_write(const utree_ctr *ctr, const utree_samples_table *tabs, size_t n_tabs, const char *path);
-/* utree_search_file_hitmap that also writes the search's sample table to `samples_path` (NULL: exactly that call -- nothing allocated, uploaded
- * or launched), ids cut at `delim` (0: '_').  The per-read output, stdout, the stats and every other report are those of a search without it,
- * and so is the pipeline: a search the device text pipeline takes stays there (stats.pipeline == 1).  The table is written after the
- * redistribution and before the profile, when the search has succeeded and exactly its reads were added; a table that cannot be written -- the
- * file, a capacity (UTREE_SAMPLE_CAPACITY, default 2^16 ids; UTREE_SAMPLE_CELLS, default 2^22 cells) -- returns UTREE_E_PROFILE (there is no
- * code of its own) and utree_last_hip_error names the table's file and the cause; a search that fails leaves the path as it was. */
+/* utree_search_file_hitmap with samples_path and sample_delim = delim set as well. */
 int utree_search_file_samples(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
                               int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
                               const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
                               const char *hitmap_path, const char *samples_path, int delim, utree_search_stats *stats);
-/* utree_rank_search_file_profile with the same two arguments: the rank-specific search's records make the same table. */
+/* utree_rank_search_file_profile with samples_path and sample_delim = delim set as well. */
 int utree_rank_search_file_samples(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
                                    const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
                                    const char *samples_path, int delim, utree_search_stats *stats);
@@ -735,17 +709,60 @@ int utree_sredist_solve(utree_sredist *h, uint32_t max_passes, utree_sredist_ent
 int utree_sredist_write(const utree_ctr *ctr, const uint8_t *ids, const uint64_t *id_off, const uint64_t *reads, const uint64_t *unclassified,
                         const uint32_t *passes, const uint64_t *ambiguous, size_t n_samples, const utree_sredist_entry *e, size_t n_entries,
                         uint64_t n_reads, const char *path);
-/* utree_search_file_samples that also writes this report to `sample_redistribute_path` (NULL: exactly that call -- nothing allocated, uploaded
- * or launched), ids cut at `delim`, at most max_passes passes per sample (0: the default).  The per-read output, stdout, the stats, the
- * pipeline and every other report are those of a search without it.  One handle per device handle (UTREE_SAMPLE_CAPACITY ids,
- * UTREE_REDIST_CAPACITY sets, UTREE_SAMPLE_CELLS cells), merged into the first and solved before the file is written -- after the sample table,
- * before the profile.  A report that cannot be written returns UTREE_E_PROFILE and utree_last_hip_error names its file and the cause (the
- * profile's failure wins, then the redistribution's, the sample table's, this report's); a search that fails leaves the path as it was. */
+/* utree_search_file_samples with sample_redistribute_path set as well: every field of the GG search's request. */
 int utree_search_file_sample_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
                                           int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
                                           const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
                                           const char *hitmap_path, const char *samples_path, int delim, const char *sample_redistribute_path,
                                           utree_search_stats *stats);
+
+/* ------------------------------------------------------------------------------------------------
+ * One whole-file search, described by one request.  Every utree_search_file* / utree_search_pairs_file / utree_rank_search_file* entry point
+ * above is a fixed-argument form of this call: it fills the fields its comment names, leaves the rest 0 / NULL and calls utree_search_run.
+ * A report's path that is NULL means: no such report -- nothing of it is allocated, uploaded or launched, and the per-read output, stdout, the
+ * stats and the other reports are those of a search without it.  A search that fails returns its own code and leaves every report path as it
+ * was; the reports are written when the search has succeeded, in the order coverage, redistribution, sample table, per-sample
+ * redistribution, profile, and only when the devices counted every read exactly once.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t size;                    /* = sizeof(utree_search_request): anything else is UTREE_E_ARG (a caller built against another layout) */
+    int do_rc, host_threads;          /* RC; the host formatting team (<= 0: as many as OpenMP gives, at most 16)                              */
+    int input_format;                 /* UTREE_INPUT_*; AUTO looks at the first byte; a non-reference format also reads gzip through zlib       */
+    const char *reads_path;           /* the reads; with mates_path the first mates; with interleaved records 2i and 2i+1 are pair i           */
+    const char *mates_path;           /* NULL, or the file of second mates (not with interleaved).  Pairs take the host framing pipeline
+                                         (stats.pipeline == 0) and every report sees the joined queries (no window crosses the 'N')           */
+    int interleaved;
+    const char *out_path;
+    const utree_rank_params *rank;    /* non-NULL: the rank-specific search on ONE device handle (n_dev must be 1), whose carried array is reset
+                                         first (utree_rank_reset).  It reads no pairs and writes a profile and a sample table only: any of
+                                         coverage_path, redistribute_path, hitmap_path, sample_redistribute_path is UTREE_E_ARG                */
+    const char *profile_path;         /* per-taxon read counts, each device handle counting its own reads (UTREE_PROFILE_CAPACITY truncated-taxon
+                                         slots, default 2^20).  Not written: UTREE_E_PROFILE, utree_last_hip_error says why                   */
+    const char *coverage_path;        /* distinct database k-mers covered per taxon; one handle per device handle, merged before the file is
+                                         written.  Not written: UTREE_E_COVERAGE (a profile that failed too keeps UTREE_E_PROFILE)            */
+    const char *redistribute_path;    /* ambiguous reads redistributed among tied labels; one handle per device handle (UTREE_REDIST_CAPACITY
+                                         slots, default 2^22), merged into the first and solved.  Not written -- the file, a table too small,
+                                         reads not added once --: UTREE_E_PROFILE (no code of its own), utree_last_hip_error names the file and
+                                         the cause.  (A search into a pipe that the host pipeline has to take over half-way cannot take back the
+                                         sets of the chunks it drops: it ends with this error rather than a wrong table.)                      */
+    uint32_t max_passes;              /* of both redistributions (0: the default; more than 1000 with either path: UTREE_E_ARG)               */
+    const char *hitmap_path;          /* every query's hit map, and the label texts to <hitmap_path>.labels, line i (0-based) = label index i.
+                                         Written in step with the output: the writer stage commits a chunk's output lines and its map lines
+                                         together, so after a framing error or UTREE_E_PAIRS both files hold the same queries.  Always the host
+                                         framing pipeline.  Not written: UTREE_E_HITMAP (a report that failed too keeps its own code)         */
+    const char *samples_path;         /* taxon x sample table, ids cut at sample_delim.  The pipeline stays what it would be (a search the device
+                                         text pipeline takes stays there).  Not written -- the file, a capacity (UTREE_SAMPLE_CAPACITY, default
+                                         2^16 ids; UTREE_SAMPLE_CELLS, default 2^22 cells) --: UTREE_E_PROFILE, as for redistribute_path      */
+    const char *sample_redistribute_path;  /* that table with every sample's ambiguous reads redistributed within the sample; one handle per
+                                         device handle (UTREE_SAMPLE_CAPACITY ids, UTREE_REDIST_CAPACITY sets, UTREE_SAMPLE_CELLS cells).  Not
+                                         written: UTREE_E_PROFILE (the profile's failure wins, then the redistribution's, the sample table's,
+                                         this report's)                                                                                       */
+    int sample_delim;                 /* one byte, 0: '_'; with either sample report not TAB, space, CR or LF (UTREE_E_ARG)                    */
+} utree_search_request;
+/* The one call that checks a request and runs it: GG search over devs[0 .. n_dev), or the rank-specific one.  Every argument is checked before
+ * `ctr` or a device handle is looked at: UTREE_E_ARG for a wrong size, a NULL ctr, devs, reads_path or out_path, n_dev < 1, an input_format
+ * that is none, mates_path together with interleaved, and what the fields above say. */
+int utree_search_run(const utree_ctr *ctr, utree_dev **devs, int n_dev, const utree_search_request *req, utree_search_stats *stats);
 
 /* ------------------------------------------------------------------------------------------------
  * `.ubt` -> `.ctr` = XT_cmp32(filename, outfile) (itree.c:1234-1315; `xtree-compress`), SURVEY.md §8(f) rank 2.

@@ -856,7 +856,7 @@ static void carve(const utree_dev *d, void *ws, uint32_t n_reads, uint64_t total
      * per batch, the workspace's size must not depend on that.) */
     w->pieces = NULL; w->ltab_rank = w->ltab_cnt = w->lflag = w->long_left = NULL; w->n_long_cap = 0; w->ltally_base = 0;
     w->cls_list = NULL; w->cls_stride = 0; w->n_pieces_cap = 0;
-    w->tally_inline = 0;                                               /* (the batch's choice: utree_classify_batch_reports) */
+    w->tally_inline = 0;                                               /* (the batch's choice: utree_classify_view) */
     if (lanes_img && max_len > UTREE_LANES_CAP) {
         w->cls_stride = (n_reads + 63u) & ~63u;
         w->cls_list = (uint32_t *)(b + off); off = align_up(off + (uint64_t)5 * w->cls_stride * 4, 256);
@@ -892,28 +892,22 @@ size_t utree_classify_workspace_bytes(const utree_dev *dev, uint32_t n_reads, ui
 int utree_classify_batch(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
                          uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out,
                          void *d_workspace, size_t workspace_bytes, void *stream) {
-    return utree_classify_batch_redist(d, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream, NULL);
+    const utree_batch_view v = {d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, NULL, 0, NULL, NULL, stream};
+    return utree_classify_view(d, &v, d_out, d_workspace, workspace_bytes, NULL, NULL);
 }
 
 /* rd: NULL (utree_classify_batch: nothing new is launched), or the redistribution handle the batch's candidate sets go into -- one more
- * pass over the records between the classify kernels and the vote, while each read's (rank, count) list still stands (redist.c) */
-int utree_classify_batch_redist(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
-                                uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out,
-                                void *d_workspace, size_t workspace_bytes, void *stream, struct utree_redist *rd) {
-    return utree_classify_batch_reports(d, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream, rd,
-                                        NULL, NULL, 0, NULL, NULL);
-}
-
-/* srd: NULL, or the handle the batch's reads are counted in per (sample, candidate set), at the same place and from the same lists (sredist.c) */
-int utree_classify_batch_reports(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
-                                 uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out,
-                                 void *d_workspace, size_t workspace_bytes, void *stream, struct utree_redist *rd, struct utree_sredist *srd,
-                                 const uint8_t *d_text, uint64_t text_bytes, const uint32_t *d_name_off, const uint32_t *d_name_len) {
+ * pass over the records between the classify kernels and the vote, while each read's (rank, count) list still stands (redist.c); srd: NULL,
+ * or the handle the batch's reads are counted in per (sample, candidate set), at the same place and from the same lists (sredist.c) */
+int utree_classify_view(utree_dev *d, const utree_batch_view *v, utree_result *d_out, void *d_workspace, size_t workspace_bytes,
+                        struct utree_redist *rd, struct utree_sredist *srd) {
+    const uint8_t *d_bases = v->d_bases; const uint64_t *d_off = v->d_off; const uint32_t *d_len = v->d_len;
+    const uint32_t n_reads = v->n_reads, max_len = v->max_len; const uint64_t total_bases = v->total_bases; const int do_rc = v->do_rc;
     int rc = UTREE_OK;
     if (!d || !d_out || (!d_workspace && n_reads)) return UTREE_E_ARG;
     if (!n_reads) return UTREE_OK;
     if (!d_bases || !d_off || !d_len) return UTREE_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)v->stream;
     utk_workspace w; size_t need;
     carve(d, d_workspace, n_reads, total_bases, max_len, do_rc, &w, &need);
     if (workspace_bytes < need) return UTREE_E_ARG;
@@ -991,7 +985,7 @@ int utree_classify_batch_reports(utree_dev *d, const uint8_t *d_bases, const uin
         }
     }
     if (rd && (rc = utree_redist_add_pending(rd, &d->kimg, d_out, &w, n_reads, d->n_cu, st))) goto fail;     /* every path has converged here */
-    if (srd && (rc = utree_sredist_add_pending(srd, &d->kimg, d_out, &w, d_text, text_bytes, d_name_off, d_name_len, n_reads, d->n_cu, st))) goto fail;
+    if (srd && (rc = utree_sredist_add_pending(srd, &d->kimg, d_out, &w, v->d_text, v->text_bytes, v->d_name_off, v->d_name_len, n_reads, d->n_cu, st))) goto fail;
     KCHK(utk_vote(&d->kimg, d_out, &w, n_reads, st));
     /* the reads the lane pass left, and the batch's error word, come back behind the kernels without a wait */
     if (ring_post(d, &w, lanes ? n_reads : 0, st)) { (void)hipGetLastError(); }

@@ -37,20 +37,16 @@ struct utree_dev {
     void *search_ctx;
 };
 
-/* utree_classify_batch with the candidate sets of the batch added to `rd` (NULL: none) in front of the vote; redist.c */
+/* utree_classify_batch on a view, with the batch's candidate sets -- one more pass between the classify kernels and the vote, while each read's
+ * (rank, count) list still stands -- added to `rd` (NULL: not; redist.c) and / or, with the view's names, counted per (sample, candidate set)
+ * in `srd` (NULL: not; sredist.c).  Both NULL: nothing more is launched and the names are not read */
 struct utree_redist;
-int utree_classify_batch_redist(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads,
-                                uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace, size_t workspace_bytes,
-                                void *stream, struct utree_redist *rd);
+struct utree_sredist;
+int utree_classify_view(utree_dev *d, const utree_batch_view *v, utree_result *d_out, void *d_workspace, size_t workspace_bytes,
+                        struct utree_redist *rd, struct utree_sredist *srd);
 int utree_redist_add_pending(struct utree_redist *rd, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, uint32_t n_reads,
                              int n_cu, void *stream);
 int utree_redist_reads(struct utree_redist *rd, uint64_t *n_reads);
-/* ... and / or, with the reads' names (as utree_samples_add takes them), counted per (sample, candidate set) in `srd` (NULL: not); sredist.c */
-struct utree_sredist;
-int utree_classify_batch_reports(utree_dev *d, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads,
-                                 uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace, size_t workspace_bytes,
-                                 void *stream, struct utree_redist *rd, struct utree_sredist *srd, const uint8_t *d_text, uint64_t text_bytes,
-                                 const uint32_t *d_name_off, const uint32_t *d_name_len);
 int utree_sredist_add_pending(struct utree_sredist *h, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, const uint8_t *d_text,
                               uint64_t text_bytes, const uint32_t *d_name_off, const uint32_t *d_name_len, uint32_t n_reads, int n_cu, void *stream);
 int utree_sredist_reads(struct utree_sredist *h, uint64_t *n_reads);

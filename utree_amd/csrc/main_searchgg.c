@@ -55,7 +55,7 @@
  *                           the convention as for UTREE_SAMPLE_TABLE.  Unset: nothing is allocated, uploaded or launched
  *     UTREE_MATES=<path>    opt-in, xtree-searchGG only: paired-end reads.  fastaToSearch.fa holds the first mates, <path> the second; pair i is
  *                           record i of both.  A pair is searched as ONE query, mate 1 + "N" + mate 2, and prints one line under mate 1's name
- *                           (include/utree_amd.h: utree_search_pairs_file; mate names are not compared); "Searched N queries" and the profile
+ *                           (include/utree_amd.h: utree_search_request; mate names are not compared); "Searched N queries" and the profile
  *                           count pairs.  Works with UTREE_INPUT, UTREE_PROFILE and UTREE_COVERAGE.  A mates file that cannot be opened:
  *                           "Invalid input files", exit 1, before the tree is loaded.  Files of unequal record counts: the complete pairs are
  *                           written, a message on stderr, exit 2
@@ -116,6 +116,10 @@ int main(int argc, char *argv[]) {
 #endif
     printf("Using up to %d threads.\n", threads);
 
+    /* everything the environment asks for goes into ONE request; what the rank-specific search has no use for is not read (or, where a user
+     * would wonder, refused or reported) */
+    utree_search_request req = {.size = sizeof req, .do_rc = doRC, .host_threads = threads, .input_format = UTREE_INPUT_REFERENCE,
+                                .reads_path = argv[2], .out_path = argv[3], .sample_delim = '_'};
     const char *mates = getenv("UTREE_MATES");
     const char *ei_pairs = getenv("UTREE_INTERLEAVED");
     const int interleaved = ei_pairs && *ei_pairs && strcmp(ei_pairs, "0");
@@ -127,34 +131,29 @@ int main(int argc, char *argv[]) {
         if (f < 0) { puts("Invalid input files"); exit(1); }                             /* itree.c:835 */
         close(f);
     }
-    const char *profile = getenv("UTREE_PROFILE");
-    if (profile && *profile) check_report_path(profile, "profile"); else profile = NULL;
-    const char *coverage = DO_GG ? getenv("UTREE_COVERAGE") : NULL;
-    if (coverage && *coverage) check_report_path(coverage, "coverage"); else coverage = NULL;
-    const char *redist = DO_GG ? getenv("UTREE_REDISTRIBUTE") : NULL;
-    if (redist && *redist) check_report_path(redist, "redistribution"); else redist = NULL;
-    const char *sredist = DO_GG ? getenv("UTREE_SAMPLE_REDISTRIBUTE") : NULL;
-    if (sredist && *sredist) check_report_path(sredist, "sample redistribution"); else sredist = NULL;
-    unsigned redist_passes = 0;                                                           /* 0: the default */
-    if ((redist || sredist) && getenv("UTREE_REDIST_PASSES")) {
+    req.mates_path = mates; req.interleaved = interleaved;
+    /* the reports: a path that is unset or empty is no report; the others must be writable now */
+    const char *p;
+    if ((p = getenv("UTREE_PROFILE")) && *p) { check_report_path(p, "profile"); req.profile_path = p; }
+    if (DO_GG && (p = getenv("UTREE_COVERAGE")) && *p) { check_report_path(p, "coverage"); req.coverage_path = p; }
+    if (DO_GG && (p = getenv("UTREE_REDISTRIBUTE")) && *p) { check_report_path(p, "redistribution"); req.redistribute_path = p; }
+    if (DO_GG && (p = getenv("UTREE_SAMPLE_REDISTRIBUTE")) && *p) { check_report_path(p, "sample redistribution"); req.sample_redistribute_path = p; }
+    if ((req.redistribute_path || req.sample_redistribute_path) && getenv("UTREE_REDIST_PASSES")) {   /* (else 0: the default) */
         const long v = atol(getenv("UTREE_REDIST_PASSES"));
         if (v < 1 || v > 1000) { fputs("ERROR: UTREE_REDIST_PASSES must be 1 .. 1000\n", stderr); exit(1); }
-        redist_passes = (unsigned)v;
+        req.max_passes = (uint32_t)v;
     }
-    const char *hitmap = getenv("UTREE_HITMAP");
-    if (hitmap && !*hitmap) hitmap = NULL;
-    if (hitmap && !DO_GG) { fputs("[utree_amd] UTREE_HITMAP is ignored: the rank-specific search looks at a hit-dependent subset of windows and has no hit map\n", stderr); hitmap = NULL; }
-    if (hitmap) check_report_path(hitmap, "hit map");
-    (void)redist_passes;                                                                  /* (xtree-search: no redistribution) */
-    const char *samples = getenv("UTREE_SAMPLE_TABLE");
-    if (samples && *samples) check_report_path(samples, "sample table"); else samples = NULL;
-    int sample_delim = '_';
+    if ((p = getenv("UTREE_HITMAP")) && *p) {
+        if (DO_GG) { check_report_path(p, "hit map"); req.hitmap_path = p; }
+        else fputs("[utree_amd] UTREE_HITMAP is ignored: the rank-specific search looks at a hit-dependent subset of windows and has no hit map\n", stderr);
+    }
+    if ((p = getenv("UTREE_SAMPLE_TABLE")) && *p) { check_report_path(p, "sample table"); req.samples_path = p; }
     const char *sd = getenv("UTREE_SAMPLE_DELIM");
     if (sd) {
         if (strlen(sd) != 1 || sd[0] == '\t' || sd[0] == ' ' || sd[0] == '\r' || sd[0] == '\n') {
             fputs("ERROR: UTREE_SAMPLE_DELIM must be one byte, and not TAB, space, CR or LF\n", stderr); exit(1);
         }
-        sample_delim = (unsigned char)sd[0];
+        req.sample_delim = (unsigned char)sd[0];
     }
 
     utree_ctr *ctr = NULL;
@@ -213,26 +212,19 @@ int main(int argc, char *argv[]) {
     fflush(stdout);
 
     utree_search_stats st;
-    int fmt = UTREE_INPUT_REFERENCE;
     const char *ei = getenv("UTREE_INPUT");
-    if (ei && !strcmp(ei, "auto")) fmt = UTREE_INPUT_AUTO;
-    else if (ei && !strcmp(ei, "fastq")) fmt = UTREE_INPUT_FASTQ;
-    else if (ei && !strcmp(ei, "fasta")) fmt = UTREE_INPUT_FASTA_MULTILINE;
+    if (ei && !strcmp(ei, "auto")) req.input_format = UTREE_INPUT_AUTO;
+    else if (ei && !strcmp(ei, "fastq")) req.input_format = UTREE_INPUT_FASTQ;
+    else if (ei && !strcmp(ei, "fasta")) req.input_format = UTREE_INPUT_FASTA_MULTILINE;
 #ifdef UTREE_RANK_SPECIFIC
     utree_rank_params prm;
     utree_rank_params_default(&prm);
     if (getenv("UTREE_SLACK")) prm.slack = (uint32_t)atoi(getenv("UTREE_SLACK"));
     if (getenv("UTREE_SPARSITY")) prm.sparsity = (uint32_t)atoi(getenv("UTREE_SPARSITY"));
     if (getenv("UTREE_TOLERANCE")) prm.tolerance = (uint32_t)atoi(getenv("UTREE_TOLERANCE"));
-    rc = utree_rank_search_file_samples(ctr, devs[0], argv[2], argv[3], doRC, &prm, threads, fmt, profile, samples, sample_delim, &st);   /* (a NULL path: no such report) */
-#else
-    if (sredist) rc = utree_search_file_sample_redistribute(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, samples, sample_delim, sredist, &st);
-    else if (samples) rc = utree_search_file_samples(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, samples, sample_delim, &st);
-    else if (hitmap) rc = utree_search_file_hitmap(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, hitmap, &st);
-    else if (redist) rc = utree_search_file_redistribute(ctr, devs, n_dev, argv[2], mates, interleaved, argv[3], doRC, threads, fmt, profile, coverage, redist, redist_passes, &st);
-    else if (mates || interleaved) rc = utree_search_pairs_file(ctr, devs, n_dev, argv[2], mates, argv[3], doRC, threads, fmt, profile, coverage, &st);
-    else rc = utree_search_file_coverage(ctr, devs, n_dev, argv[2], argv[3], doRC, threads, fmt, profile, coverage, &st);   /* (a NULL path: no such report) */
+    req.rank = &prm;
 #endif
+    rc = utree_search_run(ctr, devs, n_dev, &req, &st);
     if (rc == UTREE_E_IO) { puts("Invalid input files"); exit(1); }                      /* itree.c:835 */
     if (rc == UTREE_E_FASTA) {
         switch (st.fasta_error.code) {                                                    /* itree.c:872, 880, 886, 888 */

@@ -2,7 +2,7 @@
  *
  * A read's candidate set is the labels tied for its highest hit count; the handle keeps every distinct set with its read count on the device
  * for a whole search (redist_kernels.hip: a counter per label for the single-candidate reads, a table of the multi-label sets, their members
- * in an arena), fed by one pass per batch between the classify kernels and the vote (utree_classify_batch_redist, dev_image.c).  The passes
+ * in an arena), fed by one pass per batch between the classify kernels and the vote (utree_classify_view, dev_image.c).  The passes
  * iterate there: each set goes to its richest member under the previous tally until the tallies stop moving; the host reads one word per
  * pass.  Entries of all labels are merged by label text, rolled up over the ';'-prefixes and written as
  *
@@ -89,7 +89,8 @@ int utree_redist_classify_batch(utree_redist *rd, utree_dev *dev, const uint8_t 
                                 uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace,
                                 size_t workspace_bytes, void *stream) {
     if (!rd || !dev || rd->device != dev->device || rd->n_labels != dev->hdr.n_labels) return UTREE_E_ARG;
-    return utree_classify_batch_redist(dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream, rd);
+    const utree_batch_view v = {d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, NULL, 0, NULL, NULL, stream};
+    return utree_classify_view(dev, &v, d_out, d_workspace, workspace_bytes, rd, NULL);
 }
 
 /* the handle's error word as a code and a text */

@@ -14,32 +14,28 @@ struct utree_reports {
     struct { utree_profile *prof; utree_coverage *cov; utree_redist *rd; utree_samples *smp; utree_sredist *srd; } dev[];      /* NULL: the search writes no such report */
 };
 
-int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *profile_path, const char *coverage_path,
-                         const char *redist_path, uint32_t redist_passes, const char *samples_path, int samples_delim, const char *sredist_path,
-                         utree_reports **out) {
+int utree_reports_create(const utree_ctr *ctr, utree_dev **devs, int n_dev, const utree_search_request *req, utree_reports **out) {
     *out = NULL;
-    if (!profile_path && !coverage_path && !redist_path && !samples_path && !sredist_path) return UTREE_OK;
-    if ((redist_path || sredist_path) && redist_passes > 1000) return UTREE_E_ARG;
-    if (!ctr || !devs || n_dev < 1) return UTREE_E_ARG;
+    if (!req->profile_path && !req->coverage_path && !req->redistribute_path && !req->samples_path && !req->sample_redistribute_path) return UTREE_OK;
     utree_reports *rep = (utree_reports *)calloc(1, sizeof *rep + (size_t)n_dev * sizeof rep->dev[0]);
     if (!rep) return UTREE_E_NOMEM;
-    rep->n_dev = n_dev; rep->profile_path = profile_path; rep->coverage_path = coverage_path; rep->redist_path = redist_path;
-    rep->samples_path = samples_path; rep->sredist_path = sredist_path;
-    rep->redist_passes = redist_passes ? redist_passes : UTREE_REDIST_DEFAULT_PASSES;
+    rep->n_dev = n_dev; rep->profile_path = req->profile_path; rep->coverage_path = req->coverage_path; rep->redist_path = req->redistribute_path;
+    rep->samples_path = req->samples_path; rep->sredist_path = req->sample_redistribute_path;
+    rep->redist_passes = req->max_passes ? req->max_passes : UTREE_REDIST_DEFAULT_PASSES;
+    const int delim = req->sample_delim ? req->sample_delim : '_';
     const char *e = getenv("UTREE_PROFILE_CAPACITY");
     const uint32_t cap = e && atoll(e) >= 1 && atoll(e) <= (1ll << 30) ? (uint32_t)atoll(e) : UTREE_PROFILE_DEFAULT_CAPACITY;
     int rc = UTREE_OK;
-    for (int g = 0; profile_path && g < n_dev && !rc; ++g) rc = utree_profile_create(devs[g], cap, &rep->dev[g].prof);
-    for (int g = 0; coverage_path && g < n_dev && !rc; ++g) rc = utree_coverage_create(ctr, devs[g], NULL, NULL, &rep->dev[g].cov);
+    for (int g = 0; rep->profile_path && g < n_dev && !rc; ++g) rc = utree_profile_create(devs[g], cap, &rep->dev[g].prof);
+    for (int g = 0; rep->coverage_path && g < n_dev && !rc; ++g) rc = utree_coverage_create(ctr, devs[g], NULL, NULL, &rep->dev[g].cov);
     const char *er = getenv("UTREE_REDIST_CAPACITY");
     const uint32_t rcap = er && atoll(er) >= 1 && atoll(er) <= (1ll << 28) ? (uint32_t)atoll(er) : UTREE_REDIST_DEFAULT_CAPACITY;
-    for (int g = 0; redist_path && g < n_dev && !rc; ++g) rc = utree_redist_create(devs[g], rcap, &rep->dev[g].rd);
+    for (int g = 0; rep->redist_path && g < n_dev && !rc; ++g) rc = utree_redist_create(devs[g], rcap, &rep->dev[g].rd);
     const char *es = getenv("UTREE_SAMPLE_CAPACITY"), *ec = getenv("UTREE_SAMPLE_CELLS");
     const uint32_t scap = es && atoll(es) >= 1 && atoll(es) <= (1ll << 19) ? (uint32_t)atoll(es) : UTREE_SAMPLES_DEFAULT_CAPACITY;
     const uint32_t ccap = ec && atoll(ec) >= 1 && atoll(ec) <= (1ll << 30) ? (uint32_t)atoll(ec) : UTREE_SAMPLES_DEFAULT_CELLS;
-    for (int g = 0; samples_path && g < n_dev && !rc; ++g) rc = utree_samples_create(devs[g], scap, ccap, samples_delim ? samples_delim : '_', &rep->dev[g].smp);
-    for (int g = 0; sredist_path && g < n_dev && !rc; ++g)
-        rc = utree_sredist_create(devs[g], scap, rcap, ccap, samples_delim ? samples_delim : '_', &rep->dev[g].srd);
+    for (int g = 0; rep->samples_path && g < n_dev && !rc; ++g) rc = utree_samples_create(devs[g], scap, ccap, delim, &rep->dev[g].smp);
+    for (int g = 0; rep->sredist_path && g < n_dev && !rc; ++g) rc = utree_sredist_create(devs[g], scap, rcap, ccap, delim, &rep->dev[g].srd);
     if (rc) { utree_reports_free(rep); return rc; }
     *out = rep;
     return UTREE_OK;
@@ -65,25 +61,18 @@ int utree_reports_reset(utree_reports *rep) {
     return rc;
 }
 
-int utree_reports_classify(utree_reports *rep, int g, utree_dev *dev, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
-                           uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace,
-                           size_t workspace_bytes, const uint8_t *d_text, uint64_t text_bytes, const uint32_t *d_name_off,
-                           const uint32_t *d_name_len, void *stream) {
-    if (rep && (rep->dev[g].rd || rep->dev[g].srd))       /* (each batch feeds both when both are written) */
-        return utree_classify_batch_reports(dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream,
-                                            rep->dev[g].rd, rep->dev[g].srd, d_text, text_bytes, d_name_off, d_name_len);
-    return utree_classify_batch(dev, d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_out, d_workspace, workspace_bytes, stream);
+int utree_reports_classify(utree_reports *rep, int g, utree_dev *dev, const utree_batch_view *v, utree_result *d_out, void *d_workspace,
+                           size_t workspace_bytes) {
+    return utree_classify_view(dev, v, d_out, d_workspace, workspace_bytes, rep ? rep->dev[g].rd : NULL, rep ? rep->dev[g].srd : NULL);   /* (each batch feeds both when both are written) */
 }
 
 int utree_reports_wants_names(const utree_reports *rep) { return rep && (rep->samples_path || rep->sredist_path); }
 
-int utree_reports_add(utree_reports *rep, int g, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
-                      const utree_result *d_res, uint32_t n, int do_rc, int rank, const uint8_t *d_text, uint64_t text_bytes,
-                      const uint32_t *d_name_off, const uint32_t *d_name_len, void *stream) {
+int utree_reports_add(utree_reports *rep, int g, const utree_batch_view *v, const utree_result *d_res, int rank) {
     if (!rep) return UTREE_OK;
-    int rc = rep->dev[g].prof ? utree_profile_add(rep->dev[g].prof, d_res, n, stream) : UTREE_OK;
-    if (!rc && rep->dev[g].smp) rc = utree_samples_add(rep->dev[g].smp, d_text, text_bytes, d_name_off, d_name_len, d_res, n, stream);
-    if (!rc && rep->dev[g].cov && !rank) rc = utree_coverage_add(rep->dev[g].cov, d_bases, d_off, d_len, n, do_rc, stream);
+    int rc = rep->dev[g].prof ? utree_profile_add(rep->dev[g].prof, d_res, v->n_reads, v->stream) : UTREE_OK;
+    if (!rc && rep->dev[g].smp) rc = utree_samples_add(rep->dev[g].smp, v->d_text, v->text_bytes, v->d_name_off, v->d_name_len, d_res, v->n_reads, v->stream);
+    if (!rc && rep->dev[g].cov && !rank) rc = utree_coverage_add(rep->dev[g].cov, v->d_bases, v->d_off, v->d_len, v->n_reads, v->do_rc, v->stream);
     return rc;
 }
 

@@ -9,11 +9,11 @@
  *   writer   : write them in input order (= what the reference writes with one thread; with more threads it
  *              writes a permutation)
  *
- * Paired-end input (utree_search_pairs_file) takes the same four stages with a second input: the reader frames both files and commits the
+ * Paired-end input (a request's mates_path / interleaved) takes the same four stages with a second input: the reader frames both files and commits the
  * pairs both buffers hold, the gpu stage uploads both mates' bytes and joins them on the device (pairs_kernels.hip) in front of the batch
  * kernels; formatter and writer see one query per pair, named by mate 1.
  *
- * A hit map (utree_search_file_hitmap) rides the same slots: the gpu stage launches utree_hitmap_batch behind a shard's classify call on the
+ * A hit map (a request's hitmap_path) rides the same slots: the gpu stage launches utree_hitmap_batch behind a shard's classify call on the
  * same device buffers and brings the runs back, the formatter makes the map's lines next to the output's, and the writer commits both.
  */
 #define _FILE_OFFSET_BITS 64
@@ -40,7 +40,6 @@
 
 #define CHUNK_BYTES ((size_t)96 << 20)        /* must hold two maximal (16 MiB) lines                    */
 #define MAX_READS_PER_BATCH ((size_t)2 << 20)  /* more reads in a chunk (tiny reads) simply take another batch */
-#define LINELEN_MAX 16777216u                 /* itree.c:836 */
 #define NSLOTS 4
 #define READ_THREADS 4
 
@@ -112,6 +111,16 @@ static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev, int hitmap
     return (s->seq_off && s->name_off && s->name_len) ? UTREE_OK : UTREE_E_NOMEM;
 }
 
+static void slot_free(slot_t *s) {
+    void *pinned[] = {s->h_buf, s->h_res, s->rel_off, s->seq_len, s->m2.h_buf, s->m2.rel_off, s->m2.seq_len, s->h_meta, s->h_hm_meta, s->h_run_off,
+                      s->h_runs, s->h_names};
+    for (size_t i = 0; i < sizeof pinned / sizeof pinned[0]; ++i) if (pinned[i]) hipHostFree(pinned[i]);
+    free(s->seq_off); free(s->name_off); free(s->name_len);
+    free(s->m2.seq_off); free(s->m2.name_off); free(s->m2.name_len);
+    free(s->hm_first); free(s->hm_count); free(s->hm_base);
+    for (int t = 0; t < FMT_MAX_THREADS; ++t) { free(s->hm_buf[t]); free(s->fmt_buf[t]); }
+}
+
 typedef struct {
     utree_dev *dev;
     hipStream_t stream;
@@ -129,24 +138,22 @@ typedef struct { int fd; gzFile gz; off_t pos; int eof; } input_t;
 
 typedef struct {
     const utree_ctr *ctr;
+    const utree_search_request *req;            /* what is searched: the paths, do_rc, rank (non-NULL: the rank-specific `xtree-search`, rank.c, one device) */
     utree_reports *rep;                         /* non-NULL: the search feeds reports (reports.h)            */
     gpu_ctx *G; int n_dev;
     input_t in[2];                              /* input; [1]: the mates file of a paired search             */
     int fo;                                     /* output                                                   */
     int names;                                  /* a report reads the names (utree_reports_wants_names): they go up with the shard */
     int hm, fh;                                 /* a hit map is made; its file (-1 once writing it has failed: the search goes on) */
-    const char *hm_path;
     char *hm_msg;                               /* why the map could not be written ("" = it could): the writer's to set            */
     off_t out_pos;
-    int paired;                                 /* PAIRS_*                                                  */
+    int paired;                                 /* PAIRS_*, from the request's mates_path / interleaved     */
     size_t chunk;                               /* bytes per slot and input: CHUNK_BYTES; a paired search honours UTREE_CHUNK_BYTES */
-    const char *path[2];
     /* what utree_last_hip_error is to say: each text has ONE writer -- the reader stage (UTREE_E_PAIRS) and the gpu stage (a join the
      * device refused) --, and the caller's thread reads the one that belongs to the search's code once the stages have ended */
     char msg_pairs[512], msg_join[256];
-    int do_rc, host_threads;
-    const utree_rank_params *rank;              /* non-NULL: the rank-specific `xtree-search` (rank.c), one device  */
-    int input_format;                           /* UTREE_INPUT_*: opt-in FASTQ / multi-line FASTA (+ gzip via zlib)   */
+    int host_threads;                           /* the request's, resolved                                   */
+    int input_format;                           /* the request's UTREE_INPUT_*, AUTO resolved by the reader  */
     slot_t slot[NSLOTS];
     pthread_mutex_t mu; pthread_cond_t cv;
     int rc;                                     /* first error of any stage                                  */
@@ -328,11 +335,11 @@ static void pairs_verdict(pipe_t *P, slot_t *s, size_t np, const size_t *done, c
         const int k = over[0] ? 0 : 1;                                                    /* the shorter file */
         s->frame_rc = UTREE_E_PAIRS;
         snprintf(P->msg_pairs, sizeof P->msg_pairs, "paired input: %s file %s ends after %llu records, %s goes on", k ? "the mates" : "the reads",
-                 P->path[k], (unsigned long long)(recs[k] + done[k]), P->path[1 - k]);
+                 k ? P->req->mates_path : P->req->reads_path, (unsigned long long)(recs[k] + done[k]), k ? P->req->reads_path : P->req->mates_path);
     } else if (!two && P->in[0].eof && used[0] >= have[0] && (nr[0] & 1)) {
         s->frame_rc = UTREE_E_PAIRS;
         snprintf(P->msg_pairs, sizeof P->msg_pairs, "paired input: the interleaved file %s holds an odd number of records (%llu): its last read has no mate",
-                 P->path[0], (unsigned long long)(recs[0] + nr[0]));
+                 P->req->reads_path, (unsigned long long)(recs[0] + nr[0]));
     } else if (over[0] && (!two || over[1])) s->last = 1;                                 /* 3 */
     else if (!np) {                                                                       /* 4 */
         int full = 0;
@@ -411,13 +418,14 @@ static void *reader_pairs_main(void *arg) {
 
 /* ---- stage 2: GPU ---------------------------------------------------------------------------- */
 #define HIPOK(x) do { if ((x) != hipSuccess) { set_error(P, UTREE_E_HIP); return NULL; } } while (0)
+#define HIPE(x) do { if ((x) != hipSuccess) return UTREE_E_HIP; } while (0)      /* ... in what gpu_main and search_file call */
 
 /* the hit map of device g's shard, behind its classify call on the same device buffers; meta and offsets come back with the results */
-static int hitmap_launch(pipe_t *P, slot_t *s, size_t g, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, size_t first, size_t count,
-                         uint64_t total) {
+static int hitmap_launch(pipe_t *P, slot_t *s, size_t g, const utree_batch_view *v, size_t first) {
     gpu_ctx *c = &P->G[g];
+    const size_t count = v->n_reads;
     s->hm_first[g] = first; s->hm_count[g] = count;
-    int e = utree_hitmap_batch(c->dev, d_bases, d_off, d_len, (uint32_t)count, total, P->do_rc, c->d_run_off, c->d_runs, c->runs_cap, c->d_hm_meta,
+    int e = utree_hitmap_batch(c->dev, v->d_bases, v->d_off, v->d_len, v->n_reads, v->total_bases, v->do_rc, c->d_run_off, c->d_runs, c->runs_cap, c->d_hm_meta,
                                c->d_hm_ws, c->hm_ws_bytes, c->stream);
     if (e) return e;
     if (hipMemcpyAsync(&s->h_hm_meta[g], c->d_hm_meta, sizeof(utree_hitmap_meta), hipMemcpyDeviceToHost, c->stream) != hipSuccess) return UTREE_E_HIP;
@@ -471,8 +479,67 @@ static int names_upload(pipe_t *P, slot_t *s, size_t g, size_t first, size_t cou
     return UTREE_OK;
 }
 
+/* Stage device g's shard [first, first + count) of slot `s`: the byte span and the framed arrays go up as they stand, on the shard's stream, and
+ * *v is the batch the kernels see.  *lo: where in h_buf the uploaded span -- the view's text, with names -- begins. */
+static int stage_reads(pipe_t *P, slot_t *s, size_t g, size_t first, size_t count, utree_batch_view *v, size_t *lo_out) {
+    gpu_ctx *c = &P->G[g];
+    const size_t last = first + count - 1;
+    size_t lo = (size_t)s->seq_off[first], hi = (size_t)s->seq_off[last] + s->seq_len[last];
+    if (P->names && (size_t)s->name_off[first] < lo) lo = (size_t)s->name_off[first];      /* the span from the first name on: the names are read there */
+    uint64_t total = 0; uint32_t mx = 0;
+    for (size_t r = first; r <= last; ++r) {
+        s->rel_off[r] = s->seq_off[r] - lo; total += s->seq_len[r];
+        if (s->seq_len[r] > mx) mx = s->seq_len[r];
+    }
+    HIPE(hipSetDevice(c->dev->device));
+    HIPE(hipMemcpyAsync(c->d_buf, s->h_buf + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
+    HIPE(hipMemcpyAsync(c->d_off, s->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
+    HIPE(hipMemcpyAsync(c->d_len, s->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
+    *v = (utree_batch_view){c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->req->do_rc, c->d_buf, hi - lo, c->d_name_off, c->d_name_len, c->stream};
+    *lo_out = lo;
+    return UTREE_OK;
+}
+
+/* ... of a paired search: both mates' byte spans and framed arrays go up as they stand; the device joins them and the batch kernels, the reports
+ * included, see one query per pair.  The view's text is mate 1's span. */
+static int stage_pairs(pipe_t *P, slot_t *s, size_t g, size_t first, size_t count, utree_batch_view *v, size_t *lo_out) {
+    gpu_ctx *c = &P->G[g];
+    const int two = P->paired == PAIRS_TWO_FILES;
+    mate_t *m = &s->m2;
+    const size_t last = first + count - 1;
+    size_t lo1 = (size_t)s->seq_off[first], hi1 = (size_t)s->seq_off[last] + s->seq_len[last];
+    size_t lo2 = (size_t)m->seq_off[first], hi2 = (size_t)m->seq_off[last] + m->seq_len[last];
+    if (P->names && (size_t)s->name_off[first] < lo1) lo1 = (size_t)s->name_off[first];   /* the span from mate 1's first name on: the names are read there */
+    if (!two) { hi1 = hi2; lo2 = lo1; }                                        /* interleaved: one span holds both */
+    uint64_t total = 0; uint32_t mx = 0;
+    for (size_t r = first; r <= last; ++r) {
+        s->rel_off[r] = s->seq_off[r] - lo1; m->rel_off[r] = m->seq_off[r] - lo2;
+        const uint32_t jl = s->seq_len[r] + 1u + m->seq_len[r];                /* <= LINELEN_MAX: the reader saw to it */
+        total += jl;
+        if (jl > mx) mx = jl;
+    }
+    if (total > c->joined_cap) return UTREE_E_ARG;                             /* (cannot happen: the buffers' bytes + one per pair) */
+    HIPE(hipSetDevice(c->dev->device));
+    HIPE(hipMemcpyAsync(c->d_buf, s->h_buf + lo1, hi1 - lo1, hipMemcpyHostToDevice, c->stream));
+    if (two) HIPE(hipMemcpyAsync(c->d_buf2, m->h_buf + lo2, hi2 - lo2, hipMemcpyHostToDevice, c->stream));
+    HIPE(hipMemcpyAsync(c->d_off, s->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
+    HIPE(hipMemcpyAsync(c->d_len, s->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
+    HIPE(hipMemcpyAsync(c->d_off2, m->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
+    HIPE(hipMemcpyAsync(c->d_len2, m->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
+    /* the host has the lengths: total and max_len are its own, the join's meta comes back with the results and is checked then */
+    const int e = utree_pairs_join(c->dev, c->d_buf, c->d_off, c->d_len, two ? c->d_buf2 : c->d_buf, c->d_off2, c->d_len2, (uint32_t)count,
+                                   c->d_joined, total, c->d_joff, c->d_jlen, c->d_meta, c->stream);
+    if (e) return e;
+    c->want_total = total;
+    HIPE(hipMemcpyAsync(&s->h_meta[g], c->d_meta, sizeof(utree_pairs_meta), hipMemcpyDeviceToHost, c->stream));
+    *v = (utree_batch_view){c->d_joined, c->d_joff, c->d_jlen, (uint32_t)count, total, mx, P->req->do_rc, c->d_buf, hi1 - lo1, c->d_name_off, c->d_name_len, c->stream};
+    *lo_out = lo1;
+    return UTREE_OK;
+}
+
 static void *gpu_main(void *arg) {
     pipe_t *P = (pipe_t *)arg;
+    const utree_rank_params *rank = P->req->rank;
     for (int i = 0;; ++i) {
         slot_t *s = &P->slot[i % NSLOTS];
         if (!wait_state(P, s, S_FRAMED)) return NULL;
@@ -486,76 +553,22 @@ static void *gpu_main(void *arg) {
             size_t first = g * per; if (first > nr) first = nr;
             size_t count = first + per <= nr ? per : nr - first;
             if (!count) continue;
-            size_t last = first + count - 1;
-            if (P->paired) {
-                /* both mates' byte spans and framed arrays go up as they stand; the device joins them and the batch kernels, the reports
-                 * included, see one query per pair */
-                const int two = P->paired == PAIRS_TWO_FILES;
-                mate_t *m = &s->m2;
-                size_t lo1 = (size_t)s->seq_off[first], hi1 = (size_t)s->seq_off[last] + s->seq_len[last];
-                size_t lo2 = (size_t)m->seq_off[first], hi2 = (size_t)m->seq_off[last] + m->seq_len[last];
-                if (P->names && (size_t)s->name_off[first] < lo1) lo1 = (size_t)s->name_off[first];   /* the span from mate 1's first name on: the names are read there */
-                if (!two) { hi1 = hi2; lo2 = lo1; }                                        /* interleaved: one span holds both */
-                uint64_t total = 0; uint32_t mx = 0;
-                for (size_t r = first; r <= last; ++r) {
-                    s->rel_off[r] = s->seq_off[r] - lo1; m->rel_off[r] = m->seq_off[r] - lo2;
-                    const uint32_t jl = s->seq_len[r] + 1u + m->seq_len[r];                /* <= LINELEN_MAX: the reader saw to it */
-                    total += jl;
-                    if (jl > mx) mx = jl;
-                }
-                if (total > c->joined_cap) { set_error(P, UTREE_E_ARG); return NULL; }     /* (cannot happen: the buffers' bytes + one per pair) */
-                HIPOK(hipSetDevice(c->dev->device));
-                HIPOK(hipMemcpyAsync(c->d_buf, s->h_buf + lo1, hi1 - lo1, hipMemcpyHostToDevice, c->stream));
-                if (two) HIPOK(hipMemcpyAsync(c->d_buf2, m->h_buf + lo2, hi2 - lo2, hipMemcpyHostToDevice, c->stream));
-                HIPOK(hipMemcpyAsync(c->d_off, s->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
-                HIPOK(hipMemcpyAsync(c->d_len, s->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
-                HIPOK(hipMemcpyAsync(c->d_off2, m->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
-                HIPOK(hipMemcpyAsync(c->d_len2, m->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
-                /* the host has the lengths: total and max_len are its own, the join's meta comes back with the results and is checked then */
-                int e = utree_pairs_join(c->dev, c->d_buf, c->d_off, c->d_len, two ? c->d_buf2 : c->d_buf, c->d_off2, c->d_len2, (uint32_t)count,
-                                         c->d_joined, total, c->d_joff, c->d_jlen, c->d_meta, c->stream);
-                if (e) { set_error(P, e); return NULL; }
-                c->want_total = total;
-                HIPOK(hipMemcpyAsync(&s->h_meta[g], c->d_meta, sizeof(utree_pairs_meta), hipMemcpyDeviceToHost, c->stream));
-                if (P->names && (e = names_upload(P, s, g, first, count, lo1, hi1 - lo1))) { set_error(P, e); return NULL; }   /* (in front of the classify call: a report may read them there) */
-                e = utree_reports_classify(P->rep, (int)g, c->dev, c->d_joined, c->d_joff, c->d_jlen, (uint32_t)count, total, mx, P->do_rc, c->d_out,
-                                           c->d_ws, c->ws_bytes, c->d_buf, hi1 - lo1, c->d_name_off, c->d_name_len, c->stream);
-                if (e) { set_error(P, e); return NULL; }
-                e = utree_reports_add(P->rep, (int)g, c->d_joined, c->d_joff, c->d_jlen, c->d_out, (uint32_t)count, P->do_rc, 0, c->d_buf, hi1 - lo1,
-                                      c->d_name_off, c->d_name_len, c->stream);
-                if (e) { set_error(P, e); return NULL; }
-                if (P->hm && (e = hitmap_launch(P, s, g, c->d_joined, c->d_joff, c->d_jlen, first, count, total))) { set_error(P, e); return NULL; }
-                HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
-                continue;
-            }
-            size_t lo = (size_t)s->seq_off[first], hi = (size_t)s->seq_off[last] + s->seq_len[last];
-            if (P->names && (size_t)s->name_off[first] < lo) lo = (size_t)s->name_off[first];      /* the span from the first name on: the names are read there */
-            uint64_t total = 0; uint32_t mx = 0;
-            for (size_t r = first; r <= last; ++r) {
-                s->rel_off[r] = s->seq_off[r] - lo; total += s->seq_len[r];
-                if (s->seq_len[r] > mx) mx = s->seq_len[r];
-            }
-            HIPOK(hipSetDevice(c->dev->device));
-            HIPOK(hipMemcpyAsync(c->d_buf, s->h_buf + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(c->d_off, s->rel_off + first, count * 8, hipMemcpyHostToDevice, c->stream));
-            HIPOK(hipMemcpyAsync(c->d_len, s->seq_len + first, count * 4, hipMemcpyHostToDevice, c->stream));
-            int e = P->names ? names_upload(P, s, g, first, count, lo, hi - lo) : UTREE_OK;
+            utree_batch_view v;
+            size_t lo = 0;
+            int e = P->paired ? stage_pairs(P, s, g, first, count, &v, &lo) : stage_reads(P, s, g, first, count, &v, &lo);
+            if (!e && P->names) e = names_upload(P, s, g, first, count, lo, (size_t)v.text_bytes);   /* (in front of the classify call: a report may read them there) */
+            if (!e) e = rank ? utree_rank_batch(c->dev, v.d_bases, v.d_off, v.d_len, v.n_reads, v.total_bases, v.max_len, v.do_rc, rank, c->d_out, c->d_ws,
+                                                c->ws_bytes, c->stream)
+                             : utree_reports_classify(P->rep, (int)g, c->dev, &v, c->d_out, c->d_ws, c->ws_bytes);
+            if (!e) e = utree_reports_add(P->rep, (int)g, &v, c->d_out, rank != NULL);
+            if (!e && P->hm) e = hitmap_launch(P, s, g, &v, first);
+            if (!e && hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream) != hipSuccess) e = UTREE_E_HIP;
             if (e) { set_error(P, e); return NULL; }
-            e = P->rank ? utree_rank_batch(c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
-                                           P->rank, c->d_out, c->d_ws, c->ws_bytes, c->stream)
-                        : utree_reports_classify(P->rep, (int)g, c->dev, c->d_buf, c->d_off, c->d_len, (uint32_t)count, total, mx, P->do_rc,
-                                                 c->d_out, c->d_ws, c->ws_bytes, c->d_buf, hi - lo, c->d_name_off, c->d_name_len, c->stream);
-            if (e) { set_error(P, e); return NULL; }
-            e = utree_reports_add(P->rep, (int)g, c->d_buf, c->d_off, c->d_len, c->d_out, (uint32_t)count, P->do_rc, P->rank != NULL, c->d_buf, hi - lo,
-                                  c->d_name_off, c->d_name_len, c->stream);
-            if (e) { set_error(P, e); return NULL; }
-            if (P->hm && (e = hitmap_launch(P, s, g, c->d_buf, c->d_off, c->d_len, first, count, total))) { set_error(P, e); return NULL; }
-            HIPOK(hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream));
         }
         for (size_t g = 0; g < n_dev && nr; ++g) {
             HIPOK(hipSetDevice(P->G[g].dev->device));
             HIPOK(hipStreamSynchronize(P->G[g].stream));
-            if (!P->rank) { int pe = utree_classify_poll(P->G[g].dev); if (pe) { set_error(P, pe); return NULL; } }   /* the batches' error words */
+            if (!rank) { int pe = utree_classify_poll(P->G[g].dev); if (pe) { set_error(P, pe); return NULL; } }   /* the batches' error words */
             if (P->paired && (s->h_meta[g].error || s->h_meta[g].total_bases != P->G[g].want_total)) {               /* ... and the join's */
                 snprintf(P->msg_join, sizeof P->msg_join, "the device join of a batch of pairs reported error %u, %llu joined bytes where the host counted %llu",
                          s->h_meta[g].error, (unsigned long long)s->h_meta[g].total_bases, (unsigned long long)P->G[g].want_total);
@@ -595,7 +608,7 @@ static void *format_main(void *arg) {
             if (need > s->fmt_cap[t]) { free(s->fmt_buf[t]); s->fmt_buf[t] = (char *)malloc(need + need / 4); s->fmt_cap[t] = s->fmt_buf[t] ? need + need / 4 : 0; }
             uint64_t good = 0;
             size_t L = !s->fmt_buf[t] ? (size_t)-1
-                       : P->rank ? utree_format_rank_records(P->ctr, s->h_buf, s->name_off + a, s->name_len + a, s->h_res + a, b - a,
+                       : P->req->rank ? utree_format_rank_records(P->ctr, s->h_buf, s->name_off + a, s->name_len + a, s->h_res + a, b - a,
                                                              s->fmt_buf[t], s->fmt_cap[t], &good)
                                  : utree_format_records(P->ctr, s->h_buf, s->name_off + a, s->name_len + a, s->h_res + a, b - a,
                                                         s->fmt_buf[t], s->fmt_cap[t], &good);
@@ -652,7 +665,7 @@ static void *writer_main(void *arg) {
             while (done < s->hm_len[t]) {
                 ssize_t w = write(P->fh, s->hm_buf[t] + done, s->hm_len[t] - done);
                 if (w <= 0) {                                                     /* the search goes on without its map */
-                    snprintf(P->hm_msg, 512, "hit map %s: cannot write the file (%s)", P->hm_path, strerror(errno));
+                    snprintf(P->hm_msg, 512, "hit map %s: cannot write the file (%s)", P->req->hitmap_path, strerror(errno));
                     close(P->fh); P->fh = -1;
                     break;
                 }
@@ -704,14 +717,46 @@ static void free_ctx(gpu_ctx *g) {
     if (g->stream) hipStreamDestroy(g->stream);
 }
 
-#define HIPM(x) do { if ((x) != hipSuccess) { rc = UTREE_E_HIP; goto done; } } while (0)
-
-/* bytes per slot and input of a paired search: CHUNK_BYTES; UTREE_CHUNK_BYTES lowers it as it does for the device pipeline (tests: many slot
- * boundaries and a carry in each file of a small input) */
-static size_t pairs_chunk_bytes(void) {
-    const char *e = getenv("UTREE_CHUNK_BYTES");
-    if (e && atoll(e) >= 64 && (size_t)atoll(e) < CHUNK_BYTES) return (size_t)atoll(e);
-    return CHUNK_BYTES;
+/* device g's buffers for the slots' shards: the worst case of a shard is the slot's reads and bytes */
+static int ctx_alloc(pipe_t *P, gpu_ctx *c, utree_dev *dev) {
+    const utree_search_request *req = P->req;
+    const int paired = P->paired;
+    c->dev = dev;
+    HIPE(hipSetDevice(dev->device));
+    HIPE(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIPE(hipMalloc((void **)&c->d_buf, P->chunk + 64));
+    HIPE(hipMalloc((void **)&c->d_off, MAX_READS_PER_BATCH * 8));
+    HIPE(hipMalloc((void **)&c->d_len, MAX_READS_PER_BATCH * 4));
+    HIPE(hipMalloc((void **)&c->d_out, MAX_READS_PER_BATCH * sizeof(utree_result)));
+    if (paired) {                                                             /* the second mates, and the joined batch: both buffers' bytes + an 'N' per pair */
+        c->joined_cap = (paired == PAIRS_TWO_FILES ? 2 : 1) * P->chunk + MAX_READS_PER_BATCH;
+        if (paired == PAIRS_TWO_FILES) HIPE(hipMalloc((void **)&c->d_buf2, P->chunk + 64));
+        HIPE(hipMalloc((void **)&c->d_joined, c->joined_cap + 64));
+        HIPE(hipMalloc((void **)&c->d_off2, MAX_READS_PER_BATCH * 8));
+        HIPE(hipMalloc((void **)&c->d_len2, MAX_READS_PER_BATCH * 4));
+        HIPE(hipMalloc((void **)&c->d_joff, MAX_READS_PER_BATCH * 8));
+        HIPE(hipMalloc((void **)&c->d_jlen, MAX_READS_PER_BATCH * 4));
+        HIPE(hipMalloc((void **)&c->d_meta, sizeof(utree_pairs_meta)));
+    }
+    if (P->hm) {                                                              /* a run per window */
+        const uint64_t tb = paired ? c->joined_cap : P->chunk;
+        c->runs_cap = utk_hitmap_wcap((uint32_t)MAX_READS_PER_BATCH, tb, req->do_rc);
+        c->hm_ws_bytes = utree_hitmap_workspace_bytes(dev, (uint32_t)MAX_READS_PER_BATCH, tb, req->do_rc);
+        if (!c->hm_ws_bytes) return UTREE_E_ARG;
+        HIPE(hipMalloc((void **)&c->d_run_off, (MAX_READS_PER_BATCH + 1) * 8));
+        HIPE(hipMalloc((void **)&c->d_runs, (size_t)(c->runs_cap + 1) * sizeof(utree_hit_run)));
+        HIPE(hipMalloc((void **)&c->d_hm_meta, sizeof(utree_hitmap_meta)));
+        HIPE(hipMalloc(&c->d_hm_ws, c->hm_ws_bytes));
+    }
+    if (P->names) {
+        HIPE(hipMalloc((void **)&c->d_name_off, MAX_READS_PER_BATCH * 4));
+        HIPE(hipMalloc((void **)&c->d_name_len, MAX_READS_PER_BATCH * 4));
+    }
+    c->ws_bytes = req->rank ? utree_rank_workspace_bytes(dev, (uint32_t)MAX_READS_PER_BATCH, CHUNK_BYTES, LINELEN_MAX, req->do_rc, req->rank)
+                            : utree_classify_workspace_bytes(dev, (uint32_t)MAX_READS_PER_BATCH, paired ? c->joined_cap : CHUNK_BYTES, LINELEN_MAX, req->do_rc);
+    if (!c->ws_bytes) return UTREE_E_ARG;
+    HIPE(hipMalloc(&c->d_ws, c->ws_bytes));
+    return UTREE_OK;
 }
 
 /* <hitmap_path>.labels: line i (0-based) is the text of label index i, what a hit's code in the map names */
@@ -727,13 +772,11 @@ static int write_labels(const utree_ctr *ctr, const char *hitmap_path, char *msg
     return bad;
 }
 
-/* paired: PAIRS_TWO_FILES (mates_path holds the second mates) or PAIRS_INTERLEAVED (fasta_path holds both), GG search only */
-static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *mates_path, int paired,
-                       const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format, utree_reports *rep,
-                       const char *hitmap_path, char *hm_msg, utree_search_stats *stats) {
-    if (!ctr || !devs || n_dev < 1 || !fasta_path || !out_path || input_format < 0 || input_format > UTREE_INPUT_AUTO) return UTREE_E_ARG;
-    if (paired && (rank || (paired == PAIRS_TWO_FILES) != (mates_path != NULL))) return UTREE_E_ARG;
-    if (hitmap_path && (rank || !hm_msg)) return UTREE_E_ARG;
+/* One search that utree_search_run has checked; rep: the reports it feeds (NULL: none); hm_msg: why the hit map was not written, when it was not */
+static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const utree_search_request *req, utree_reports *rep, char *hm_msg,
+                       utree_search_stats *stats) {
+    const int paired = req->mates_path ? PAIRS_TWO_FILES : req->interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE;   /* (GG search only) */
+    const char *hitmap_path = req->hitmap_path, *out_path = req->out_path;
     int rc = UTREE_OK;
     uint64_t dev_printed = 0;
     utree_search_resume resume;
@@ -741,8 +784,8 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     /* The GG search on the reference's input format takes the device text pipeline (search_dev.c); it hands back input it
      * does not take -- malformed records, NUL bytes, lines fgets would split -- and the host framing below then reproduces
      * the reference on it case by case.  UTREE_HOST_TEXT=1 forces the host pipeline (tests, A/B). */
-    if (!rank && !paired && !hitmap_path && input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
-        rc = utree_search_file_device(ctr, devs, n_dev, fasta_path, out_path, do_rc, host_threads, rep, stats, &dev_printed, &resume);
+    if (!req->rank && !paired && !hitmap_path && req->input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
+        rc = utree_search_file_device(ctr, devs, n_dev, req->reads_path, out_path, req->do_rc, req->host_threads, rep, stats, &dev_printed, &resume);
         if (rc != UTREE_RETRY_HOST) return rc;
         rc = UTREE_OK;
         /* the reports carry the chunks the device pipeline has written when this pipeline continues behind them (resume.fo >= 0), as the
@@ -752,15 +795,14 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     double t_start = now_s();
     pipe_t *P = (pipe_t *)calloc(1, sizeof *P);
     if (!P) { if (resume.fo >= 0) close(resume.fo); return UTREE_E_NOMEM; }
-    P->ctr = ctr; P->rep = rep; P->n_dev = n_dev; P->do_rc = do_rc; P->rank = rank; P->input_format = input_format;
+    P->ctr = ctr; P->req = req; P->rep = rep; P->n_dev = n_dev; P->input_format = req->input_format;
     P->progress_printed = dev_printed;
-    P->paired = paired; P->chunk = paired || hitmap_path ? pairs_chunk_bytes() : CHUNK_BYTES;
+    P->paired = paired; P->chunk = paired || hitmap_path ? utree_chunk_bytes(CHUNK_BYTES) : CHUNK_BYTES;
     P->names = utree_reports_wants_names(rep);
-    P->hm = hitmap_path != NULL; P->fh = -1; P->hm_path = hitmap_path; P->hm_msg = hm_msg;
-    P->path[0] = fasta_path; P->path[1] = mates_path;
+    P->hm = hitmap_path != NULL; P->fh = -1; P->hm_msg = hm_msg;
     P->in[1].fd = -1;
-    P->in[0].fd = open(fasta_path, O_RDONLY);
-    if (paired == PAIRS_TWO_FILES && P->in[0].fd >= 0 && (P->in[1].fd = open(mates_path, O_RDONLY)) < 0) { close(P->in[0].fd); P->in[0].fd = -1; }
+    P->in[0].fd = open(req->reads_path, O_RDONLY);
+    if (paired == PAIRS_TWO_FILES && P->in[0].fd >= 0 && (P->in[1].fd = open(req->mates_path, O_RDONLY)) < 0) { close(P->in[0].fd); P->in[0].fd = -1; }
     if (resume.fo >= 0) {
         /* the output is a pipe and the device pipeline has written the chunks in front of `in_off`: go on from there, on the same descriptor */
         P->fo = resume.fo; P->in[0].pos = (off_t)resume.in_off;
@@ -790,7 +832,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
         else if (write_labels(ctr, hitmap_path, hm_msg)) { close(P->fh); P->fh = -1; }
         if (P->fh < 0) P->hm = 0;
     }
-    for (int k = 0; k < 2 && input_format != UTREE_INPUT_REFERENCE; ++k) {
+    for (int k = 0; k < 2 && req->input_format != UTREE_INPUT_REFERENCE; ++k) {
         if (P->in[k].fd < 0) continue;
         P->in[k].gz = gzdopen(dup(P->in[k].fd), "rb");
         if (!P->in[k].gz) {
@@ -802,6 +844,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
         }
         gzbuffer(P->in[k].gz, 1u << 20);
     }
+    int host_threads = req->host_threads;
 #ifdef _OPENMP
     if (host_threads <= 0) host_threads = omp_get_max_threads();
 #else
@@ -814,44 +857,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     for (uint32_t i = 0; i < ctr->info.n_labels; ++i) if (ctr->label_len[i] > P->max_label) P->max_label = ctr->label_len[i];
     P->G = (gpu_ctx *)calloc((size_t)n_dev, sizeof(gpu_ctx));
     if (!P->G) { rc = UTREE_E_NOMEM; goto done; }
-    for (int g = 0; g < n_dev; ++g) {
-        gpu_ctx *c = &P->G[g];
-        c->dev = devs[g];
-        HIPM(hipSetDevice(devs[g]->device));
-        HIPM(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        HIPM(hipMalloc((void **)&c->d_buf, P->chunk + 64));
-        HIPM(hipMalloc((void **)&c->d_off, MAX_READS_PER_BATCH * 8));
-        HIPM(hipMalloc((void **)&c->d_len, MAX_READS_PER_BATCH * 4));
-        HIPM(hipMalloc((void **)&c->d_out, MAX_READS_PER_BATCH * sizeof(utree_result)));
-        if (paired) {                                                             /* the second mates, and the joined batch: both buffers' bytes + an 'N' per pair */
-            c->joined_cap = (paired == PAIRS_TWO_FILES ? 2 : 1) * P->chunk + MAX_READS_PER_BATCH;
-            if (paired == PAIRS_TWO_FILES) HIPM(hipMalloc((void **)&c->d_buf2, P->chunk + 64));
-            HIPM(hipMalloc((void **)&c->d_joined, c->joined_cap + 64));
-            HIPM(hipMalloc((void **)&c->d_off2, MAX_READS_PER_BATCH * 8));
-            HIPM(hipMalloc((void **)&c->d_len2, MAX_READS_PER_BATCH * 4));
-            HIPM(hipMalloc((void **)&c->d_joff, MAX_READS_PER_BATCH * 8));
-            HIPM(hipMalloc((void **)&c->d_jlen, MAX_READS_PER_BATCH * 4));
-            HIPM(hipMalloc((void **)&c->d_meta, sizeof(utree_pairs_meta)));
-        }
-        if (P->hm) {                                                              /* the worst case of a shard: the slot's reads and bytes, a run per window */
-            const uint64_t tb = paired ? c->joined_cap : P->chunk;
-            c->runs_cap = utk_hitmap_wcap((uint32_t)MAX_READS_PER_BATCH, tb, do_rc);
-            c->hm_ws_bytes = utree_hitmap_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, tb, do_rc);
-            if (!c->hm_ws_bytes) { rc = UTREE_E_ARG; goto done; }
-            HIPM(hipMalloc((void **)&c->d_run_off, (MAX_READS_PER_BATCH + 1) * 8));
-            HIPM(hipMalloc((void **)&c->d_runs, (size_t)(c->runs_cap + 1) * sizeof(utree_hit_run)));
-            HIPM(hipMalloc((void **)&c->d_hm_meta, sizeof(utree_hitmap_meta)));
-            HIPM(hipMalloc(&c->d_hm_ws, c->hm_ws_bytes));
-        }
-        if (P->names) {
-            HIPM(hipMalloc((void **)&c->d_name_off, MAX_READS_PER_BATCH * 4));
-            HIPM(hipMalloc((void **)&c->d_name_len, MAX_READS_PER_BATCH * 4));
-        }
-        c->ws_bytes = rank ? utree_rank_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, CHUNK_BYTES, LINELEN_MAX, do_rc, rank)
-                           : utree_classify_workspace_bytes(devs[g], (uint32_t)MAX_READS_PER_BATCH, paired ? c->joined_cap : CHUNK_BYTES, LINELEN_MAX, do_rc);
-        if (!c->ws_bytes) { rc = UTREE_E_ARG; goto done; }
-        HIPM(hipMalloc(&c->d_ws, c->ws_bytes));
-    }
+    for (int g = 0; g < n_dev; ++g) if ((rc = ctx_alloc(P, &P->G[g], devs[g]))) goto done;
     {
         pthread_t tr, tg, tf, tw;
         pthread_create(&tr, NULL, paired ? reader_pairs_main : reader_main, P);
@@ -876,26 +882,7 @@ done:
     if (P->fo >= 0) close(P->fo);
     if (P->fh >= 0 && close(P->fh) && !hm_msg[0]) snprintf(hm_msg, 512, "hit map %s: cannot write the file (%s)", hitmap_path, strerror(errno));
     if (P->G) { for (int g = 0; g < n_dev; ++g) free_ctx(&P->G[g]); free(P->G); }
-    for (int i = 0; i < NSLOTS; ++i) {
-        slot_t *s = &P->slot[i];
-        if (s->h_buf) hipHostFree(s->h_buf);
-        if (s->h_res) hipHostFree(s->h_res);
-        if (s->rel_off) hipHostFree(s->rel_off);
-        if (s->seq_len) hipHostFree(s->seq_len);
-        free(s->seq_off); free(s->name_off); free(s->name_len);
-        if (s->m2.h_buf) hipHostFree(s->m2.h_buf);
-        if (s->m2.rel_off) hipHostFree(s->m2.rel_off);
-        if (s->m2.seq_len) hipHostFree(s->m2.seq_len);
-        if (s->h_meta) hipHostFree(s->h_meta);
-        if (s->h_hm_meta) hipHostFree(s->h_hm_meta);
-        if (s->h_run_off) hipHostFree(s->h_run_off);
-        if (s->h_runs) hipHostFree(s->h_runs);
-        if (s->h_names) hipHostFree(s->h_names);
-        free(s->hm_first); free(s->hm_count); free(s->hm_base);
-        for (int t = 0; t < FMT_MAX_THREADS; ++t) free(s->hm_buf[t]);
-        free(s->m2.seq_off); free(s->m2.name_off); free(s->m2.name_len);
-        for (int t = 0; t < FMT_MAX_THREADS; ++t) free(s->fmt_buf[t]);
-    }
+    for (int i = 0; i < NSLOTS; ++i) slot_free(&P->slot[i]);
     P->st.seconds_total = now_s() - t_start;
     P->st.seconds_kernels = P->t_gpu;
     P->st.pipeline = 0; P->st.n_lanes = 1;
@@ -909,101 +896,6 @@ done:
     pthread_cond_destroy(&P->cv);
     free(P);
     return rc;
-}
-
-/* One whole-file search as every public entry point asks for it.  rank: NULL = the GG search over n_dev device handles; else XT_doSearch32(utree,
- * in, out, 0, speed, doRC) (itree.c:1376 without DO_GG): the same pipeline, the batches to ONE device in file order because each read's vote
- * depends on the reads before it (rank.c).  profile_path / coverage_path: NULL, or the report to feed while searching and to write when the
- * search has succeeded (the search's own codes stay its own); redist_path, sredist_path: the same for the redistribution and the per-sample
- * redistribution (GG search only). */
-static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int paired,
-                          const char *out_path, int do_rc, const utree_rank_params *rank, int host_threads, int input_format,
-                          const char *profile_path, const char *coverage_path, const char *redist_path, uint32_t redist_passes,
-                          const char *hitmap_path, const char *samples_path, int delim, const char *sredist_path, utree_search_stats *stats) {
-    utree_reports *rep = NULL;
-    utree_search_stats st;
-    char hm_msg[512] = "";                                         /* why the hit map was not written, when it was not */
-    memset(&st, 0, sizeof st);
-    if (rank && (redist_path || hitmap_path || sredist_path)) return UTREE_E_ARG;  /* (another vote: no candidate sets; a hit-dependent subset of windows: no map) */
-    int rc = utree_reports_create(ctr, devs, n_dev, profile_path, coverage_path, redist_path, redist_passes, samples_path, delim, sredist_path, &rep);
-    if (!rc && !rep && !hitmap_path)
-        return search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, NULL, NULL, NULL, stats);   /* no report asked for */
-    if (!rc) rc = search_file(ctr, devs, n_dev, reads_path, mates_path, paired, out_path, do_rc, rank, host_threads, input_format, rep, hitmap_path, hm_msg, &st);
-    if (!rc && rep) rc = utree_reports_write(rep, ctr, st.n_reads);
-    if (!rc && hm_msg[0]) { utree_set_error_text(hm_msg); rc = UTREE_E_HITMAP; }
-    utree_reports_free(rep);
-    if (stats) *stats = st;
-    return rc;
-}
-
-int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *fasta_path, const char *out_path,
-                      int do_rc, int host_threads, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, fasta_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, NULL, 0, NULL, NULL, 0, NULL, stats);
-}
-int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
-                           int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, NULL, NULL, NULL, 0, NULL, NULL, 0, NULL, stats);
-}
-int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
-                              int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, NULL, NULL, 0, NULL, NULL, 0, NULL, stats);
-}
-int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
-                               int host_threads, int input_format, const char *profile_path, const char *coverage_path,
-                               utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, NULL, PAIRS_NONE, out_path, do_rc, NULL, host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, NULL, 0, NULL, stats);
-}
-
-/* pairs: both mates of a pair cast one vote (include/utree_amd.h) */
-int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, const char *out_path,
-                            int do_rc, int host_threads, int input_format, const char *profile_path, const char *coverage_path,
-                            utree_search_stats *stats) {
-    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : PAIRS_INTERLEAVED, out_path, do_rc, NULL,
-                          host_threads, input_format, profile_path, coverage_path, NULL, 0, NULL, NULL, 0, NULL, stats);
-}
-
-int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
-                                   int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
-                                   const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
-                                   utree_search_stats *stats) {
-    if (mates_path && interleaved) return UTREE_E_ARG;
-    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, NULL, NULL, 0, NULL, stats);
-}
-
-int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int interleaved,
-                             const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
-                             const char *coverage_path, const char *redistribute_path, uint32_t max_passes, const char *hitmap_path,
-                             utree_search_stats *stats) {
-    if (mates_path && interleaved) return UTREE_E_ARG;
-    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, NULL, 0, NULL, stats);
-}
-
-/* a sample table of multiplexed reads next to everything else (include/utree_amd.h) */
-int utree_search_file_samples(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int interleaved,
-                              const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
-                              const char *coverage_path, const char *redistribute_path, uint32_t max_passes, const char *hitmap_path,
-                              const char *samples_path, int delim, utree_search_stats *stats) {
-    if (mates_path && interleaved) return UTREE_E_ARG;
-    if (samples_path && (delim < 0 || delim > 255 || delim == '\t' || delim == ' ' || delim == '\r' || delim == '\n')) return UTREE_E_ARG;
-    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, samples_path,
-                          delim, NULL, stats);
-}
-
-/* ... and the per-sample redistribution (include/utree_amd.h) */
-int utree_search_file_sample_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
-                                          int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
-                                          const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
-                                          const char *hitmap_path, const char *samples_path, int delim, const char *sample_redistribute_path,
-                                          utree_search_stats *stats) {
-    if (mates_path && interleaved) return UTREE_E_ARG;
-    if ((samples_path || sample_redistribute_path) && (delim < 0 || delim > 255 || delim == '\t' || delim == ' ' || delim == '\r' || delim == '\n'))
-        return UTREE_E_ARG;
-    return search_request(ctr, devs, n_dev, reads_path, mates_path, mates_path ? PAIRS_TWO_FILES : interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE, out_path,
-                          do_rc, NULL, host_threads, input_format, profile_path, coverage_path, redistribute_path, max_passes, hitmap_path, samples_path,
-                          delim, sample_redistribute_path, stats);
 }
 
 int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_off1, const uint32_t *d_len1, const uint8_t *d_bases2,
@@ -1020,26 +912,121 @@ int utree_pairs_join(utree_dev *dev, const uint8_t *d_bases1, const uint64_t *d_
     return UTREE_OK;
 }
 
-int utree_rank_search_file(const utree_ctr *ctr, utree_dev *dev, const char *fasta_path, const char *out_path, int do_rc,
-                           const utree_rank_params *params, int host_threads, utree_search_stats *stats) {
-    return utree_rank_search_file_profile(ctr, dev, fasta_path, out_path, do_rc, params, host_threads, UTREE_INPUT_REFERENCE, NULL, stats);
+/* One checked request: its reports are fed while searching and written when the search has succeeded (the search's own codes stay its own) */
+static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, const utree_search_request *req, utree_search_stats *stats) {
+    utree_reports *rep = NULL;
+    utree_search_stats st;
+    char hm_msg[512] = "";                                         /* why the hit map was not written, when it was not */
+    memset(&st, 0, sizeof st);
+    int rc = utree_reports_create(ctr, devs, n_dev, req, &rep);
+    if (!rc && !rep && !req->hitmap_path) return search_file(ctr, devs, n_dev, req, NULL, hm_msg, stats);   /* no report asked for */
+    if (!rc) rc = search_file(ctr, devs, n_dev, req, rep, hm_msg, &st);
+    if (!rc && rep) rc = utree_reports_write(rep, ctr, st.n_reads);
+    if (!rc && hm_msg[0]) { utree_set_error_text(hm_msg); rc = UTREE_E_HITMAP; }
+    utree_reports_free(rep);
+    if (stats) *stats = st;
+    return rc;
 }
-int utree_rank_search_file_opts(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
-                                const utree_rank_params *params, int host_threads, int input_format, utree_search_stats *stats) {
-    return utree_rank_search_file_profile(ctr, dev, reads_path, out_path, do_rc, params, host_threads, input_format, NULL, stats);
+
+/* The one place that checks a request, every check in front of the first look at `ctr` or a device handle.  rank: XT_doSearch32(utree, in, out, 0,
+ * speed, doRC) (itree.c:1376 without DO_GG): the same pipeline, the batches to ONE device in file order because each read's vote depends on the
+ * reads before it (rank.c) -- another vote: no candidate sets; a hit-dependent subset of windows: no map, and no coverage of the GG search's */
+int utree_search_run(const utree_ctr *ctr, utree_dev **devs, int n_dev, const utree_search_request *req, utree_search_stats *stats) {
+    if (!req || req->size != sizeof *req) return UTREE_E_ARG;
+    if (!ctr || !devs || n_dev < 1 || !req->reads_path || !req->out_path) return UTREE_E_ARG;
+    if (req->input_format < 0 || req->input_format > UTREE_INPUT_AUTO || (req->mates_path && req->interleaved)) return UTREE_E_ARG;
+    const int d = req->sample_delim;
+    if ((req->samples_path || req->sample_redistribute_path) && (d < 0 || d > 255 || d == '\t' || d == ' ' || d == '\r' || d == '\n')) return UTREE_E_ARG;
+    if ((req->redistribute_path || req->sample_redistribute_path) && req->max_passes > 1000) return UTREE_E_ARG;
+    if (req->rank) {
+        if (n_dev != 1 || req->mates_path || req->interleaved || req->coverage_path || req->redistribute_path || req->hitmap_path ||
+            req->sample_redistribute_path) return UTREE_E_ARG;
+        const int rc = utree_rank_reset(devs[0]);
+        if (rc) return rc;
+    }
+    return search_request(ctr, devs, n_dev, req, stats);
+}
+
+/* ---- the fixed-argument forms of utree_search_run (include/utree_amd.h) ------------------------------------------------------------------ */
+#define REQ(...) const utree_search_request r = {.size = sizeof r, .reads_path = reads_path, .out_path = out_path, .do_rc = do_rc, .host_threads = host_threads, __VA_ARGS__}
+#define REPORTS4 .input_format = input_format, .mates_path = mates_path, .interleaved = interleaved, .profile_path = profile_path, \
+                 .coverage_path = coverage_path, .redistribute_path = redistribute_path, .max_passes = max_passes
+
+int utree_search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
+                      int do_rc, int host_threads, utree_search_stats *stats) {
+    REQ(.input_format = UTREE_INPUT_REFERENCE);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+int utree_search_file_opts(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path,
+                           int do_rc, int host_threads, int input_format, utree_search_stats *stats) {
+    REQ(.input_format = input_format);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+int utree_search_file_profile(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
+                              int host_threads, int input_format, const char *profile_path, utree_search_stats *stats) {
+    REQ(.input_format = input_format, .profile_path = profile_path);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+int utree_search_file_coverage(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *out_path, int do_rc,
+                               int host_threads, int input_format, const char *profile_path, const char *coverage_path,
+                               utree_search_stats *stats) {
+    REQ(.input_format = input_format, .profile_path = profile_path, .coverage_path = coverage_path);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, const char *out_path,
+                            int do_rc, int host_threads, int input_format, const char *profile_path, const char *coverage_path,
+                            utree_search_stats *stats) {
+    REQ(.input_format = input_format, .mates_path = mates_path, .interleaved = !mates_path, .profile_path = profile_path, .coverage_path = coverage_path);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                                   int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
+                                   const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
+                                   utree_search_stats *stats) {
+    REQ(REPORTS4);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+int utree_search_file_hitmap(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int interleaved,
+                             const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
+                             const char *coverage_path, const char *redistribute_path, uint32_t max_passes, const char *hitmap_path,
+                             utree_search_stats *stats) {
+    REQ(REPORTS4, .hitmap_path = hitmap_path);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+int utree_search_file_samples(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path, int interleaved,
+                              const char *out_path, int do_rc, int host_threads, int input_format, const char *profile_path,
+                              const char *coverage_path, const char *redistribute_path, uint32_t max_passes, const char *hitmap_path,
+                              const char *samples_path, int delim, utree_search_stats *stats) {
+    REQ(REPORTS4, .hitmap_path = hitmap_path, .samples_path = samples_path, .sample_delim = delim);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+int utree_search_file_sample_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
+                                          int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
+                                          const char *profile_path, const char *coverage_path, const char *redistribute_path, uint32_t max_passes,
+                                          const char *hitmap_path, const char *samples_path, int delim, const char *sample_redistribute_path,
+                                          utree_search_stats *stats) {
+    REQ(REPORTS4, .hitmap_path = hitmap_path, .samples_path = samples_path, .sample_delim = delim, .sample_redistribute_path = sample_redistribute_path);
+    return utree_search_run(ctr, devs, n_dev, &r, stats);
+}
+
+/* the rank-specific search: one handle; without params there is nothing to run */
+int utree_rank_search_file_samples(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
+                                   const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
+                                   const char *samples_path, int delim, utree_search_stats *stats) {
+    if (!dev || !params) return UTREE_E_ARG;
+    REQ(.input_format = input_format, .rank = params, .profile_path = profile_path, .samples_path = samples_path, .sample_delim = delim);
+    return utree_search_run(ctr, &dev, 1, &r, stats);
 }
 int utree_rank_search_file_profile(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
                                    const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
                                    utree_search_stats *stats) {
     return utree_rank_search_file_samples(ctr, dev, reads_path, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, 0, stats);
 }
-int utree_rank_search_file_samples(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
-                                   const utree_rank_params *params, int host_threads, int input_format, const char *profile_path,
-                                   const char *samples_path, int delim, utree_search_stats *stats) {
-    if (!dev || !params) return UTREE_E_ARG;
-    if (samples_path && (delim < 0 || delim > 255 || delim == '\t' || delim == ' ' || delim == '\r' || delim == '\n')) return UTREE_E_ARG;
-    int rc = utree_rank_reset(dev);
-    if (rc) return rc;
-    return search_request(ctr, &dev, 1, reads_path, NULL, PAIRS_NONE, out_path, do_rc, params, host_threads, input_format, profile_path, NULL, NULL, 0, NULL,
-                          samples_path, delim, NULL, stats);
+int utree_rank_search_file_opts(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
+                                const utree_rank_params *params, int host_threads, int input_format, utree_search_stats *stats) {
+    return utree_rank_search_file_samples(ctr, dev, reads_path, out_path, do_rc, params, host_threads, input_format, NULL, NULL, 0, stats);
+}
+int utree_rank_search_file(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *out_path, int do_rc,
+                           const utree_rank_params *params, int host_threads, utree_search_stats *stats) {
+    return utree_rank_search_file_samples(ctr, dev, reads_path, out_path, do_rc, params, host_threads, UTREE_INPUT_REFERENCE, NULL, NULL, 0, stats);
 }

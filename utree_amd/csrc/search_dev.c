@@ -40,15 +40,7 @@
 #define DCHUNK_BYTES ((size_t)64 << 20)
 #define DOUT_BYTES   ((size_t)128 << 20)       /* output text a chunk may produce                                  */
 #define DMAX_READS   ((uint32_t)4 << 20)       /* reads per chunk (a chunk of shorter records takes the host path)  */
-#define LINELEN_MAX 16777216u                  /* itree.c:836                                                      */
 #define MAX_LANES 64
-
-/* bytes per chunk: DCHUNK_BYTES; UTREE_CHUNK_BYTES lowers it (tests: many chunk boundaries in a small file) */
-static size_t chunk_bytes(void) {
-    const char *e = getenv("UTREE_CHUNK_BYTES");
-    if (e && atoll(e) >= 64 && (size_t)atoll(e) < DCHUNK_BYTES) return (size_t)atoll(e);
-    return DCHUNK_BYTES;
-}
 
 /* ---- per-device buffers, kept in the utree_dev between searches (pinned memory is slow to allocate) ---- */
 typedef struct {
@@ -357,9 +349,9 @@ static void *lane_main(void *arg) {
         if (m1.flags || (m1.n_lines & 1u) || m1.n_lines > 2 * DMAX_READS || m1.n_lines / 2 > grid_reads) { dretry(P, c, off, 0); return NULL; }
         const uint32_t nr = m1.n_lines / 2;
         /* ---- classify (kernels.hip), then the output text ---- */
+        const utree_batch_view v = {b->d_in, b->d_seq_off, b->d_seq_len, nr, m1.total_bases, m1.max_len, P->do_rc, b->d_in, n, b->d_name_off, b->d_name_len, b->stream};
         if (nr) {
-            int e = utree_reports_classify(P->rep, L->g, L->dev, b->d_in, b->d_seq_off, b->d_seq_len, nr, m1.total_bases, m1.max_len, P->do_rc, b->d_res,
-                                           b->d_ws, b->ws_bytes, b->d_in, n, b->d_name_off, b->d_name_len, b->stream);
+            int e = utree_reports_classify(P->rep, L->g, L->dev, &v, b->d_res, b->d_ws, b->ws_bytes);
             if (e) { dfail(P, e); return NULL; }
             LK(utk_text_format(&L->dev->kimg, ((struct utree_search_ctx *)L->dev->search_ctx)->d_ix2rank, b->d_in, b->d_res, b->d_name_off,
                                b->d_name_len, nr, b->d_line_len, b->d_line_off, b->d_scan, b->scan_bytes, b->d_out, DOUT_BYTES, b->d_meta, 0,
@@ -397,7 +389,7 @@ static void *lane_main(void *arg) {
         pthread_mutex_unlock(&P->mu);
         /* the chunk is committed (published chunks are never dropped): its records and reads go into the search's reports, on this lane's stream
          * behind the vote -- d_in, d_seq_off and d_seq_len still hold the chunk, and d_name_off / d_name_len the names the lines print */
-        if (nr) { int pe = utree_reports_add(P->rep, L->g, b->d_in, b->d_seq_off, b->d_seq_len, b->d_res, nr, P->do_rc, 0, b->d_in, n, b->d_name_off, b->d_name_len, b->stream); if (pe) { dfail(P, pe); return NULL; } }
+        if (nr) { int pe = utree_reports_add(P->rep, L->g, &v, b->d_res, 0); if (pe) { dfail(P, pe); return NULL; } }
         double t4 = now_s();
         L->t_wait += t4 - t3;
         LH(hipStreamSynchronize(b->stream));
@@ -489,7 +481,7 @@ int utree_search_file_device(const utree_ctr *ctr, utree_dev **devs, int n_dev, 
         return UTREE_RETRY_HOST;
     }
     P->file_size = sb.st_size;
-    P->chunk_bytes = chunk_bytes();
+    P->chunk_bytes = utree_chunk_bytes(DCHUNK_BYTES);
     { int prc = find_parts(P); if (prc) { for (int p = 0; p < P->n_parts; ++p) close(P->fo_part[p]); close(P->fd); free(P); return prc; } }
     const int K = lanes_per_device(n_dev), n_lanes = K * n_dev;
     int rc = UTREE_OK;

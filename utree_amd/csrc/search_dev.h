@@ -4,6 +4,14 @@
 #include "utree_internal.h"
 #include "reports.h"
 
+#define LINELEN_MAX 16777216u                  /* itree.c:836 */
+/* bytes per chunk (search_dev.c) or per slot and input (search.c): `dflt`; UTREE_CHUNK_BYTES lowers it (tests: many chunk boundaries, and a
+ * carry in each file, of a small input) */
+static inline size_t utree_chunk_bytes(size_t dflt) {
+    const char *e = getenv("UTREE_CHUNK_BYTES");
+    return e && atoll(e) >= 64 && (size_t)atoll(e) < dflt ? (size_t)atoll(e) : dflt;
+}
+
 /* not an error of the ABI: the input needs the host framing (search.c runs it next) */
 #define UTREE_RETRY_HOST 1000
 

@@ -232,6 +232,16 @@ const char *utk_classify_long_name(const utk_image *im, char *buf, size_t cap);
 int utk_model_counts(const utk_image *im, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads,
                      int do_rc, unsigned long long *d_counts, void *stream);
 
+/* One batch as the searches' per-batch calls take it (dev_image.c, reports.c, search.c, search_dev.c): the reads as utree_classify_batch takes
+ * them, the text their names are in -- name r is d_text[d_name_off[r] .. + d_name_len[r]) of text_bytes bytes, read only by a report that
+ * reads names (else NULL / 0) -- and the stream everything of the batch is posted on. */
+typedef struct {
+    const uint8_t *d_bases; const uint64_t *d_off; const uint32_t *d_len;
+    uint32_t n_reads; uint64_t total_bases; uint32_t max_len; int do_rc;
+    const uint8_t *d_text; uint64_t text_bytes; const uint32_t *d_name_off, *d_name_len;
+    void *stream;
+} utree_batch_view;
+
 /* ---- small things every host file uses ---- */
 static inline double now_s(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 /* UTREE_TIMING=1 / UTREE_DEBUG=1: stage timings and warnings on stderr */

@@ -69,6 +69,18 @@ class RankParams(C.Structure):
     _fields_ = [("slack", C.c_uint32), ("sparsity", C.c_uint32), ("tolerance", C.c_uint32)]
 
 
+class SearchRequest(C.Structure):
+    """utree_search_request: one whole-file search as utree_search_run takes it; the paths are bytes or None, `size` is filled in."""
+    _fields_ = [("size", C.c_uint32), ("do_rc", C.c_int), ("host_threads", C.c_int), ("input_format", C.c_int),
+                ("reads_path", C.c_char_p), ("mates_path", C.c_char_p), ("interleaved", C.c_int), ("out_path", C.c_char_p),
+                ("rank", C.POINTER(RankParams)), ("profile_path", C.c_char_p), ("coverage_path", C.c_char_p),
+                ("redistribute_path", C.c_char_p), ("max_passes", C.c_uint32), ("hitmap_path", C.c_char_p), ("samples_path", C.c_char_p),
+                ("sample_redistribute_path", C.c_char_p), ("sample_delim", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__(size=C.sizeof(SearchRequest), **kw)
+
+
 class ProfileEntry(C.Structure):
     """utree_profile_entry: reads whose line prints (label, cut) -- cut -2 whole label, -1 empty taxon, >= 0 the first cut bytes."""
     _fields_ = [("label", C.c_uint32), ("cut", C.c_int32), ("reads", C.c_uint64)]
@@ -192,6 +204,7 @@ SYMBOLS = {
     "utree_search_prepare": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "utree_search_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                     C.POINTER(SearchStats)]),
+    "utree_search_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(SearchRequest), C.POINTER(SearchStats)]),
     "utree_profile_create": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "utree_profile_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "utree_profile_reset": (C.c_int, [C.c_void_p]),

@@ -920,7 +920,8 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
               mates: Optional[str] = None, interleaved: bool = False, redistribute: Optional[str] = None, redist_passes: int = 100,
               hitmap: Optional[str] = None, samples: Optional[str] = None, sample_delim: bytes = b"_",
               sample_redistribute: Optional[str] = None):
-    """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833): returns (code, stats); stats.fasta_error says which of
+    """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833) as one utree_search_request through utree_search_run (the utree_search_file*
+    calls named below are its fixed-argument forms): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
     FASTA / gzip input.  profile: also write the per-taxon read counts there; coverage: also write the per-taxon k-mer
     coverage there (utree_search_file_coverage; None: no such report).
@@ -938,46 +939,22 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
     if mates is not None and interleaved:
         raise ValueError("search_gg: give mates= or interleaved=True, not both")
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
+    return _search_run(db, arr, len(trees), "search_gg", fasta, out, rc, threads, input_format, sample_delim, mates_path=mates, interleaved=int(interleaved),
+                       profile_path=profile, coverage_path=coverage, redistribute_path=redistribute, max_passes=redist_passes, hitmap_path=hitmap,
+                       samples_path=samples, sample_redistribute_path=sample_redistribute)
+
+
+def _search_run(db, arr, n_dev, who, fasta, out, rc, threads, input_format, sample_delim, **fields):
+    """One SearchRequest from search_gg's / search_rank's arguments (paths: str or None), one utree_search_run: (code, stats)."""
+    req = _lib.SearchRequest(do_rc=int(rc), host_threads=threads, input_format=input_format, reads_path=fasta.encode(), out_path=out.encode())
+    for k, v in fields.items():
+        setattr(req, k, v.encode() if isinstance(v, str) else v)
+    if req.samples_path is not None or req.sample_redistribute_path is not None:
+        if not (isinstance(sample_delim, (bytes, bytearray)) and len(sample_delim) == 1):
+            raise ValueError("%s: sample_delim must be one byte" % who)
+        req.sample_delim = sample_delim[0]
     st = _lib.SearchStats()
-    if sample_redistribute is not None:
-        if not (isinstance(sample_delim, (bytes, bytearray)) and len(sample_delim) == 1):
-            raise ValueError("search_gg: sample_delim must be one byte")
-        enc = lambda p: p.encode() if p is not None else None
-        code = _lib.load().utree_search_file_sample_redistribute(db._h, arr, len(trees), fasta.encode(), enc(mates), int(interleaved), out.encode(),
-                                                                 int(rc), threads, input_format, enc(profile), enc(coverage), enc(redistribute),
-                                                                 redist_passes, enc(hitmap), enc(samples), sample_delim[0],
-                                                                 sample_redistribute.encode(), C.byref(st))
-        return code, st
-    if samples is not None:
-        if not (isinstance(sample_delim, (bytes, bytearray)) and len(sample_delim) == 1):
-            raise ValueError("search_gg: sample_delim must be one byte")
-        enc = lambda p: p.encode() if p is not None else None
-        code = _lib.load().utree_search_file_samples(db._h, arr, len(trees), fasta.encode(), enc(mates), int(interleaved), out.encode(), int(rc),
-                                                     threads, input_format, enc(profile), enc(coverage), enc(redistribute), redist_passes,
-                                                     enc(hitmap), samples.encode(), sample_delim[0], C.byref(st))
-        return code, st
-    if hitmap is not None:
-        enc = lambda p: p.encode() if p is not None else None
-        code = _lib.load().utree_search_file_hitmap(db._h, arr, len(trees), fasta.encode(), enc(mates), int(interleaved), out.encode(), int(rc),
-                                                    threads, input_format, enc(profile), enc(coverage), enc(redistribute), redist_passes,
-                                                    hitmap.encode(), C.byref(st))
-        return code, st
-    if redistribute is not None:
-        code = _lib.load().utree_search_file_redistribute(db._h, arr, len(trees), fasta.encode(), mates.encode() if mates is not None else None,
-                                                          int(interleaved), out.encode(), int(rc), threads, input_format,
-                                                          profile.encode() if profile is not None else None,
-                                                          coverage.encode() if coverage is not None else None, redistribute.encode(),
-                                                          redist_passes, C.byref(st))
-        return code, st
-    if mates is not None or interleaved:
-        code = _lib.load().utree_search_pairs_file(db._h, arr, len(trees), fasta.encode(), mates.encode() if mates is not None else None,
-                                                   out.encode(), int(rc), threads, input_format,
-                                                   profile.encode() if profile is not None else None,
-                                                   coverage.encode() if coverage is not None else None, C.byref(st))
-        return code, st
-    code = _lib.load().utree_search_file_coverage(db._h, arr, len(trees), fasta.encode(), out.encode(), int(rc), threads, input_format,
-                                                  profile.encode() if profile is not None else None,
-                                                  coverage.encode() if coverage is not None else None, C.byref(st))
+    code = _lib.load().utree_search_run(db._h, arr, n_dev, C.byref(req), C.byref(st))
     return code, st
 
 
@@ -986,18 +963,9 @@ def search_rank(db: CtrDB, tree: DeviceTree, fasta: str, out: str, rc: bool = Fa
                 samples: Optional[str] = None, sample_delim: bytes = b"_"):
     """XT_doSearch32(utree, in, out, 0, speed, doRC): the `xtree-search` binary (itree.c:1376 without DO_GG).  profile, samples,
     sample_delim: as search_gg's."""
-    st = _lib.SearchStats()
     prm = _lib.RankParams(slack, sparsity, tolerance)
-    if samples is not None:
-        if not (isinstance(sample_delim, (bytes, bytearray)) and len(sample_delim) == 1):
-            raise ValueError("search_rank: sample_delim must be one byte")
-        code = _lib.load().utree_rank_search_file_samples(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm), threads, input_format,
-                                                          profile.encode() if profile is not None else None, samples.encode(), sample_delim[0],
-                                                          C.byref(st))
-        return code, st
-    code = _lib.load().utree_rank_search_file_profile(db._h, tree._h, fasta.encode(), out.encode(), int(rc), C.byref(prm), threads,
-                                                      input_format, profile.encode() if profile is not None else None, C.byref(st))
-    return code, st
+    return _search_run(db, (C.c_void_p * 1)(tree._h), 1, "search_rank", fasta, out, rc, threads, input_format, sample_delim, rank=C.pointer(prm),
+                       profile_path=profile, samples_path=samples)
 
 
 def build(fasta: str, mapfile: str, ubt: str, W: int = 8, I: int = 2, complevel: int = 1, gg: bool = True, device: int = 0):
