@@ -474,7 +474,8 @@ int utree_search_pairs_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, c
  *     <s>\t...\n    for every label text with assigned > 0 and every ';'-prefix of one, in unsigned bytewise order (shorter first)
  * G is the profile's `classified` (every read with found > 0 has a candidate): the `assigned` column sums to it.
  * What this is not: a read whose best label is itself an interior taxon stays there (BUILD_GG relabels colliding k-mers to shorter labels,
- * itree.c:268-307); there is no genome-length or k-mer-distribution normalisation; there is no per-read reassignment output.
+ * itree.c:268-307); there is no genome-length or k-mer-distribution normalisation.  The per-read reassignment is a report of its own:
+ * utree_redist_classify_batch_keys / utree_redist_assign / utree_redist_reads_format below (UTREE_REDISTRIBUTE_READS).
  *
  * A handle lives on ONE device for one database: a 64-bit counter per label for the single-candidate reads, an open-addressed table of the
  * multi-label sets with their read counts (16 B a slot) and an arena of eight labels per slot for the sets' members.
@@ -513,6 +514,33 @@ int utree_redist_solve(utree_redist *rd, uint32_t max_passes, utree_redist_entry
 /* Host only: entries (label indices of ctr; several with one label are added up) -> merged by text, rolled up, written to `path`. */
 int utree_redist_write(const utree_ctr *ctr, const utree_redist_entry *e, size_t n, uint64_t n_reads, uint64_t ambiguous, uint32_t passes,
                        const char *path);
+/* ---- each read's redistributed label (xtree's --perq-out) ----
+ * A KEY per read says where its candidates are: UTREE_REDIST_KEY_NONE -- no hit (found == 0), or the pass refused the read (it has then set
+ * the handle's error word, as without keys); l < 0x80000000 -- the read's only candidate is the file-order label index l;
+ * 0x80000000 | slot -- its candidates are the set in `slot` of the handle's table (at most 2^28 slots).  Every read of a batch gets exactly
+ * one key.  Keys of a handle stay valid until utree_redist_reset: utree_redist_merge INTO a handle only adds slots and never moves one, so the
+ * keys a handle gave before a merge are still right after it.  Nothing is normalised, and a read whose best label is an interior taxon stays
+ * there, as above. */
+#define UTREE_REDIST_KEY_NONE 0xFFFFFFFFu
+/* utree_redist_classify_batch (same arguments, d_out bit for bit the same, the same sets added) that also writes d_key[0 .. n_reads).
+ * UTREE_E_UNSUPPORTED for a database of 2^31 labels or more, UTREE_E_ARG for d_key == NULL with n_reads > 0. */
+int utree_redist_classify_batch_keys(utree_redist *rd, utree_dev *dev, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                                     uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace,
+                                     size_t workspace_bytes, uint32_t *d_key, void *stream);
+/* The assignment of n keys.  d_key: keys of `keys`' table, on its device, as are d_label and d_ncand (may be NULL).  `solved`: `keys` itself, or
+ * the handle `keys` was merged into, after utree_redist_solve -- a later add, insert, merge into or reset of `solved` ends that state.
+ * d_label[r] = win(S_r, T_P), the label utree_redist_solve's `assigned` counts read r under, d_ncand[r] = |S_r| (1: the read never had another
+ * candidate); KEY_NONE gives 0xFFFFFFFF and 0; a key that names no label of the database and no occupied slot of the table gives 0xFFFFFFFF and
+ * 0xFFFFFFFF, and nothing is read for it.  UTREE_E_ARG when `solved` is not in the solved state, the handles are of different databases, or
+ * d_key or d_label is NULL with n > 0.  With solved != keys the call first brings T_P over to `keys`' device; the winners of `keys`' slots are
+ * computed once per solve, not per call.  Synchronous up to that point, asynchronous on `stream` afterwards. */
+int utree_redist_assign(utree_redist *keys, utree_redist *solved, const uint32_t *d_key, uint64_t n, uint32_t *d_label, uint32_t *d_ncand,
+                        void *stream);
+/* Host only: one line "name\tlabel text\tncand\n" for every read with label != 0xFFFFFFFF, in order; name = names[name_off[i] .. + name_len[i]),
+ * the label text whole (never a ';'-prefix; it may be empty).  Returns bytes written, or (size_t)-1 when cap is too small or a label is none of
+ * ctr's -- as utree_hitmap_format. */
+size_t utree_redist_reads_format(const utree_ctr *ctr, const uint8_t *names, const uint64_t *name_off, const uint32_t *name_len,
+                                 const uint32_t *label, const uint32_t *ncand, size_t n, char *out, size_t cap);
 /* utree_search_file_coverage with mates_path, interleaved, redistribute_path and max_passes set as well. */
 int utree_search_file_redistribute(const utree_ctr *ctr, utree_dev **devs, int n_dev, const char *reads_path, const char *mates_path,
                                    int interleaved, const char *out_path, int do_rc, int host_threads, int input_format,
@@ -721,11 +749,12 @@ int utree_search_file_sample_redistribute(const utree_ctr *ctr, utree_dev **devs
  * above is a fixed-argument form of this call: it fills the fields its comment names, leaves the rest 0 / NULL and calls utree_search_run.
  * A report's path that is NULL means: no such report -- nothing of it is allocated, uploaded or launched, and the per-read output, stdout, the
  * stats and the other reports are those of a search without it.  A search that fails returns its own code and leaves every report path as it
- * was; the reports are written when the search has succeeded, in the order coverage, redistribution, sample table, per-sample
+ * was; the reports are written when the search has succeeded, in the order coverage, redistribution, redistributed reads, sample table, per-sample
  * redistribution, profile, and only when the devices counted every read exactly once.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
-    uint32_t size;                    /* = sizeof(utree_search_request): anything else is UTREE_E_ARG (a caller built against another layout) */
+    uint32_t size;                    /* = sizeof(utree_search_request), or the size of the layout without redistribute_reads_path (a caller built
+                                         before that field: a request without that report); anything else is UTREE_E_ARG                      */
     int do_rc, host_threads;          /* RC; the host formatting team (<= 0: as many as OpenMP gives, at most 16)                              */
     int input_format;                 /* UTREE_INPUT_*; AUTO looks at the first byte; a non-reference format also reads gzip through zlib       */
     const char *reads_path;           /* the reads; with mates_path the first mates; with interleaved records 2i and 2i+1 are pair i           */
@@ -735,7 +764,8 @@ typedef struct {
     const char *out_path;
     const utree_rank_params *rank;    /* non-NULL: the rank-specific search on ONE device handle (n_dev must be 1), whose carried array is reset
                                          first (utree_rank_reset).  It reads no pairs and writes a profile and a sample table only: any of
-                                         coverage_path, redistribute_path, hitmap_path, sample_redistribute_path is UTREE_E_ARG                */
+                                         coverage_path, redistribute_path, hitmap_path, sample_redistribute_path, redistribute_reads_path is
+                                         UTREE_E_ARG                                                                                          */
     const char *profile_path;         /* per-taxon read counts, each device handle counting its own reads (UTREE_PROFILE_CAPACITY truncated-taxon
                                          slots, default 2^20).  Not written: UTREE_E_PROFILE, utree_last_hip_error says why                   */
     const char *coverage_path;        /* distinct database k-mers covered per taxon; one handle per device handle, merged before the file is
@@ -745,7 +775,7 @@ typedef struct {
                                          reads not added once --: UTREE_E_PROFILE (no code of its own), utree_last_hip_error names the file and
                                          the cause.  (A search into a pipe that the host pipeline has to take over half-way cannot take back the
                                          sets of the chunks it drops: it ends with this error rather than a wrong table.)                      */
-    uint32_t max_passes;              /* of both redistributions (0: the default; more than 1000 with either path: UTREE_E_ARG)               */
+    uint32_t max_passes;              /* of the redistributions (0: the default; more than 1000 with any of their paths: UTREE_E_ARG)         */
     const char *hitmap_path;          /* every query's hit map, and the label texts to <hitmap_path>.labels, line i (0-based) = label index i.
                                          Written in step with the output: the writer stage commits a chunk's output lines and its map lines
                                          together, so after a framing error or UTREE_E_PAIRS both files hold the same queries.  Always the host
@@ -758,6 +788,11 @@ typedef struct {
                                          written: UTREE_E_PROFILE (the profile's failure wins, then the redistribution's, the sample table's,
                                          this report's)                                                                                       */
     int sample_delim;                 /* one byte, 0: '_'; with either sample report not TAB, space, CR or LF (UTREE_E_ARG)                    */
+    const char *redistribute_reads_path;   /* each classified query's redistributed label: one line "name \t label text \t n_candidates" per line
+                                         of the output, in its order (pairs: under mate 1's name), no header.  With or without
+                                         redistribute_path (ONE solve serves both files; max_passes, UTREE_REDIST_CAPACITY apply).  Always the
+                                         host framing pipeline; the keys are spooled to <path>.spool while searching (removed on every way out)
+                                         and assigned after the solve.  Not written: UTREE_E_PROFILE, ranking with redistribute_path           */
 } utree_search_request;
 /* The one call that checks a request and runs it: GG search over devs[0 .. n_dev), or the rank-specific one.  Every argument is checked before
  * `ctr` or a device handle is looked at: UTREE_E_ARG for a wrong size, a NULL ctr, devs, reads_path or out_path, n_dev < 1, an input_format

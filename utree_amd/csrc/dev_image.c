@@ -893,14 +893,15 @@ int utree_classify_batch(utree_dev *d, const uint8_t *d_bases, const uint64_t *d
                          uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out,
                          void *d_workspace, size_t workspace_bytes, void *stream) {
     const utree_batch_view v = {d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, NULL, 0, NULL, NULL, stream};
-    return utree_classify_view(d, &v, d_out, d_workspace, workspace_bytes, NULL, NULL);
+    return utree_classify_view(d, &v, d_out, d_workspace, workspace_bytes, NULL, NULL, NULL);
 }
 
 /* rd: NULL (utree_classify_batch: nothing new is launched), or the redistribution handle the batch's candidate sets go into -- one more
  * pass over the records between the classify kernels and the vote, while each read's (rank, count) list still stands (redist.c); srd: NULL,
- * or the handle the batch's reads are counted in per (sample, candidate set), at the same place and from the same lists (sredist.c) */
+ * or the handle the batch's reads are counted in per (sample, candidate set), at the same place and from the same lists (sredist.c);
+ * d_key: NULL, or where rd's pass also writes every read's key */
 int utree_classify_view(utree_dev *d, const utree_batch_view *v, utree_result *d_out, void *d_workspace, size_t workspace_bytes,
-                        struct utree_redist *rd, struct utree_sredist *srd) {
+                        struct utree_redist *rd, struct utree_sredist *srd, uint32_t *d_key) {
     const uint8_t *d_bases = v->d_bases; const uint64_t *d_off = v->d_off; const uint32_t *d_len = v->d_len;
     const uint32_t n_reads = v->n_reads, max_len = v->max_len; const uint64_t total_bases = v->total_bases; const int do_rc = v->do_rc;
     int rc = UTREE_OK;
@@ -984,7 +985,7 @@ int utree_classify_view(utree_dev *d, const utree_batch_view *v, utree_result *d
             if (e0) { HIPCHK(hipEventRecord(e1, st)); d->recorded[tslot] = 1; }
         }
     }
-    if (rd && (rc = utree_redist_add_pending(rd, &d->kimg, d_out, &w, n_reads, d->n_cu, st))) goto fail;     /* every path has converged here */
+    if (rd && (rc = utree_redist_add_pending(rd, &d->kimg, d_out, &w, n_reads, d->n_cu, d_key, st))) goto fail;     /* every path has converged here */
     if (srd && (rc = utree_sredist_add_pending(srd, &d->kimg, d_out, &w, v->d_text, v->text_bytes, v->d_name_off, v->d_name_len, n_reads, d->n_cu, st))) goto fail;
     KCHK(utk_vote(&d->kimg, d_out, &w, n_reads, st));
     /* the reads the lane pass left, and the batch's error word, come back behind the kernels without a wait */

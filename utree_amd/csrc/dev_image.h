@@ -39,13 +39,14 @@ struct utree_dev {
 
 /* utree_classify_batch on a view, with the batch's candidate sets -- one more pass between the classify kernels and the vote, while each read's
  * (rank, count) list still stands -- added to `rd` (NULL: not; redist.c) and / or, with the view's names, counted per (sample, candidate set)
- * in `srd` (NULL: not; sredist.c).  Both NULL: nothing more is launched and the names are not read */
+ * in `srd` (NULL: not; sredist.c).  Both NULL: nothing more is launched and the names are not read.  d_key: NULL, or -- with `rd` -- where the
+ * key of every read's candidates in rd's table goes (n_reads of them; include/utree_amd.h: utree_redist_classify_batch_keys) */
 struct utree_redist;
 struct utree_sredist;
 int utree_classify_view(utree_dev *d, const utree_batch_view *v, utree_result *d_out, void *d_workspace, size_t workspace_bytes,
-                        struct utree_redist *rd, struct utree_sredist *srd);
+                        struct utree_redist *rd, struct utree_sredist *srd, uint32_t *d_key);
 int utree_redist_add_pending(struct utree_redist *rd, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, uint32_t n_reads,
-                             int n_cu, void *stream);
+                             int n_cu, uint32_t *d_key, void *stream);
 int utree_redist_reads(struct utree_redist *rd, uint64_t *n_reads);
 int utree_sredist_add_pending(struct utree_sredist *h, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, const uint8_t *d_text,
                               uint64_t text_bytes, const uint32_t *d_name_off, const uint32_t *d_name_len, uint32_t n_reads, int n_cu, void *stream);

@@ -31,6 +31,13 @@
  *                           codes as for UTREE_PROFILE, with which and with UTREE_COVERAGE / UTREE_MATES it may be combined.
  *                           UTREE_REDIST_PASSES=<1..1000> caps the passes (default 100; 1: one pass, xtree's fast mode),
  *                           UTREE_REDIST_CAPACITY=<slots> sizes the table of distinct sets (default 2^22).  Unset: nothing of it runs
+ *     UTREE_REDISTRIBUTE_READS=<path> opt-in, xtree-searchGG only (xtree-search ignores it, as it ignores UTREE_REDISTRIBUTE): also write, for every
+ *                           query that has a line in the output and in that order, "name \t label text \t n_candidates": the label the
+ *                           redistribution assigns the read to (include/utree_amd.h: utree_redist_assign), the text whole; n_candidates 1: the
+ *                           read never had another candidate.  No header; pairs print under mate 1's name.  With or without
+ *                           UTREE_REDISTRIBUTE (one solve serves both files; UTREE_REDIST_PASSES and UTREE_REDIST_CAPACITY apply), and
+ *                           with everything that combines with it.  The search takes the host framing pipeline and spools the reads' keys to
+ *                           <path>.spool, which is removed on every way out.  Path checks, failures and exit codes as for UTREE_REDISTRIBUTE
  *     UTREE_HITMAP=<path>   opt-in, xtree-searchGG only (xtree-search says so in one line on stderr and ignores it): also write, for EVERY query, which
  *                           label each of its k-mer windows hit, in window order, as runs "code:count" (include/utree_amd.h: utree_hitmap_format),
  *                           and the label texts to <path>.labels (line i = label index i).  The map is written in step with the output, so
@@ -138,7 +145,8 @@ int main(int argc, char *argv[]) {
     if (DO_GG && (p = getenv("UTREE_COVERAGE")) && *p) { check_report_path(p, "coverage"); req.coverage_path = p; }
     if (DO_GG && (p = getenv("UTREE_REDISTRIBUTE")) && *p) { check_report_path(p, "redistribution"); req.redistribute_path = p; }
     if (DO_GG && (p = getenv("UTREE_SAMPLE_REDISTRIBUTE")) && *p) { check_report_path(p, "sample redistribution"); req.sample_redistribute_path = p; }
-    if ((req.redistribute_path || req.sample_redistribute_path) && getenv("UTREE_REDIST_PASSES")) {   /* (else 0: the default) */
+    if (DO_GG && (p = getenv("UTREE_REDISTRIBUTE_READS")) && *p) { check_report_path(p, "redistributed reads"); req.redistribute_reads_path = p; }
+    if ((req.redistribute_path || req.sample_redistribute_path || req.redistribute_reads_path) && getenv("UTREE_REDIST_PASSES")) {   /* (else 0: the default) */
         const long v = atol(getenv("UTREE_REDIST_PASSES"));
         if (v < 1 || v > 1000) { fputs("ERROR: UTREE_REDIST_PASSES must be 1 .. 1000\n", stderr); exit(1); }
         req.max_passes = (uint32_t)v;

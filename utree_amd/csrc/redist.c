@@ -11,7 +11,12 @@
  *     <taxon>\t...\n      one row per taxon with assigned > 0 and ';'-prefix of one, in unsigned bytewise order (shorter first on a tie)
  *
  * What it is not: a read whose best label is an interior taxon stays there (BUILD_GG relabels colliding k-mers to shorter labels); nothing is
- * normalised by genome length or k-mer distribution; no per-read reassignment is written.
+ * normalised by genome length or k-mer distribution.
+ *
+ * Each read's redistributed label (utree_redist_classify_batch_keys, utree_redist_assign, utree_redist_reads_format): the per-batch pass can also
+ * write a key per read -- nothing, a label, or the slot its set is in --, a solve keeps its final tally T_P in the handle, and the assignment
+ * of any number of keys is then win(set, T_P) per slot, computed once per solve, and a gather.  The same limits hold: an interior best label
+ * stays, nothing is normalised.
  */
 #define _GNU_SOURCE
 #define __HIP_PLATFORM_AMD__ 1
@@ -29,7 +34,23 @@ struct utree_redist {
     utk_redist_tab tab;                 /* device pointers */
     unsigned long long *d_tally;        /* [2][n_labels]: the passes' previous and next tally */
     uint32_t n_labels;
+    /* the last solve, kept for utree_redist_assign: T_P is tp (one half of d_tally).  `solved` is cleared, and `changed` counted up, by every
+     * later add, insert, merge into and reset (adds come from several threads: atomics) */
+    int solved;
+    unsigned changed;
+    unsigned long long *tp, solve_id;   /* solve_id: unique per solve of any handle */
+    uint32_t passes;
+    /* the assignment's side, for the keys of THIS handle's table: win(slot, T_P) and the slot's candidates, (mask + 1) * 4 bytes each, allocated
+     * on first use; valid for the solve win_of of a handle whose tally was here (d_tp when it was another's) while `changed` is win_changed */
+    uint32_t *d_win, *d_ncand;
+    unsigned long long *d_tp, win_of;
+    unsigned win_changed;
 };
+static unsigned long long g_solve_id;
+static void touched(utree_redist *rd) {
+    __atomic_store_n(&rd->solved, 0, __ATOMIC_RELEASE);
+    __atomic_fetch_add(&rd->changed, 1u, __ATOMIC_RELAXED);
+}
 
 #define CHK(x) do { if ((x) != hipSuccess) { utree_dev_set_hip_error((int)hipGetLastError(), #x); rc = UTREE_E_HIP; goto fail; } } while (0)
 
@@ -59,6 +80,7 @@ int utree_redist_create(utree_dev *dev, uint32_t set_capacity, utree_redist **ou
 
 int utree_redist_reset(utree_redist *rd) {
     if (!rd) return UTREE_E_ARG;
+    touched(rd);
     if (hipSetDevice(rd->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return UTREE_E_HIP;    /* adds in flight on any stream */
     if (hipMemset(rd->tab.slots, 0, ((size_t)rd->tab.mask + 1) * 16) != hipSuccess) return UTREE_E_HIP;        /* key 0 = free */
     if (hipMemset(rd->tab.single, 0, (size_t)(rd->n_labels ? rd->n_labels : 1) * 8) != hipSuccess) return UTREE_E_HIP;
@@ -75,12 +97,16 @@ void utree_redist_free(utree_redist *rd) {
     if (rd->tab.single) hipFree(rd->tab.single);
     if (rd->tab.misc) hipFree(rd->tab.misc);
     if (rd->d_tally) hipFree(rd->d_tally);
+    if (rd->d_win) hipFree(rd->d_win);
+    if (rd->d_ncand) hipFree(rd->d_ncand);
+    if (rd->d_tp) hipFree(rd->d_tp);
     free(rd);
 }
 
 int utree_redist_add_pending(utree_redist *rd, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, uint32_t n_reads, int n_cu,
-                             void *stream) {
-    const int e = utk_redist_add(&rd->tab, im, d_res, ws, n_reads, n_cu, stream);
+                             uint32_t *d_key, void *stream) {
+    touched(rd);
+    const int e = utk_redist_add(&rd->tab, im, d_res, ws, n_reads, n_cu, d_key, stream);
     if (e) { utree_dev_set_hip_error(e, "utk_redist_add"); return UTREE_E_HIP; }
     return UTREE_OK;
 }
@@ -90,7 +116,16 @@ int utree_redist_classify_batch(utree_redist *rd, utree_dev *dev, const uint8_t 
                                 size_t workspace_bytes, void *stream) {
     if (!rd || !dev || rd->device != dev->device || rd->n_labels != dev->hdr.n_labels) return UTREE_E_ARG;
     const utree_batch_view v = {d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, NULL, 0, NULL, NULL, stream};
-    return utree_classify_view(dev, &v, d_out, d_workspace, workspace_bytes, rd, NULL);
+    return utree_classify_view(dev, &v, d_out, d_workspace, workspace_bytes, rd, NULL, NULL);
+}
+
+int utree_redist_classify_batch_keys(utree_redist *rd, utree_dev *dev, const uint8_t *d_bases, const uint64_t *d_off, const uint32_t *d_len,
+                                     uint32_t n_reads, uint64_t total_bases, uint32_t max_len, int do_rc, utree_result *d_out, void *d_workspace,
+                                     size_t workspace_bytes, uint32_t *d_key, void *stream) {
+    if (!rd || !dev || rd->device != dev->device || rd->n_labels != dev->hdr.n_labels || (n_reads && !d_key)) return UTREE_E_ARG;
+    if (rd->n_labels >= 0x80000000u) return UTREE_E_UNSUPPORTED;               /* a label key is below 2^31 */
+    const utree_batch_view v = {d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, NULL, 0, NULL, NULL, stream};
+    return utree_classify_view(dev, &v, d_out, d_workspace, workspace_bytes, rd, NULL, d_key);
 }
 
 /* the handle's error word as a code and a text */
@@ -190,6 +225,7 @@ done:
 
 int utree_redist_merge(utree_redist *dst, utree_redist *src) {
     if (!dst || !src || dst == src || dst->n_labels != src->n_labels) return UTREE_E_ARG;
+    touched(dst);                                                       /* (slots are only added: dst's keys stay valid) */
     size_t ns = 0, nl = 0;
     uint64_t reads = 0;
     int rc = utree_redist_read(src, NULL, 0, NULL, 0, &ns, &nl, &reads, NULL);
@@ -234,6 +270,8 @@ int utree_redist_solve(utree_redist *rd, uint32_t max_passes, utree_redist_entry
     unsigned long long *prev = rd->d_tally, *next = rd->d_tally + (nl ? nl : 1);
     uint32_t p = 0;
     *n = 0;
+    const unsigned changed = __atomic_load_n(&rd->changed, __ATOMIC_RELAXED);
+    __atomic_store_n(&rd->solved, 0, __ATOMIC_RELEASE);
     CHK(hipSetDevice(rd->device));
     CHK(hipDeviceSynchronize());
     CHK(hipMemcpy(misc, rd->tab.misc, sizeof misc, hipMemcpyDeviceToHost));
@@ -266,10 +304,85 @@ int utree_redist_solve(utree_redist *rd, uint32_t max_passes, utree_redist_entry
     if (k > cap) rc = UTREE_E_ARG;
     if (passes) *passes = p;
     if (ambiguous) *ambiguous = misc[4];
+    CHK(hipDeviceSynchronize());
+    /* T_P stays where the loop left it, for utree_redist_assign (nothing was added meanwhile: else the tally is not that of the table) */
+    if (__atomic_load_n(&rd->changed, __ATOMIC_RELAXED) == changed) {
+        rd->tp = prev; rd->passes = p; rd->solve_id = __atomic_add_fetch(&g_solve_id, 1ull, __ATOMIC_RELAXED);
+        __atomic_store_n(&rd->solved, 1, __ATOMIC_RELEASE);
+    }
 fail:
     (void)hipDeviceSynchronize();
     free(m);
     return rc;
+}
+
+int utree_redist_assign(utree_redist *keys, utree_redist *solved, const uint32_t *d_key, uint64_t n, uint32_t *d_label, uint32_t *d_ncand,
+                        void *stream) {
+    if (!keys || !solved || keys->n_labels != solved->n_labels || !__atomic_load_n(&solved->solved, __ATOMIC_ACQUIRE)) return UTREE_E_ARG;
+    if (n && (!d_key || !d_label)) return UTREE_E_ARG;
+    int rc = UTREE_OK;
+    void *h = NULL;
+    const size_t nl = keys->n_labels ? keys->n_labels : 1, ns = (size_t)keys->tab.mask + 1;
+    const unsigned changed = __atomic_load_n(&keys->changed, __ATOMIC_RELAXED);
+    CHK(hipSetDevice(keys->device));
+    if (!keys->d_win || keys->win_of != solved->solve_id || keys->win_changed != changed) {
+        /* once per solve: T_P to this device, every slot's winner under it.  Synchronous: the tally's owner may go on to solve again */
+        if (!keys->d_win && (hipMalloc((void **)&keys->d_win, ns * 4) != hipSuccess || hipMalloc((void **)&keys->d_ncand, ns * 4) != hipSuccess)) {
+            (void)hipGetLastError();
+            if (keys->d_win) hipFree(keys->d_win);
+            keys->d_win = NULL; keys->d_ncand = NULL;
+            return UTREE_E_NOMEM;
+        }
+        keys->win_of = 0;
+        const unsigned long long *tp = solved->tp;
+        if (solved != keys) {
+            if (!keys->d_tp && hipMalloc((void **)&keys->d_tp, nl * 8) != hipSuccess) { (void)hipGetLastError(); keys->d_tp = NULL; return UTREE_E_NOMEM; }
+            if (solved->device == keys->device) CHK(hipMemcpy(keys->d_tp, solved->tp, nl * 8, hipMemcpyDeviceToDevice));
+            else {                                                      /* through the host: any two devices */
+                if (!(h = malloc(nl * 8))) return UTREE_E_NOMEM;
+                CHK(hipSetDevice(solved->device));
+                CHK(hipMemcpy(h, solved->tp, nl * 8, hipMemcpyDeviceToHost));
+                CHK(hipSetDevice(keys->device));
+                CHK(hipMemcpy(keys->d_tp, h, nl * 8, hipMemcpyHostToDevice));
+            }
+            tp = keys->d_tp;
+        }
+        CHK(hipDeviceSynchronize());                                    /* adds to this table in flight on any stream */
+        if (utk_redist_winner(&keys->tab, tp, keys->d_win, keys->d_ncand, NULL)) { rc = UTREE_E_HIP; goto fail; }
+        CHK(hipStreamSynchronize(NULL));
+        keys->win_of = solved->solve_id; keys->win_changed = changed;
+    }
+    if (utk_redist_assign(&keys->tab, keys->d_win, keys->d_ncand, d_key, n, d_label, d_ncand, stream)) {
+        utree_dev_set_hip_error((int)hipGetLastError(), "utk_redist_assign");
+        rc = UTREE_E_HIP;
+    }
+fail:
+    free(h);
+    return rc;
+}
+
+/* ---- host: one line per read that has a label ------------------------------------------------------------------------------- */
+size_t utree_redist_reads_format(const utree_ctr *ctr, const uint8_t *names, const uint64_t *name_off, const uint32_t *name_len,
+                                 const uint32_t *label, const uint32_t *ncand, size_t n, char *out, size_t cap) {
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t l = label[i];
+        if (l == 0xFFFFFFFFu) continue;
+        if (l >= ctr->info.n_labels) return (size_t)-1;
+        char tok[16];
+        size_t t = 0;
+        uint32_t v = ncand[i];
+        do { tok[t++] = (char)('0' + v % 10); v /= 10; } while (v);
+        const size_t ll = ctr->label_len[l], need = (size_t)name_len[i] + 1 + ll + 1 + t + 1;
+        if (need > cap - at) return (size_t)-1;
+        memcpy(out + at, names + name_off[i], name_len[i]); at += name_len[i];
+        out[at++] = '\t';
+        memcpy(out + at, ctr->labels[l], ll); at += ll;
+        out[at++] = '\t';
+        while (t) out[at++] = tok[--t];
+        out[at++] = '\n';
+    }
+    return at;
 }
 
 /* ---- host: every label's figures as rows of the taxon table (taxon_table.c) ----------------------------------------------- */

@@ -27,9 +27,10 @@ typedef struct {
 } utk_redist_tab;
 
 /* the candidate sets of a batch whose records still wait for utk_vote (RANK_PENDING / CUT_PENDING, or finished) into the table; misc[0] +=
- * n_reads; asynchronous on `stream` */
+ * n_reads; d_key: NULL, or where every read's key goes (include/utree_amd.h: UTREE_REDIST_KEY_NONE; another instantiation of the kernel);
+ * asynchronous on `stream` */
 int utk_redist_add(const utk_redist_tab *t, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, uint32_t n_reads, int n_cu,
-                   void *stream);
+                   uint32_t *d_key, void *stream);
 /* n_sets sets given flat -- set i is d_labels[d_first[i] .. + d_n[i]) with d_reads[i] reads -- re-inserted (utree_redist_merge) */
 int utk_redist_insert(const utk_redist_tab *t, const unsigned long long *d_reads, const unsigned long long *d_first, const uint32_t *d_n,
                       const uint32_t *d_labels, uint64_t n_sets, void *stream);
@@ -39,6 +40,12 @@ int utk_redist_sum(unsigned long long *dst, const unsigned long long *src, uint6
 int utk_redist_tally0(const utk_redist_tab *t, unsigned long long *tally, void *stream);
 /* one pass: next[l] = single[l] + reads of the sets whose richest candidate under `prev` is l; misc[3] = sum over l of |next[l] - prev[l]| */
 int utk_redist_pass(const utk_redist_tab *t, const unsigned long long *prev, unsigned long long *next, void *stream);
+
+/* every slot's winner under `tally` and its number of candidates: d_win[s] = win(set s, tally), d_ncand[s] = |set s| (free: ~0 and 0); no atomics */
+int utk_redist_winner(const utk_redist_tab *t, const unsigned long long *tally, uint32_t *d_win, uint32_t *d_ncand, void *stream);
+/* n keys of the table -> label and candidates of each read, from d_win / d_ncand: a pure gather (d_ncand_out may be NULL) */
+int utk_redist_assign(const utk_redist_tab *t, const uint32_t *d_win, const uint32_t *d_ncand, const uint32_t *d_key, uint64_t n, uint32_t *d_label,
+                      uint32_t *d_ncand_out, void *stream);
 
 #ifdef __cplusplus
 }

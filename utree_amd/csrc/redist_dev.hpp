@@ -11,6 +11,7 @@
 #define UTREE_REDIST_DEV_HPP
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "redist.h"
 
 #define RD_PROBES 4096u
@@ -55,9 +56,12 @@ struct FlatSeq {
 //   decode(i, r, tag)   queue entry i -> the read's record index and whatever else the sinks want of it
 //   one(tag, c)         the read's only candidate is the file-order index c (~0: a rank the database does not have)
 //   many(r, tag)        it has several: onto the second queue
-template <uint32_t BLOCK, class DECODE, class ONE, class MANY>
+//   none(tag)           it has none (an empty list: refused, the error word is set); may be left out
+struct RdNoSink {};
+template <uint32_t BLOCK, class DECODE, class ONE, class MANY, class NONE = RdNoSink>
 __device__ __forceinline__ void rd_scan_listed(const utk_redist_tab &t, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
-                                               const uint64_t *__restrict__ tally, uint32_t first, uint32_t qn, DECODE decode, ONE one, MANY many) {
+                                               const uint64_t *__restrict__ tally, uint32_t first, uint32_t qn, DECODE decode, ONE one, MANY many,
+                                               NONE none = NONE()) {
     const uint32_t nl = t.n_labels;
     uint32_t uix[RD_UNROLL], mx[RD_UNROLL], ties[RD_UNROLL], k0[RD_UNROLL], rr[RD_UNROLL], tag[RD_UNROLL], umax = 0;
     const uint64_t *T[RD_UNROLL];
@@ -92,7 +96,11 @@ __device__ __forceinline__ void rd_scan_listed(const utk_redist_tab &t, const ui
 #pragma unroll
     for (int u = 0; u < RD_UNROLL; ++u) {
         if (first + (uint32_t)u * BLOCK >= qn) continue;
-        if (!ties[u] || !mx[u]) { rd_flag(t, UTK_REDIST_F_LABEL); continue; }       // (an empty list: the classify kernels write none; never dropped silently)
+        if (!ties[u] || !mx[u]) {                                                   // (an empty list: the classify kernels write none; never dropped silently)
+            rd_flag(t, UTK_REDIST_F_LABEL);
+            if constexpr (!std::is_same<NONE, RdNoSink>::value) none(tag[u]);
+            continue;
+        }
         if (ties[u] == 1) one(tag[u], c0[u]);
         else many(rr[u], tag[u]);                                                   // several candidates: the table, with full wavefronts
     }

@@ -11,6 +11,10 @@
 // Insert (redist_dev.hpp): whole sets are compared, a key is published only after its labels, no lane waits for another; a table or arena
 // that is used up sets a flag in the error word; the read-back then fails (UTREE_E_DEVICE), no read is dropped silently.
 //
+// Keys (redist_add_k<true>, include/utree_amd.h: utree_redist_classify_batch_keys): the same pass also writes, per read, where its candidates
+// are -- nothing, a label, or the slot rd_insert found or claimed for its set -- one 4-byte store at each place a read's fate is known.  After a
+// solve redist_winner_k evaluates win(set, T_P) once per slot, and redist_assign_k gathers each read's label and number of candidates by key.
+//
 // redist_tally0_k / redist_pass_k: one thread per slot; the set's reads go to every member (T0) or to the richest member under the previous
 // tally, the smallest file-order index on a tie (a pass), one no-return atomic each; the singleton counters enter every tally as a constant;
 // redist_changes_k reduces sum |next - prev| to one word, the only thing the host reads per pass.
@@ -31,23 +35,34 @@ __device__ __forceinline__ void rd_single(const utk_redist_tab &t, RdLds &s, uin
     if (one < n_dense) atomicAdd(&s.dense[one], 1u);
     else rd_add(t.single + one, 1ull);
 }
+// the key of a read whose only candidate is `one` (a label rd_single refuses: none)
+__device__ __forceinline__ uint32_t rd_key_single(const utk_redist_tab &t, uint32_t one) { return one < t.n_labels ? one : UTREE_REDIST_KEY_NONE; }
 
-// RD_UNROLL queued reads per thread (redist_dev.hpp: rd_scan_listed): one candidate is counted, several go on the second queue
+// RD_UNROLL queued reads per thread (redist_dev.hpp: rd_scan_listed): one candidate is counted, several go on the second queue; KEYS: the
+// read's index is the tag, and a read that ends here gets its key
+template <bool KEYS>
 __device__ void rd_listed(const utk_redist_tab &t, RdLds &s, uint32_t n_dense, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
-                          const uint64_t *__restrict__ tally, uint32_t first, uint32_t qn) {
+                          const uint64_t *__restrict__ tally, uint32_t first, uint32_t qn, uint32_t *__restrict__ key) {
     rd_scan_listed<RD_BLOCK>(t, rank2ix, res, tally, first, qn,
-                             [&](uint32_t i, uint32_t &r, uint32_t &) { r = s.q[i]; },
-                             [&](uint32_t, uint32_t one) { rd_single(t, s, n_dense, one); },
-                             [&](uint32_t r, uint32_t) { s.q2[atomicAdd(&s.q2n, 1u)] = r; });
+                             [&](uint32_t i, uint32_t &r, uint32_t &tag) { r = s.q[i]; if (KEYS) tag = r; },
+                             [&](uint32_t tag, uint32_t one) { rd_single(t, s, n_dense, one); if (KEYS) key[tag] = rd_key_single(t, one); },
+                             [&](uint32_t r, uint32_t) { s.q2[atomicAdd(&s.q2n, 1u)] = r; },
+                             [&](uint32_t tag) { if (KEYS) key[tag] = UTREE_REDIST_KEY_NONE; });
 }
 
-// a queued read with several candidates: its set into the table
+// a queued read with several candidates: its set into the table; KEYS: the slot it is in is the read's key
+template <bool KEYS>
 __device__ void rd_multi(const utk_redist_tab &t, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
-                         const uint64_t *__restrict__ tally, uint32_t r) {
+                         const uint64_t *__restrict__ tally, uint32_t r, uint32_t *__restrict__ key) {
     TiedSeq seq;
     const uint32_t ties = rd_scan_tied(t, rank2ix, res, tally, r, seq);
-    if (ties < 2) { rd_flag(t, UTK_REDIST_F_LABEL); return; }     // (rd_listed queued it for having more: never dropped silently)
-    rd_insert(t, seq, ties, 1ull);
+    if (ties < 2) {                                               // (rd_listed queued it for having more: never dropped silently)
+        rd_flag(t, UTK_REDIST_F_LABEL);
+        if (KEYS) key[r] = UTREE_REDIST_KEY_NONE;
+        return;
+    }
+    const uint32_t slot = rd_insert(t, seq, ties, 1ull);
+    if (KEYS) key[r] = slot == RD_NO_SLOT ? UTREE_REDIST_KEY_NONE : 0x80000000u | slot;
 }
 
 // Rounds of RD_TILE reads per workgroup.  First every thread takes its records, four loads in flight: no hit -- nothing; one distinct label --
@@ -56,8 +71,10 @@ __device__ void rd_multi(const utk_redist_tab &t, const uint32_t *__restrict__ r
 // hold another round's reads.  A wavefront executes the union of its lanes' paths, and a probe of the table is a chain of device-scope
 // round trips: with one read in twelve ambiguous nearly every wavefront ran that chain for a few of its lanes in every step when the reads were
 // taken as they came (measured: 2.6 ms per 16 M reads that way, 1.9 ms with the first queue alone, of which 1.7 ms were the probes).
+// KEYS: key[r] is written for every read r of the batch, once, where the read leaves the pass (false: `key` is not looked at).
+template <bool KEYS>
 __global__ void __launch_bounds__(RD_BLOCK) redist_add_k(utk_redist_tab t, const uint32_t *__restrict__ rank2ix, const utree_result *__restrict__ res,
-                                                         const uint64_t *__restrict__ tally, uint32_t n, uint32_t per_block) {
+                                                         const uint64_t *__restrict__ tally, uint32_t n, uint32_t per_block, uint32_t *__restrict__ key) {
     __shared__ RdLds s;
     const uint32_t n_dense = t.n_labels < RD_DENSE ? t.n_labels : RD_DENSE;
     for (uint32_t i = threadIdx.x; i < n_dense; i += RD_BLOCK) s.dense[i] = 0;
@@ -78,19 +95,26 @@ __global__ void __launch_bounds__(RD_BLOCK) redist_add_k(utk_redist_tab t, const
             }
 #pragma unroll
             for (int u = 0; u < RD_UNROLL; ++u) {
-                if (!fnd[u]) continue;
-                if (cut[u] == RD_CUT_PENDING) s.q[atomicAdd(&s.qn, 1u)] = (uint32_t)(r0 + (uint64_t)u * RD_BLOCK);     // (at most RD_TILE per round)
-                else if (cut[u] == RD_RANK_PENDING) rd_single(t, s, n_dense, lab[u] < t.n_labels ? rank2ix[lab[u]] : 0xFFFFFFFFu);
-                else rd_single(t, s, n_dense, lab[u]);     // finished by classify_long_k: one label, already a file-order index
+                const uint64_t r = r0 + (uint64_t)u * RD_BLOCK;
+                if (!fnd[u]) { if (KEYS && r < tend) key[r] = UTREE_REDIST_KEY_NONE; continue; }
+                if (cut[u] == RD_CUT_PENDING) s.q[atomicAdd(&s.qn, 1u)] = (uint32_t)r;     // (at most RD_TILE per round)
+                else if (cut[u] == RD_RANK_PENDING) {
+                    const uint32_t one = lab[u] < t.n_labels ? rank2ix[lab[u]] : 0xFFFFFFFFu;
+                    rd_single(t, s, n_dense, one);
+                    if (KEYS) key[r] = rd_key_single(t, one);
+                } else {
+                    rd_single(t, s, n_dense, lab[u]);     // finished by classify_long_k: one label, already a file-order index
+                    if (KEYS) key[r] = rd_key_single(t, lab[u]);
+                }
             }
         }
         __syncthreads();
         const uint32_t qn = s.qn;
-        for (uint32_t i = threadIdx.x; i < qn; i += RD_UNROLL * RD_BLOCK) rd_listed(t, s, n_dense, rank2ix, res, tally, i, qn);
+        for (uint32_t i = threadIdx.x; i < qn; i += RD_UNROLL * RD_BLOCK) rd_listed<KEYS>(t, s, n_dense, rank2ix, res, tally, i, qn, key);
         __syncthreads();
         const uint32_t q2n = s.q2n;
         if (q2n + RD_TILE > RD_Q2 || tend == end) {                 // (the same decision in every thread)
-            for (uint32_t i = threadIdx.x; i < q2n; i += RD_BLOCK) rd_multi(t, rank2ix, res, tally, s.q2[i]);
+            for (uint32_t i = threadIdx.x; i < q2n; i += RD_BLOCK) rd_multi<KEYS>(t, rank2ix, res, tally, s.q2[i], key);
             __syncthreads();
             if (threadIdx.x == 0) s.q2n = 0;
         }
@@ -148,6 +172,43 @@ __global__ void __launch_bounds__(256) redist_pass_k(utk_redist_tab t, const uns
     }
 }
 
+// win(set, tally) and the set's size, per slot: what redist_pass_k<true> evaluates, kept instead of counted (free slots: ~0 and 0)
+__global__ void __launch_bounds__(256) redist_winner_k(utk_redist_tab t, const unsigned long long *__restrict__ tally, uint32_t *__restrict__ win,
+                                                       uint32_t *__restrict__ ncand) {
+    for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= t.mask; s += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long k = t.slots[2 * s];
+        if (k == RD_FREE) { win[s] = 0xFFFFFFFFu; ncand[s] = 0; continue; }
+        const uint32_t *a = t.arena + (k >> 32);
+        const uint32_t n = (uint32_t)k;
+        uint32_t best = a[0];
+        unsigned long long tb = tally[best];
+        for (uint32_t i = 1; i < n; ++i) {
+            const uint32_t l = a[i];
+            const unsigned long long tl = tally[l];
+            if (tl > tb || (tl == tb && l < best)) { best = l; tb = tl; }
+        }
+        win[s] = best; ncand[s] = n;
+    }
+}
+
+// one thread per read, a gather by key: every comparison stands in front of the load it guards, a bad key reads nothing
+__global__ void __launch_bounds__(256) redist_assign_k(utk_redist_tab t, const uint32_t *__restrict__ win, const uint32_t *__restrict__ ncand,
+                                                       const uint32_t *__restrict__ key, uint64_t n, uint32_t *__restrict__ label,
+                                                       uint32_t *__restrict__ ncand_out) {
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t k = key[r];
+        uint32_t l = 0xFFFFFFFFu, c = 0xFFFFFFFFu;
+        if (k == UTREE_REDIST_KEY_NONE) c = 0;
+        else if (k < 0x80000000u) { if (k < t.n_labels) { l = k; c = 1; } }
+        else {
+            const uint32_t s = k & 0x7FFFFFFFu;
+            if (s <= t.mask && t.slots[2 * (size_t)s] != RD_FREE) { l = win[s]; c = ncand[s]; }
+        }
+        label[r] = l;
+        if (ncand_out) ncand_out[r] = c;
+    }
+}
+
 __global__ void __launch_bounds__(256) redist_changes_k(const unsigned long long *__restrict__ prev, const unsigned long long *__restrict__ next, uint32_t n,
                                                         unsigned long long *out) {
     unsigned long long c = 0;
@@ -163,14 +224,18 @@ static inline uint32_t grid_for(uint64_t n, uint32_t block, uint32_t most) {
 }
 
 extern "C" int utk_redist_add(const utk_redist_tab *t, const utk_image *im, const utree_result *d_res, const utk_workspace *ws, uint32_t n_reads,
-                              int n_cu, void *stream) {
+                              int n_cu, uint32_t *d_key, void *stream) {
     if (!n_reads) return 0;
     // one workgroup per CU at most (the LDS counters take 112 KiB of its 160), each over a contiguous run of records
     uint32_t blocks = (uint32_t)(n_cu > 0 ? n_cu : 256);
     const uint32_t min_per = 4u * RD_BLOCK;
     if ((n_reads + min_per - 1) / min_per < blocks) blocks = (n_reads + min_per - 1) / min_per;
     const uint32_t per = (uint32_t)(((uint64_t)n_reads + blocks - 1) / blocks);
-    hipLaunchKernelGGL(redist_add_k, dim3(blocks), dim3(RD_BLOCK), 0, (hipStream_t)stream, *t, im->rank2ix, d_res, ws->tally, n_reads, per);
+    if (d_key)
+        hipLaunchKernelGGL(redist_add_k<true>, dim3(blocks), dim3(RD_BLOCK), 0, (hipStream_t)stream, *t, im->rank2ix, d_res, ws->tally, n_reads, per, d_key);
+    else
+        hipLaunchKernelGGL(redist_add_k<false>, dim3(blocks), dim3(RD_BLOCK), 0, (hipStream_t)stream, *t, im->rank2ix, d_res, ws->tally, n_reads, per,
+                           (uint32_t *)NULL);
     return (int)hipGetLastError();
 }
 
@@ -205,5 +270,17 @@ extern "C" int utk_redist_pass(const utk_redist_tab *t, const unsigned long long
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(redist_changes_k, dim3(grid_for(t->n_labels, 256, 1024)), dim3(256), 0, (hipStream_t)stream, prev, next, t->n_labels, t->misc + 3);
+    return (int)hipGetLastError();
+}
+
+extern "C" int utk_redist_winner(const utk_redist_tab *t, const unsigned long long *tally, uint32_t *d_win, uint32_t *d_ncand, void *stream) {
+    hipLaunchKernelGGL(redist_winner_k, dim3(grid_for((uint64_t)t->mask + 1, 256, 4096)), dim3(256), 0, (hipStream_t)stream, *t, tally, d_win, d_ncand);
+    return (int)hipGetLastError();
+}
+
+extern "C" int utk_redist_assign(const utk_redist_tab *t, const uint32_t *d_win, const uint32_t *d_ncand, const uint32_t *d_key, uint64_t n,
+                                 uint32_t *d_label, uint32_t *d_ncand_out, void *stream) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(redist_assign_k, dim3(grid_for(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, *t, d_win, d_ncand, d_key, n, d_label, d_ncand_out);
     return (int)hipGetLastError();
 }

@@ -15,6 +15,11 @@
  *
  * A hit map (a request's hitmap_path) rides the same slots: the gpu stage launches utree_hitmap_batch behind a shard's classify call on the
  * same device buffers and brings the runs back, the formatter makes the map's lines next to the output's, and the writer commits both.
+ *
+ * Each read's redistributed label (a request's redistribute_reads_path) is known only after the last read: the gpu stage classifies through the
+ * keys entry point and brings a shard's keys back next to its results, the formatter makes one spool record per query that prints a line --
+ * key, device handle, name --, the writer appends them to <path>.spool together with the chunk's output lines, and reports.c assigns the spooled
+ * keys after the solve.  Host memory does not grow with the number of reads.
  */
 #define _FILE_OFFSET_BITS 64
 #define _GNU_SOURCE
@@ -23,6 +28,7 @@
 #include <errno.h>
 #include <fcntl.h>
 #include <pthread.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -80,10 +86,17 @@ typedef struct {
     size_t hm_cap[FMT_MAX_THREADS], hm_len[FMT_MAX_THREADS];
     /* a report that reads the names only: the names' offsets relative to their shard's uploaded span, and their lengths behind them */
     uint32_t *h_names;                         /* pinned, 2 * MAX_READS_PER_BATCH                           */
+    /* redistributed reads only: every read's key (of the table of the device handle that classified it: read r went to handle r / per), and
+     * the spool records of the queries that print a line, pieces as fmt_buf's */
+    uint32_t *h_key;                           /* pinned, MAX_READS_PER_BATCH                               */
+    size_t per;
+    char *sp_buf[FMT_MAX_THREADS];
+    size_t sp_cap[FMT_MAX_THREADS], sp_len[FMT_MAX_THREADS];
 } slot_t;
 
-static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev, int hitmap, int names) {
+static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev, int hitmap, int names, int keys) {
     if (s->h_buf) return UTREE_OK;
+    if (keys && hipHostMalloc((void **)&s->h_key, MAX_READS_PER_BATCH * 4, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
     if (names && hipHostMalloc((void **)&s->h_names, 2 * MAX_READS_PER_BATCH * 4, hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
     if (hitmap) {
         if (hipHostMalloc((void **)&s->h_hm_meta, (size_t)n_dev * sizeof(utree_hitmap_meta), hipHostMallocDefault) != hipSuccess) return UTREE_E_NOMEM;
@@ -113,12 +126,12 @@ static int slot_alloc(slot_t *s, size_t chunk, int paired, int n_dev, int hitmap
 
 static void slot_free(slot_t *s) {
     void *pinned[] = {s->h_buf, s->h_res, s->rel_off, s->seq_len, s->m2.h_buf, s->m2.rel_off, s->m2.seq_len, s->h_meta, s->h_hm_meta, s->h_run_off,
-                      s->h_runs, s->h_names};
+                      s->h_runs, s->h_names, s->h_key};
     for (size_t i = 0; i < sizeof pinned / sizeof pinned[0]; ++i) if (pinned[i]) hipHostFree(pinned[i]);
     free(s->seq_off); free(s->name_off); free(s->name_len);
     free(s->m2.seq_off); free(s->m2.name_off); free(s->m2.name_len);
     free(s->hm_first); free(s->hm_count); free(s->hm_base);
-    for (int t = 0; t < FMT_MAX_THREADS; ++t) { free(s->hm_buf[t]); free(s->fmt_buf[t]); }
+    for (int t = 0; t < FMT_MAX_THREADS; ++t) { free(s->hm_buf[t]); free(s->fmt_buf[t]); free(s->sp_buf[t]); }
 }
 
 typedef struct {
@@ -131,6 +144,7 @@ typedef struct {
     /* hit map: the shard's run offsets, runs (the worst case: one per window) and meta, and the call's workspace */
     uint64_t *d_run_off; utree_hit_run *d_runs; uint64_t runs_cap; utree_hitmap_meta *d_hm_meta; void *d_hm_ws; size_t hm_ws_bytes;
     uint32_t *d_name_off, *d_name_len;          /* a report that reads the names only: relative to d_buf      */
+    uint32_t *d_key;                            /* redistributed reads only: the shard's keys                 */
 } gpu_ctx;
 
 /* one input file: plain (a team of pread) or, with an opt-in format, through zlib (plain and gzip alike) */
@@ -146,6 +160,8 @@ typedef struct {
     int names;                                  /* a report reads the names (utree_reports_wants_names): they go up with the shard */
     int hm, fh;                                 /* a hit map is made; its file (-1 once writing it has failed: the search goes on) */
     char *hm_msg;                               /* why the map could not be written ("" = it could): the writer's to set            */
+    int keys, fs;                               /* every read's key is brought back and spooled; the spool (-1 once writing it has failed: the search goes on) */
+    char *sp_msg;                               /* why the spool could not be written ("" = it could): the writer's to set          */
     off_t out_pos;
     int paired;                                 /* PAIRS_*, from the request's mates_path / interleaved     */
     size_t chunk;                               /* bytes per slot and input: CHUNK_BYTES; a paired search honours UTREE_CHUNK_BYTES */
@@ -247,7 +263,7 @@ static void *reader_main(void *arg) {
         slot_t *s = &P->slot[i % NSLOTS];
         if (!wait_state(P, s, S_EMPTY)) return NULL;
         if (i < NSLOTS) {                       /* pinned memory is slow to allocate: do it while earlier chunks are in flight */
-            int arc = slot_alloc(s, P->chunk, PAIRS_NONE, P->n_dev, P->hm, P->names);
+            int arc = slot_alloc(s, P->chunk, PAIRS_NONE, P->n_dev, P->hm, P->names, P->keys);
             if (arc) { set_error(P, arc); return NULL; }
         }
         if (carry) memmove(s->h_buf, carry_src, carry);
@@ -359,7 +375,7 @@ static void *reader_pairs_main(void *arg) {
         mate_t *m = &s->m2;
         if (!wait_state(P, s, S_EMPTY)) return NULL;
         if (i < NSLOTS) {
-            int arc = slot_alloc(s, P->chunk, P->paired, P->n_dev, P->hm, P->names);
+            int arc = slot_alloc(s, P->chunk, P->paired, P->n_dev, P->hm, P->names, P->keys);
             if (arc) { set_error(P, arc); return NULL; }
         }
         uint8_t *buf[2] = {s->h_buf, m->h_buf};
@@ -546,6 +562,7 @@ static void *gpu_main(void *arg) {
         double t0 = now_s();
         size_t nr = s->nr, n_dev = (size_t)P->n_dev;
         size_t per = (nr + n_dev - 1) / n_dev;
+        s->per = per ? per : 1;
         for (size_t g = 0; g < n_dev && nr && P->paired; ++g) { memset(&s->h_meta[g], 0, sizeof s->h_meta[g]); P->G[g].want_total = 0; }
         for (size_t g = 0; g < n_dev && P->hm; ++g) { s->hm_first[g] = 0; s->hm_count[g] = 0; s->hm_base[g] = 0; }
         for (size_t g = 0; g < n_dev && nr; ++g) {
@@ -559,7 +576,8 @@ static void *gpu_main(void *arg) {
             if (!e && P->names) e = names_upload(P, s, g, first, count, lo, (size_t)v.text_bytes);   /* (in front of the classify call: a report may read them there) */
             if (!e) e = rank ? utree_rank_batch(c->dev, v.d_bases, v.d_off, v.d_len, v.n_reads, v.total_bases, v.max_len, v.do_rc, rank, c->d_out, c->d_ws,
                                                 c->ws_bytes, c->stream)
-                             : utree_reports_classify(P->rep, (int)g, c->dev, &v, c->d_out, c->d_ws, c->ws_bytes);
+                             : utree_reports_classify(P->rep, (int)g, c->dev, &v, c->d_out, c->d_ws, c->ws_bytes, P->keys ? c->d_key : NULL);
+            if (!e && P->keys && hipMemcpyAsync(s->h_key + first, c->d_key, count * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) e = UTREE_E_HIP;
             if (!e) e = utree_reports_add(P->rep, (int)g, &v, c->d_out, rank != NULL);
             if (!e && P->hm) e = hitmap_launch(P, s, g, &v, first);
             if (!e && hipMemcpyAsync(s->h_res + first, c->d_out, count * sizeof(utree_result), hipMemcpyDeviceToHost, c->stream) != hipSuccess) e = UTREE_E_HIP;
@@ -613,6 +631,20 @@ static void *format_main(void *arg) {
                                  : utree_format_records(P->ctr, s->h_buf, s->name_off + a, s->name_len + a, s->h_res + a, b - a,
                                                         s->fmt_buf[t], s->fmt_cap[t], &good);
             if (L == (size_t)-1) { fail |= 1; s->fmt_len[t] = 0; } else { s->fmt_len[t] = L; good_total += good; }
+            if (P->keys) {
+                /* the spool records of [a, b): one per query that prints a line, in the lines' order */
+                size_t sneed = 0, sl = 0;
+                for (size_t r = a; r < b; ++r) if (s->h_res[r].found) sneed += sizeof(utree_spool_rec) + s->name_len[r];
+                if (sneed > s->sp_cap[t]) { free(s->sp_buf[t]); s->sp_buf[t] = (char *)malloc(sneed + sneed / 4); s->sp_cap[t] = s->sp_buf[t] ? sneed + sneed / 4 : 0; }
+                if (sneed && !s->sp_buf[t]) fail |= 1;
+                else for (size_t r = a; r < b; ++r) {
+                    if (!s->h_res[r].found) continue;
+                    const utree_spool_rec rec = {s->h_key[r], (uint32_t)(r / s->per), s->name_len[r]};
+                    memcpy(s->sp_buf[t] + sl, &rec, sizeof rec); sl += sizeof rec;
+                    memcpy(s->sp_buf[t] + sl, s->h_buf + s->name_off[r], s->name_len[r]); sl += s->name_len[r];
+                }
+                s->sp_len[t] = sl;
+            }
             if (!P->hm) continue;
             /* the map's lines of [a, b): a line per query; the slice is cut where one device's shard ends and the next one's begins */
             size_t hneed = 64, hl = 0;
@@ -672,6 +704,18 @@ static void *writer_main(void *arg) {
                 done += (size_t)w;
             }
         }
+        for (int t = 0; t < s->fmt_T && P->keys && P->fs >= 0; ++t) {              /* ... and its spool records */
+            size_t done = 0;
+            while (done < s->sp_len[t]) {
+                ssize_t w = write(P->fs, s->sp_buf[t] + done, s->sp_len[t] - done);
+                if (w <= 0) {                                                     /* the search goes on without that report */
+                    snprintf(P->sp_msg, 512, "cannot write the spool %.300s.spool (%s)", P->req->redistribute_reads_path, strerror(errno));
+                    close(P->fs); P->fs = -1;
+                    break;
+                }
+                done += (size_t)w;
+            }
+        }
         P->t_write += now_s() - t1;
         P->st.good_finds += s->good;
         P->st.n_reads += nr;
@@ -714,6 +758,7 @@ static void free_ctx(gpu_ctx *g) {
     if (g->d_hm_ws) hipFree(g->d_hm_ws);
     if (g->d_name_off) hipFree(g->d_name_off);
     if (g->d_name_len) hipFree(g->d_name_len);
+    if (g->d_key) hipFree(g->d_key);
     if (g->stream) hipStreamDestroy(g->stream);
 }
 
@@ -752,6 +797,7 @@ static int ctx_alloc(pipe_t *P, gpu_ctx *c, utree_dev *dev) {
         HIPE(hipMalloc((void **)&c->d_name_off, MAX_READS_PER_BATCH * 4));
         HIPE(hipMalloc((void **)&c->d_name_len, MAX_READS_PER_BATCH * 4));
     }
+    if (P->keys) HIPE(hipMalloc((void **)&c->d_key, MAX_READS_PER_BATCH * 4));
     c->ws_bytes = req->rank ? utree_rank_workspace_bytes(dev, (uint32_t)MAX_READS_PER_BATCH, CHUNK_BYTES, LINELEN_MAX, req->do_rc, req->rank)
                             : utree_classify_workspace_bytes(dev, (uint32_t)MAX_READS_PER_BATCH, paired ? c->joined_cap : CHUNK_BYTES, LINELEN_MAX, req->do_rc);
     if (!c->ws_bytes) return UTREE_E_ARG;
@@ -772,9 +818,14 @@ static int write_labels(const utree_ctr *ctr, const char *hitmap_path, char *msg
     return bad;
 }
 
-/* One search that utree_search_run has checked; rep: the reports it feeds (NULL: none); hm_msg: why the hit map was not written, when it was not */
+/* the spool of a search that writes each read's redistributed label: <redistribute_reads_path>.spool, created when the search starts and removed
+ * on every way out (search_request); fd -1 and msg: it could not be created, or written */
+typedef struct { int fd; char path[4096], msg[512]; } spool_t;
+
+/* One search that utree_search_run has checked; rep: the reports it feeds (NULL: none); hm_msg: why the hit map was not written, when it was not;
+ * sp: NULL, or the spool the queries' keys go to (closed here) */
 static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const utree_search_request *req, utree_reports *rep, char *hm_msg,
-                       utree_search_stats *stats) {
+                       spool_t *sp, utree_search_stats *stats) {
     const int paired = req->mates_path ? PAIRS_TWO_FILES : req->interleaved ? PAIRS_INTERLEAVED : PAIRS_NONE;   /* (GG search only) */
     const char *hitmap_path = req->hitmap_path, *out_path = req->out_path;
     int rc = UTREE_OK;
@@ -784,7 +835,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     /* The GG search on the reference's input format takes the device text pipeline (search_dev.c); it hands back input it
      * does not take -- malformed records, NUL bytes, lines fgets would split -- and the host framing below then reproduces
      * the reference on it case by case.  UTREE_HOST_TEXT=1 forces the host pipeline (tests, A/B). */
-    if (!req->rank && !paired && !hitmap_path && req->input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
+    if (!req->rank && !paired && !hitmap_path && !req->redistribute_reads_path && req->input_format == UTREE_INPUT_REFERENCE && !getenv("UTREE_HOST_TEXT")) {
         rc = utree_search_file_device(ctr, devs, n_dev, req->reads_path, out_path, req->do_rc, req->host_threads, rep, stats, &dev_printed, &resume);
         if (rc != UTREE_RETRY_HOST) return rc;
         rc = UTREE_OK;
@@ -794,10 +845,12 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
     }
     double t_start = now_s();
     pipe_t *P = (pipe_t *)calloc(1, sizeof *P);
-    if (!P) { if (resume.fo >= 0) close(resume.fo); return UTREE_E_NOMEM; }
+    if (!P) { if (resume.fo >= 0) close(resume.fo); if (sp && sp->fd >= 0) { close(sp->fd); sp->fd = -1; } return UTREE_E_NOMEM; }
     P->ctr = ctr; P->req = req; P->rep = rep; P->n_dev = n_dev; P->input_format = req->input_format;
     P->progress_printed = dev_printed;
-    P->paired = paired; P->chunk = paired || hitmap_path ? utree_chunk_bytes(CHUNK_BYTES) : CHUNK_BYTES;
+    P->paired = paired; P->chunk = paired || hitmap_path || req->redistribute_reads_path ? utree_chunk_bytes(CHUNK_BYTES) : CHUNK_BYTES;
+    P->fs = sp ? sp->fd : -1; P->keys = P->fs >= 0 && utree_reports_wants_keys(rep); P->sp_msg = sp ? sp->msg : NULL;
+    if (sp) sp->fd = -1;                                                          /* (this search's to close from here on) */
     P->names = utree_reports_wants_names(rep);
     P->hm = hitmap_path != NULL; P->fh = -1; P->hm_msg = hm_msg;
     P->in[1].fd = -1;
@@ -822,6 +875,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
         if (P->in[0].fd >= 0) close(P->in[0].fd);
         if (P->in[1].fd >= 0) close(P->in[1].fd);
         if (P->fo >= 0) close(P->fo);
+        if (P->fs >= 0) close(P->fs);
         free(P);
         return UTREE_E_IO;
     }
@@ -839,6 +893,7 @@ static int search_file(const utree_ctr *ctr, utree_dev **devs, int n_dev, const 
             if (P->in[0].gz) gzclose(P->in[0].gz);
             close(P->in[0].fd); if (P->in[1].fd >= 0) close(P->in[1].fd);
             if (P->fh >= 0) close(P->fh);
+            if (P->fs >= 0) close(P->fs);
             close(P->fo); free(P);
             return UTREE_E_IO;
         }
@@ -881,6 +936,7 @@ done:
     }
     if (P->fo >= 0) close(P->fo);
     if (P->fh >= 0 && close(P->fh) && !hm_msg[0]) snprintf(hm_msg, 512, "hit map %s: cannot write the file (%s)", hitmap_path, strerror(errno));
+    if (P->fs >= 0 && close(P->fs) && !sp->msg[0]) snprintf(sp->msg, sizeof sp->msg, "cannot write the spool %.300s (%s)", sp->path, strerror(errno));
     if (P->G) { for (int g = 0; g < n_dev; ++g) free_ctx(&P->G[g]); free(P->G); }
     for (int i = 0; i < NSLOTS; ++i) slot_free(&P->slot[i]);
     P->st.seconds_total = now_s() - t_start;
@@ -917,12 +973,24 @@ static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, con
     utree_reports *rep = NULL;
     utree_search_stats st;
     char hm_msg[512] = "";                                         /* why the hit map was not written, when it was not */
+    spool_t *sp = NULL;
     memset(&st, 0, sizeof st);
     int rc = utree_reports_create(ctr, devs, n_dev, req, &rep);
-    if (!rc && !rep && !req->hitmap_path) return search_file(ctr, devs, n_dev, req, NULL, hm_msg, stats);   /* no report asked for */
-    if (!rc) rc = search_file(ctr, devs, n_dev, req, rep, hm_msg, &st);
-    if (!rc && rep) rc = utree_reports_write(rep, ctr, st.n_reads);
+    if (!rc && !rep && !req->hitmap_path) return search_file(ctr, devs, n_dev, req, NULL, hm_msg, NULL, stats);   /* no report asked for */
+    if (!rc && utree_reports_wants_keys(rep)) {
+        /* a spool that cannot be created does not stop the search: it runs without the report and says so at its end */
+        if (!(sp = (spool_t *)calloc(1, sizeof *sp))) rc = UTREE_E_NOMEM;
+        else if (snprintf(sp->path, sizeof sp->path, "%s.spool", req->redistribute_reads_path) >= (int)sizeof sp->path) {
+            sp->fd = -1; sp->path[0] = 0; snprintf(sp->msg, sizeof sp->msg, "the path is too long for its spool");
+        } else if ((sp->fd = open(sp->path, O_WRONLY | O_CREAT | O_TRUNC, 0644)) < 0)
+            snprintf(sp->msg, sizeof sp->msg, "cannot create the spool %.300s (%s)", sp->path, strerror(errno));
+    }
+    if (!rc) rc = search_file(ctr, devs, n_dev, req, rep, hm_msg, sp, &st);
+    if (sp && sp->fd >= 0) { close(sp->fd); sp->fd = -1; }         /* (a search that ended before it took the spool over) */
+    if (!rc && rep) rc = utree_reports_write(rep, ctr, st.n_reads, sp && !sp->msg[0] ? sp->path : NULL, sp ? sp->msg : NULL);
     if (!rc && hm_msg[0]) { utree_set_error_text(hm_msg); rc = UTREE_E_HITMAP; }
+    if (sp && sp->path[0]) unlink(sp->path);                       /* on every way out */
+    free(sp);
     utree_reports_free(rep);
     if (stats) *stats = st;
     return rc;
@@ -932,15 +1000,24 @@ static int search_request(const utree_ctr *ctr, utree_dev **devs, int n_dev, con
  * speed, doRC) (itree.c:1376 without DO_GG): the same pipeline, the batches to ONE device in file order because each read's vote depends on the
  * reads before it (rank.c) -- another vote: no candidate sets; a hit-dependent subset of windows: no map, and no coverage of the GG search's */
 int utree_search_run(const utree_ctr *ctr, utree_dev **devs, int n_dev, const utree_search_request *req, utree_search_stats *stats) {
+    /* a caller built before redistribute_reads_path gives the size of the layout without it: a request without that report */
+    const size_t al = _Alignof(utree_search_request), old_size = (offsetof(utree_search_request, redistribute_reads_path) + al - 1) / al * al;
+    utree_search_request grown;
+    if (req && req->size == old_size && old_size < sizeof grown) {
+        memset(&grown, 0, sizeof grown);
+        memcpy(&grown, req, old_size);
+        grown.size = sizeof grown;
+        req = &grown;
+    }
     if (!req || req->size != sizeof *req) return UTREE_E_ARG;
     if (!ctr || !devs || n_dev < 1 || !req->reads_path || !req->out_path) return UTREE_E_ARG;
     if (req->input_format < 0 || req->input_format > UTREE_INPUT_AUTO || (req->mates_path && req->interleaved)) return UTREE_E_ARG;
     const int d = req->sample_delim;
     if ((req->samples_path || req->sample_redistribute_path) && (d < 0 || d > 255 || d == '\t' || d == ' ' || d == '\r' || d == '\n')) return UTREE_E_ARG;
-    if ((req->redistribute_path || req->sample_redistribute_path) && req->max_passes > 1000) return UTREE_E_ARG;
+    if ((req->redistribute_path || req->sample_redistribute_path || req->redistribute_reads_path) && req->max_passes > 1000) return UTREE_E_ARG;
     if (req->rank) {
         if (n_dev != 1 || req->mates_path || req->interleaved || req->coverage_path || req->redistribute_path || req->hitmap_path ||
-            req->sample_redistribute_path) return UTREE_E_ARG;
+            req->sample_redistribute_path || req->redistribute_reads_path) return UTREE_E_ARG;
         const int rc = utree_rank_reset(devs[0]);
         if (rc) return rc;
     }

@@ -351,7 +351,7 @@ static void *lane_main(void *arg) {
         /* ---- classify (kernels.hip), then the output text ---- */
         const utree_batch_view v = {b->d_in, b->d_seq_off, b->d_seq_len, nr, m1.total_bases, m1.max_len, P->do_rc, b->d_in, n, b->d_name_off, b->d_name_len, b->stream};
         if (nr) {
-            int e = utree_reports_classify(P->rep, L->g, L->dev, &v, b->d_res, b->d_ws, b->ws_bytes);
+            int e = utree_reports_classify(P->rep, L->g, L->dev, &v, b->d_res, b->d_ws, b->ws_bytes, NULL);
             if (e) { dfail(P, e); return NULL; }
             LK(utk_text_format(&L->dev->kimg, ((struct utree_search_ctx *)L->dev->search_ctx)->d_ix2rank, b->d_in, b->d_res, b->d_name_off,
                                b->d_name_len, nr, b->d_line_len, b->d_line_off, b->d_scan, b->scan_bytes, b->d_out, DOUT_BYTES, b->d_meta, 0,

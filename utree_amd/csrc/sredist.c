@@ -89,7 +89,7 @@ int utree_sredist_classify_batch(utree_sredist *h, utree_dev *dev, const uint8_t
     if (!h || !dev || h->device != dev->device || h->n_labels != dev->hdr.n_labels) return UTREE_E_ARG;
     if (n_reads && (!d_name_off || !d_name_len || (!d_text && text_bytes))) return UTREE_E_ARG;
     const utree_batch_view v = {d_bases, d_off, d_len, n_reads, total_bases, max_len, do_rc, d_text, text_bytes, d_name_off, d_name_len, stream};
-    return utree_classify_view(dev, &v, d_out, d_workspace, workspace_bytes, NULL, h);
+    return utree_classify_view(dev, &v, d_out, d_workspace, workspace_bytes, NULL, h, NULL);
 }
 
 /* ---- the device's state as one flat table on the host ------------------------------------------------------------------------------------- */

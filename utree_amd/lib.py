@@ -19,6 +19,7 @@ _LIB = None
 
 OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE, E_PAIRS, E_HITMAP = range(16)
 HIT_MISS, HIT_INVALID = 0xFFFFFFFF, 0xFFFFFFFE
+REDIST_KEY_NONE = 0xFFFFFFFF
 BUILD_E_MAP_EMPTY, BUILD_E_MAP, BUILD_E_FASTA, BUILD_E_NO_KMERS, BUILD_E_NAME = range(1, 6)
 FINE_AUTO = -1
 FANOUT_NONE, FANOUT_BROADCAST, FANOUT_UPLOAD = range(3)
@@ -75,7 +76,7 @@ class SearchRequest(C.Structure):
                 ("reads_path", C.c_char_p), ("mates_path", C.c_char_p), ("interleaved", C.c_int), ("out_path", C.c_char_p),
                 ("rank", C.POINTER(RankParams)), ("profile_path", C.c_char_p), ("coverage_path", C.c_char_p),
                 ("redistribute_path", C.c_char_p), ("max_passes", C.c_uint32), ("hitmap_path", C.c_char_p), ("samples_path", C.c_char_p),
-                ("sample_redistribute_path", C.c_char_p), ("sample_delim", C.c_int)]
+                ("sample_redistribute_path", C.c_char_p), ("sample_delim", C.c_int), ("redistribute_reads_path", C.c_char_p)]
 
     def __init__(self, **kw):
         super().__init__(size=C.sizeof(SearchRequest), **kw)
@@ -236,6 +237,11 @@ SYMBOLS = {
     "utree_redist_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
     "utree_redist_solve": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint64)]),
+    "utree_redist_classify_batch_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                                   C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "utree_redist_assign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "utree_redist_reads_format": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                               C.c_size_t]),
     "utree_redist_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.c_char_p]),
     "utree_search_file_redistribute": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
                                                  C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(SearchStats)]),

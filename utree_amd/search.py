@@ -667,9 +667,10 @@ class Redistribution:
         self._h = h
 
     def classify(self, bases, off, length, rc: bool = False, total_bases: Optional[int] = None, max_len: Optional[int] = None, out=None,
-                 workspace=None):
+                 workspace=None, keys=None):
         """As DeviceTree.classify (the same results, bit for bit); the candidate sets of the batch are added on the way.  Asynchronous on
-        torch's current stream; any number of streams may add at once (give each its own workspace)."""
+        torch's current stream; any number of streams may add at once (give each its own workspace).  keys: an int32 / uint32 tensor of one
+        element per read on the reads' device -- every read's key goes there (utree_redist_classify_batch_keys), for assign()."""
         import torch
         n = off.numel()
         dev = bases.device
@@ -685,10 +686,33 @@ class Redistribution:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
             workspace = self._ws
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if keys is not None:
+            if keys.numel() != n or keys.element_size() != 4 or not keys.is_contiguous() or keys.device != dev:
+                raise ValueError("Redistribution.classify: keys must be a contiguous 4-byte tensor of one element per read on the reads' device")
+            _lib.check(_lib.load().utree_redist_classify_batch_keys(self._h, self.tree._h, bases.data_ptr(), off.data_ptr(), length.data_ptr(), n,
+                                                                    total_bases, max_len, int(rc), out.data_ptr(), workspace.data_ptr(),
+                                                                    workspace.numel(), keys.data_ptr(), stream), "utree_redist_classify_batch_keys")
+            return out
         _lib.check(_lib.load().utree_redist_classify_batch(self._h, self.tree._h, bases.data_ptr(), off.data_ptr(), length.data_ptr(), n,
                                                            total_bases, max_len, int(rc), out.data_ptr(), workspace.data_ptr(),
                                                            workspace.numel(), stream), "utree_redist_classify_batch")
         return out
+
+    def assign(self, keys, solved: Optional["Redistribution"] = None):
+        """(label, ncand): int32 tensors (bit patterns of uint32) of one element per key -- the label the last solve() of `solved` (this handle,
+        or the one this handle was merged into) assigns each read to, and how many candidates the read had; 0xFFFFFFFF and 0 for a read
+        without a hit (utree_redist_assign).  keys: what classify(keys=) of THIS handle wrote.  Asynchronous on torch's current stream once
+        the slots' winners stand (once per solve)."""
+        import torch
+        if keys.element_size() != 4 or not keys.is_contiguous():
+            raise ValueError("Redistribution.assign: keys must be a contiguous 4-byte tensor")
+        n = keys.numel()
+        label = torch.empty(n, dtype=torch.int32, device=keys.device)
+        ncand = torch.empty(n, dtype=torch.int32, device=keys.device)
+        stream = torch.cuda.current_stream(keys.device).cuda_stream
+        _lib.check(_lib.load().utree_redist_assign(self._h, (solved or self)._h, keys.data_ptr() if n else None, n, label.data_ptr() if n else None,
+                                                   ncand.data_ptr() if n else None, stream), "utree_redist_assign")
+        return label, ncand
 
     def sets(self):
         """(sets, n_reads, n_classified): sets = {sorted tuple of file-order label indices: reads}, single-label sets included.  Raises
@@ -919,7 +943,7 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
               input_format: int = _lib.INPUT_REFERENCE, profile: Optional[str] = None, coverage: Optional[str] = None,
               mates: Optional[str] = None, interleaved: bool = False, redistribute: Optional[str] = None, redist_passes: int = 100,
               hitmap: Optional[str] = None, samples: Optional[str] = None, sample_delim: bytes = b"_",
-              sample_redistribute: Optional[str] = None):
+              sample_redistribute: Optional[str] = None, redistribute_reads: Optional[str] = None):
     """XT_doSearch32(utree, in, out, 8, speed, doRC) (itree.c:833) as one utree_search_request through utree_search_run (the utree_search_file*
     calls named below are its fixed-argument forms): returns (code, stats); stats.fasta_error says which of
     the reference's exit(2) conditions a malformed read hit.  input_format != INPUT_REFERENCE opts into FASTQ / multi-line
@@ -935,13 +959,15 @@ def search_gg(db: CtrDB, trees: Sequence[DeviceTree], fasta: str, out: str, rc: 
     samples: the reads are a combined file named <sample><sample_delim><n>; also write the taxon x sample table there
     (utree_search_file_samples); a table that cannot be written returns E_PROFILE.
     sample_redistribute: also write the taxon x sample table with every sample's ambiguous reads redistributed within that sample there
-    (utree_search_file_sample_redistribute; ids cut at sample_delim, at most redist_passes passes per sample); E_PROFILE likewise."""
+    (utree_search_file_sample_redistribute; ids cut at sample_delim, at most redist_passes passes per sample); E_PROFILE likewise.
+    redistribute_reads: also write, for every query with a line in `out` and in that order, "name\\tlabel text\\tn_candidates" there -- the label
+    the redistribution assigns the read to (with or without redistribute=: one solve serves both); host framing pipeline; E_PROFILE likewise."""
     if mates is not None and interleaved:
         raise ValueError("search_gg: give mates= or interleaved=True, not both")
     arr = (C.c_void_p * len(trees))(*[t._h for t in trees])
     return _search_run(db, arr, len(trees), "search_gg", fasta, out, rc, threads, input_format, sample_delim, mates_path=mates, interleaved=int(interleaved),
                        profile_path=profile, coverage_path=coverage, redistribute_path=redistribute, max_passes=redist_passes, hitmap_path=hitmap,
-                       samples_path=samples, sample_redistribute_path=sample_redistribute)
+                       samples_path=samples, sample_redistribute_path=sample_redistribute, redistribute_reads_path=redistribute_reads)
 
 
 def _search_run(db, arr, n_dev, who, fasta, out, rc, threads, input_format, sample_delim, **fields):
