@@ -854,6 +854,65 @@ typedef struct {
 int utree_build_file(const char *fasta_path, const char *map_path, const char *ubt_path, uint32_t W, uint32_t I,
                      int complevel, int gg, int device, utree_build_stats *stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * Database MERGE (`utree-merge` / `utree-mergeGG`; the reference has no such tool, but it defines what one must be).
+ *
+ * A database is what the builder's insert loop (xeTreeU / xeTreeU_RF, itree.c:242-307) holds after being fed (k-mer, label)
+ * pairs in some order.  utree_merge_files(in_paths[0 .. n_in), ...) writes the `.ubt` that UT_writeTreeBinary
+ * (itree.c:1317-1343) would write for the tree of an IMAGINED BUILD (BUILD_GG for gg = 1, BUILD for gg = 0) that is fed, at
+ * compression level 0, one FASTA record of exactly k bases per input node (with lv = 0 a k-base line makes one iteration of
+ * the position loop and yields one word, itree.c:584-624): input by input in argument order, within an input in file order,
+ * each record mapped to the text of the label its node carries.  So:
+ *   - Nodes.  The output holds the distinct words of all inputs, ascending.  A word that occurs in several inputs gets the
+ *     fold of its labels in input order; an equal label text changes nothing.  gg: the folded label is the earlier label cut
+ *     before the last ';' the two texts share in their common byte prefix, or BAD when they share fewer than two
+ *     (critical_cutoff, itree.c:74, 285-304); !gg: any difference is BAD (260-264).  BAD is absorbing within one call and is
+ *     not written.  The reference's rule has consequences that are part of the contract: "k;p;c" against "k;p;c;o" gives
+ *     "k;p"; a third sibling species of one genus lifts the k-mer from genus to family; the result depends on the input order.
+ *   - Labels.  A label gets its index when the first node carrying it is inserted, a prefix label when the collision that
+ *     creates it happens; a text already present keeps its index (addSampleU, itree.c:593 and 299).  A label line of an input
+ *     that none of its nodes carries is not carried over.  The label tail is `text \t nodes carrying it \n` in index order,
+ *     header word 3 the sum of those counts.  No `.log` / `.gg.log` is written.
+ *   - What it is NOT.  (1) A k-mer that an input's own build dropped as BAD has left no trace in that input and can come back
+ *     under another input's label: only a rebuild from FASTA is BAD-exact.  (2) Nothing is known about the compression level:
+ *     inputs built at different levels merge, and the result's sensitivity is that of the sparser one.
+ *
+ * Inputs are `.ubt` or `.ctr` files, told apart by structure: exactly one layout must have a tail that starts inside the file,
+ * consists of complete `text \t decimal \n` lines and counts N nodes (else UTREE_E_FORMAT).  Label lines that repeat a text are
+ * read as the loader reads them (the first line's index).  A `.ctr`'s words are rebuilt from bin membership + suffix; a bin
+ * table that is not non-decreasing, or rebuilt words that are not strictly ascending (xtree-compress's first-bin quirk when the
+ * first prefix holds a single node), are UTREE_E_UNSUPPORTED.  A `.ubt` whose words are not strictly ascending, or a node whose
+ * index names no label line, is UTREE_E_FORMAT.  Inputs of different I merge; inputs of different W, W outside {4, 8, 16}, more
+ * than 65534 labels with a 2-byte index, and 2^24 labels-and-prefixes are UTREE_E_UNSUPPORTED.  I = 0: the widest index among
+ * the inputs; else 2 or 4.  UTREE_E_ARG (NULL path, n_in < 1, another I) is returned before a file is opened or the device is
+ * touched.  utree_last_hip_error has the detail of every failure; a failed call leaves no output file behind.
+ * The nodes go through `device` in passes over contiguous word ranges sized from its free memory (n_passes).
+ * utree_merge_probe (host only) reports how one input reads.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint64_t n_in_nodes;     /* nodes read, all inputs                                   */
+    uint64_t n_nodes;        /* nodes written                                            */
+    uint64_t n_shared;       /* distinct words that occur in more than one input         */
+    uint64_t n_relabelled;   /* ... written under a label none of their inputs gave them */
+    uint64_t n_dropped;      /* ... BAD, not written                                     */
+    uint64_t n_labels;       /* label lines written                                      */
+    uint32_t W, I, n_inputs, n_passes;
+    double   seconds;
+} utree_merge_stats;
+
+int utree_merge_files(const char *const *in_paths, int n_in, const char *ubt_path, uint32_t I, int gg, int device,
+                      utree_merge_stats *stats);
+
+typedef struct {
+    uint32_t W, I;
+    uint32_t is_ctr;         /* 0: `.ubt` layout, 1: `.ctr` layout                       */
+    uint32_t pad;
+    uint64_t n_nodes;
+    uint64_t n_labels;       /* distinct label texts                                     */
+} utree_merge_input;
+
+int utree_merge_probe(const char *path, utree_merge_input *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 #include <unistd.h>
 #include "utree_internal.h"
 #include "build_gpu.h"
+#include "strtab.h"
 
 
 static uint8_t *read_all(const char *path, uint64_t *n) {
@@ -29,56 +30,6 @@ static uint8_t *read_all(const char *path, uint64_t *n) {
     if (b) { memset(b + sz, 0, 16); *n = (uint64_t)sz; }
     return b;
 }
-
-/* ---- interning of byte strings (ptr, len) -> dense ids, strings kept NUL-terminated in one blob ---- */
-typedef struct { char *blob; uint64_t blob_n, blob_cap; uint64_t *off; uint32_t *len; uint32_t n, cap; uint32_t *slot; uint32_t nslot; } strtab;
-static uint64_t hbytes(const char *s, size_t n) { uint64_t h = 1469598103934665603ull; for (size_t i = 0; i < n; ++i) { h ^= (uint8_t)s[i]; h *= 1099511628211ull; } return h; }
-static int st_rehash(strtab *t) {
-    uint32_t ns = t->nslot ? t->nslot * 2 : 4096;
-    uint32_t *sl = (uint32_t *)malloc(sizeof(uint32_t) * ns);
-    if (!sl) return -1;
-    memset(sl, 0xFF, sizeof(uint32_t) * ns);
-    for (uint32_t i = 0; i < t->n; ++i) {
-        uint64_t h = hbytes(t->blob + t->off[i], t->len[i]) & (ns - 1);
-        while (sl[h] != 0xFFFFFFFFu) h = (h + 1) & (ns - 1);
-        sl[h] = i;
-    }
-    free(t->slot); t->slot = sl; t->nslot = ns;
-    return 0;
-}
-/* id of s[0..n); *fresh = 1 when it was added now.  0xFFFFFFFF on allocation failure. */
-static uint32_t st_intern(strtab *t, const char *s, size_t n, int *fresh) {
-    if ((uint64_t)t->n * 2 >= t->nslot && st_rehash(t)) return 0xFFFFFFFFu;
-    uint64_t h = hbytes(s, n) & (t->nslot - 1);
-    while (t->slot[h] != 0xFFFFFFFFu) {
-        uint32_t i = t->slot[h];
-        if (t->len[i] == n && !memcmp(t->blob + t->off[i], s, n)) { *fresh = 0; return i; }
-        h = (h + 1) & (t->nslot - 1);
-    }
-    if (t->n == t->cap) {
-        uint32_t nc = t->cap ? t->cap * 2 : 1024;
-        uint64_t *o = (uint64_t *)realloc(t->off, sizeof(uint64_t) * nc);
-        uint32_t *l = (uint32_t *)realloc(t->len, sizeof(uint32_t) * nc);
-        if (o) t->off = o;
-        if (l) t->len = l;
-        if (!o || !l) return 0xFFFFFFFFu;
-        t->cap = nc;
-    }
-    if (t->blob_n + n + 1 > t->blob_cap) {
-        uint64_t nc = t->blob_cap ? t->blob_cap * 2 : (1u << 16);
-        while (nc < t->blob_n + n + 1) nc *= 2;
-        char *b = (char *)realloc(t->blob, nc);
-        if (!b) return 0xFFFFFFFFu;
-        t->blob = b; t->blob_cap = nc;
-    }
-    memcpy(t->blob + t->blob_n, s, n); t->blob[t->blob_n + n] = 0;
-    t->off[t->n] = t->blob_n; t->len[t->n] = (uint32_t)n;
-    t->blob_n += n + 1;
-    t->slot[h] = t->n;
-    *fresh = 1;
-    return t->n++;
-}
-static void st_free(strtab *t) { free(t->blob); free(t->off); free(t->len); free(t->slot); }
 
 typedef struct { const char *name, *label; } mapent;
 static int by_name(const void *a, const void *b) {                                    /* xcmp, itree.c:486-489 */
@@ -124,13 +75,13 @@ int utree_build_file(const char *fasta_path, const char *map_path, const char *u
     uint64_t fn = 0, mn = 0;
     uint8_t *fa = read_all(fasta_path, &fn), *mp = read_all(map_path, &mn);
     mapent *ent = NULL;
-    uint64_t *seq_off = NULL; uint32_t *seq_len = NULL, *ref_u = NULL, *trunc_off = NULL, *trunc_ids = NULL, *ix_of_u = NULL;
+    uint64_t *seq_off = NULL; uint32_t *seq_len = NULL, *ref_u = NULL, *ix_of_u = NULL;
     uint64_t *per_label = NULL;
     event *ev = NULL;
-    strtab U; memset(&U, 0, sizeof U);
+    label_universe LU; memset(&LU, 0, sizeof LU);
     utk_build_state *S = NULL;
     utk_build_result res; memset(&res, 0, sizeof res);
-    uint32_t n_trunc = 0, trunc_cap = 0, n_refs = 0, ref_cap = 0, n_labels = 0;
+    uint32_t n_refs = 0, ref_cap = 0, n_labels = 0;
     int fd = -1;
     if (!fa || !mp) { rc = UTREE_E_IO; goto done; }                                     /* "Invalid input file(s)" (504): exit 1 */
     if (!mn) { rc = UTREE_E_IO; st.error_kind = UTREE_BUILD_E_MAP_EMPTY; goto done; }   /* "Input map empty." (512): exit 1 */
@@ -179,33 +130,8 @@ int utree_build_file(const char *fasta_path, const char *map_path, const char *u
             /* the label and every cut of it before a ';' (what xeTreeU_RF can turn it into, itree.c:286-301) */
             const char *lab = ent[pre].label;
             size_t ll = strlen(lab);
-            int fresh;
-            uint32_t u = st_intern(&U, lab, ll, &fresh);
+            uint32_t u = universe_add(&LU, lab, ll);
             if (u == 0xFFFFFFFFu) { rc = UTREE_E_NOMEM; goto done; }
-            if (fresh) {
-                uint32_t semis = 0;
-                for (size_t q = 0; q < ll; ++q) semis += lab[q] == ';';
-                if (U.n + semis + 8 > trunc_cap || n_trunc + semis + 8 > trunc_cap) {
-                    uint32_t nc = trunc_cap ? trunc_cap * 2 : 4096;
-                    while (nc < U.n + semis + 8 || nc < n_trunc + semis + 8) nc *= 2;
-                    uint32_t *a = (uint32_t *)realloc(trunc_off, sizeof(uint32_t) * nc), *b = (uint32_t *)realloc(trunc_ids, sizeof(uint32_t) * nc);
-                    if (a) trunc_off = a;
-                    if (b) trunc_ids = b;
-                    if (!a || !b) { rc = UTREE_E_NOMEM; goto done; }
-                    trunc_cap = nc;
-                }
-                const uint32_t list = n_trunc;
-                trunc_off[u] = list;
-                uint32_t m = 0;
-                for (size_t q = 0; q < ll; ++q) if (lab[q] == ';') {
-                    int f2;
-                    uint32_t c = st_intern(&U, lab, q, &f2);
-                    if (c == 0xFFFFFFFFu) { rc = UTREE_E_NOMEM; goto done; }
-                    if (f2) trunc_off[c] = list;                                        /* its own cuts are the first m entries of this list */
-                    trunc_ids[n_trunc++] = c;
-                    ++m;
-                }
-            }
             pos += hl;
             if (pos >= fn) { rc = UTREE_E_BUILD; st.error_kind = UTREE_BUILD_E_FASTA; st.n_seqs = ns; goto done; }   /* 585-586: exit 2 */
             nl = (uint8_t *)memchr(fa + pos, '\n', fn - pos);
@@ -232,11 +158,10 @@ int utree_build_file(const char *fasta_path, const char *map_path, const char *u
         st.n_seqs = ns;
     }
     if (!n_refs) { rc = UTREE_E_BUILD; st.error_kind = UTREE_BUILD_E_NO_KMERS; goto done; }
-    if (U.n + 1 > trunc_cap) { uint32_t *a = (uint32_t *)realloc(trunc_off, sizeof(uint32_t) * (U.n + 8)); if (!a) { rc = UTREE_E_NOMEM; goto done; } trunc_off = a; }
-    trunc_off[U.n] = n_trunc;
+    if (universe_close(&LU)) { rc = UTREE_E_NOMEM; goto done; }
     /* ---- device: k-mers, stable sort, per-k-mer replay ---- */
     {
-        utk_build_job job = {fa, fn, seq_off, seq_len, ref_u, n_refs, U.blob, U.blob_n, U.off, U.n, trunc_off, trunc_ids, n_trunc,
+        utk_build_job job = {fa, fn, seq_off, seq_len, ref_u, n_refs, LU.U.blob, LU.U.blob_n, LU.U.off, LU.U.n, LU.trunc_off, LU.trunc_ids, LU.n_trunc,
                              W, I, (uint32_t)complevel, gg, device};
         rc = utk_build_phase1(&job, &res, &S);
         if (rc) goto done;
@@ -247,13 +172,13 @@ int utree_build_file(const char *fasta_path, const char *map_path, const char *u
      *      a cut label at the collision that first produced it (297); the clock is the position in the input ---- */
     {
         uint64_t nev = 0;
-        ev = (event *)malloc(sizeof(event) * ((size_t)n_refs + U.n + 1));
-        ix_of_u = (uint32_t *)malloc(sizeof(uint32_t) * (U.n + 1));
+        ev = (event *)malloc(sizeof(event) * ((size_t)n_refs + LU.U.n + 1));
+        ix_of_u = (uint32_t *)malloc(sizeof(uint32_t) * (LU.U.n + 1));
         if (!ev || !ix_of_u) { rc = UTREE_E_NOMEM; goto done; }
         for (uint32_t r = 0; r < n_refs; ++r) { ev[nev].time = res.h_ref_time[r]; ev[nev].seq = r; ev[nev].u = ref_u[r]; ++nev; }
-        for (uint32_t u = 0; u < U.n; ++u) if (res.h_first_time[u] != ~0ull) { ev[nev].time = res.h_first_time[u]; ev[nev].seq = 0; ev[nev].u = u; ++nev; }
+        for (uint32_t u = 0; u < LU.U.n; ++u) if (res.h_first_time[u] != ~0ull) { ev[nev].time = res.h_first_time[u]; ev[nev].seq = 0; ev[nev].u = u; ++nev; }
         qsort(ev, nev, sizeof(event), by_time);
-        memset(ix_of_u, 0xFF, sizeof(uint32_t) * (U.n + 1));
+        memset(ix_of_u, 0xFF, sizeof(uint32_t) * (LU.U.n + 1));
         for (uint64_t i = 0; i < nev; ++i) if (ix_of_u[ev[i].u] == 0xFFFFFFFFu) ix_of_u[ev[i].u] = n_labels++;
         if (n_labels >= EMPTY) { rc = UTREE_E_UNSUPPORTED; goto done; }                 /* would collide with EMPTY_IX / BAD_IX */
     }
@@ -266,17 +191,17 @@ int utree_build_file(const char *fasta_path, const char *map_path, const char *u
         per_label = (uint64_t *)calloc(n_labels ? n_labels : 1, sizeof(uint64_t));
         if (!per_label) { rc = UTREE_E_NOMEM; goto done; }
         if (write_all(fd, md, 32)) { rc = UTREE_E_IO; goto done; }
-        rc = utk_build_phase2(S, ix_of_u, U.n, n_labels, fd, per_label);
+        rc = utk_build_phase2(S, ix_of_u, LU.U.n, n_labels, fd, per_label);
         if (rc) goto done;
         /* label lines in index order */
         uint32_t *u_of_ix = (uint32_t *)malloc(sizeof(uint32_t) * (n_labels ? n_labels : 1));
         if (!u_of_ix) { rc = UTREE_E_NOMEM; goto done; }
-        for (uint32_t u = 0; u < U.n; ++u) if (ix_of_u[u] != 0xFFFFFFFFu) u_of_ix[ix_of_u[u]] = u;
-        size_t cap = (size_t)U.blob_n + 32ull * n_labels + 64, o = 0;
+        for (uint32_t u = 0; u < LU.U.n; ++u) if (ix_of_u[u] != 0xFFFFFFFFu) u_of_ix[ix_of_u[u]] = u;
+        size_t cap = (size_t)LU.U.blob_n + 32ull * n_labels + 64, o = 0;
         char *txt = (char *)malloc(cap);
         if (!txt) { free(u_of_ix); rc = UTREE_E_NOMEM; goto done; }
         for (uint32_t i = 0; i < n_labels; ++i)
-            o += (size_t)sprintf(txt + o, "%s\t%llu\n", U.blob + U.off[u_of_ix[i]], (unsigned long long)per_label[i]);
+            o += (size_t)sprintf(txt + o, "%s\t%llu\n", LU.U.blob + LU.U.off[u_of_ix[i]], (unsigned long long)per_label[i]);
         int werr = write_all(fd, txt, o);
         char *logp = (char *)malloc(strlen(ubt_path) + 16);
         if (logp) {
@@ -293,8 +218,8 @@ done:
     if (S) utk_build_free(S);
     free(res.h_first_time); free(res.h_ref_time);
     free(ev); free(ix_of_u); free(per_label);
-    free(seq_off); free(seq_len); free(ref_u); free(trunc_off); free(trunc_ids);
-    st_free(&U);
+    free(seq_off); free(seq_len); free(ref_u);
+    universe_free(&LU);
     free(ent); free(fa); free(mp);
     st.seconds = now_s() - t0;
     if (stats) *stats = st;

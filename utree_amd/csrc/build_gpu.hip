@@ -32,10 +32,13 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 #include "utree_internal.h"
 #include "build_gpu.h"
+#include "build_fold.hpp"
 
 namespace {
 
-constexpr uint32_t ST_BAD = 0xFFFFFFFFu, ST_SKIP = 0xFFFFFFFEu;
+using utk_fold::ST_BAD;
+using utk_fold::ST_SKIP;
+using utk_fold::universe;
 constexpr int BLOCK = 256;
 
 struct dev_in {
@@ -163,22 +166,6 @@ __global__ void gather64_k(const uint64_t *__restrict__ src, const uint64_t *__r
     if (i < n) dst[i] = src[idx[i]];
 }
 
-struct universe {
-    const char *blob; const uint64_t *off;         // NUL-terminated strings
-    const uint32_t *trunc_off, *trunc_ids;         // trunc_ids[trunc_off[u] + m - 1] = u cut before its m-th ';'
-};
-
-// itree.c:286-295: ';' the two labels have in common before their first difference
-__device__ __forceinline__ uint32_t shared_semicolons(const universe &U, uint32_t a, uint32_t b) {
-    const char *x = U.blob + U.off[a], *y = U.blob + U.off[b];
-    uint32_t n = 0;
-    for (;; ++x, ++y) {
-        const char c = *x;
-        if (c != *y || !c) return n;
-        n += c == ';';
-    }
-}
-
 template <int W, bool GG>
 __global__ __launch_bounds__(BLOCK) void fold_k(const uint64_t *__restrict__ key_lo, const uint64_t *__restrict__ key_hi,
                                                 const uint64_t *__restrict__ val, uint64_t n, universe U,
@@ -197,12 +184,9 @@ __global__ __launch_bounds__(BLOCK) void fold_k(const uint64_t *__restrict__ key
     for (uint64_t t = j + 1; t < n && key_lo[t] == lo && (W != 16 || key_hi[t] == hi); ++t) {
         const uint64_t v = val[t];
         const uint32_t nu = (uint32_t)(v & 0xFFFFFFu);
-        if (nu == st) continue;                                             // same label: nothing happens (262, 280)
-        if (!GG) { st = ST_BAD; break; }                                    // 264; BAD is absorbing (263)
-        const uint32_t m = shared_semicolons(U, st, nu);
-        if (m < 2) { st = ST_BAD; break; }                                  // critical_cutoff (74, 295); absorbing (281)
-        st = U.trunc_ids[U.trunc_off[st] + m - 1];                          // 296-301
-        atomicMin(&first_time[st], (unsigned long long)(((v >> 24) << 1) | 1ull));   // event clock: 2*position+1
+        const bool cut = utk_fold::fold_next<GG>(U, st, nu);                // build_fold.hpp: the step merge_kernels.hip shares
+        if (st == ST_BAD) break;                                            // BAD is absorbing (263, 281)
+        if (cut) atomicMin(&first_time[st], (unsigned long long)(((v >> 24) << 1) | 1ull));   // event clock: 2*position+1
     }
     state_out[j] = st;
 }

@@ -1,0 +1,382 @@
+/* merge.c -- host side of utree_merge_files (`utree-merge`, `utree-mergeGG`): the inputs' layouts (`.ubt` or `.ctr`, told apart by
+ * structure), their label lines, the label universe the device folds over, the plan of passes over contiguous ranges of words, the
+ * numbering of labels in the order the imagined build creates them, and the `.ubt` written (UT_writeTreeBinary, itree.c:1317-1343).
+ * The node work is in merge_kernels.hip; include/utree_amd.h states what a merge is.
+ */
+#define _FILE_OFFSET_BITS 64
+#define _GNU_SOURCE
+#include <fcntl.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include "utree_internal.h"
+#include "dev_image.h"
+#include "merge_gpu.h"
+#include "strtab.h"
+
+#define NPREFIX (1u << 24)
+
+typedef struct {
+    const char *path;
+    int fd;
+    const uint8_t *map; uint64_t size;
+    int is_ctr;
+    uint32_t W, I, rec, binw;
+    uint64_t n, rec_off, tail_off;
+    uint64_t *bins;                  /* .ctr: NPREFIX + 1 bin starts */
+    uint32_t *u_of_ix; uint32_t n_lines;       /* distinct label texts in order of first appearance (the loader's numbering) -> universe id */
+    uint64_t g0;                     /* nodes of the inputs in front */
+} merge_in;
+
+static int fail_text(int rc, const char *fmt, const char *path, const char *more) {
+    char msg[512];
+    snprintf(msg, sizeof msg, fmt, path, more);
+    utree_set_error_text(msg);
+    return rc;
+}
+
+/* the tail at `off`: complete `text \t decimal \n` lines whose counts sum to n */
+static int tail_ok(const uint8_t *m, uint64_t size, uint64_t off, uint64_t n) {
+    if (off > size) return 0;
+    uint64_t sum = 0, p = off;
+    while (p < size) {
+        const uint8_t *nl = (const uint8_t *)memchr(m + p, '\n', size - p);
+        if (!nl) return 0;
+        const uint8_t *tab = (const uint8_t *)memchr(m + p, '\t', (size_t)(nl - (m + p)));
+        if (!tab || tab == m + p || tab + 1 == nl) return 0;
+        uint64_t v = 0;
+        for (const uint8_t *d = tab + 1; d < nl; ++d) {
+            if (*d < '0' || *d > '9' || v > (1ull << 60)) return 0;
+            v = v * 10 + (uint64_t)(*d - '0');
+        }
+        sum += v;
+        if (sum > n) return 0;
+        p = (uint64_t)(nl - m) + 1;
+    }
+    return sum == n;
+}
+
+static void close_input(merge_in *in) {
+    if (in->map && in->map != MAP_FAILED) munmap((void *)in->map, in->size ? in->size : 1);
+    if (in->fd >= 0) close(in->fd);
+    free(in->bins); free(in->u_of_ix);
+}
+
+/* header, layout, bin table, label lines -> universe */
+static int open_input(merge_in *in, const char *path, label_universe *L) {
+    in->path = path;
+    in->fd = open(path, O_RDONLY);
+    if (in->fd < 0) return fail_text(UTREE_E_IO, "%s: cannot open%s", path, "");
+    struct stat sb;
+    if (fstat(in->fd, &sb) || !S_ISREG(sb.st_mode)) return fail_text(UTREE_E_IO, "%s: not a readable file%s", path, "");
+    in->size = (uint64_t)sb.st_size;
+    if (in->size < 32) return fail_text(UTREE_E_FORMAT, "%s: shorter than a header%s", path, "");
+    in->map = (const uint8_t *)mmap(NULL, in->size, PROT_READ, MAP_PRIVATE, in->fd, 0);
+    if (in->map == MAP_FAILED) { in->map = NULL; return fail_text(UTREE_E_IO, "%s: cannot map%s", path, ""); }
+    uint64_t md[4];
+    memcpy(md, in->map, 32);
+    if (md[1] != 0 || (md[2] != 2 && md[2] != 4) || md[0] > 64) return fail_text(UTREE_E_FORMAT, "%s: not a .ubt / .ctr header%s", path, "");
+    if (md[0] != 4 && md[0] != 8 && md[0] != 16) return fail_text(UTREE_E_UNSUPPORTED, "%s: word size is not 4, 8 or 16 bytes%s", path, "");
+    in->W = (uint32_t)md[0]; in->I = (uint32_t)md[2]; in->n = md[3];
+    if (in->n > in->size) return fail_text(UTREE_E_FORMAT, "%s: more nodes than bytes%s", path, "");
+    /* exactly one layout must have a tail that starts inside the file, is made of complete lines, and counts n nodes */
+    const uint64_t ubt_tail = 32 + in->n * (in->W + in->I);
+    in->binw = in->n < 0xFFFFFFFFull ? 4 : 8;                                          /* itree.c:1301-1306 */
+    const uint64_t ctr_rec = 32 + (uint64_t)UTREE_NUMBINS * in->binw, ctr_tail = ctr_rec + in->n * (in->W + in->I - 3);
+    const int as_ubt = tail_ok(in->map, in->size, ubt_tail, in->n), as_ctr = tail_ok(in->map, in->size, ctr_tail, in->n);
+    if (as_ubt == as_ctr) return fail_text(UTREE_E_FORMAT, "%s: %s", path, as_ubt ? "reads as a .ubt and as a .ctr" : "neither a .ubt nor a .ctr: no layout ends in label lines that count its nodes");
+    in->is_ctr = as_ctr;
+    in->rec = in->is_ctr ? in->W + in->I - 3 : in->W + in->I;
+    in->rec_off = in->is_ctr ? ctr_rec : 32;
+    in->tail_off = in->is_ctr ? ctr_tail : ubt_tail;
+    if (in->is_ctr) {
+        in->bins = (uint64_t *)malloc(8ull * UTREE_NUMBINS);
+        if (!in->bins) return UTREE_E_NOMEM;
+        const uint8_t *b = in->map + 32;
+        int mono = 1;
+        for (uint32_t p = 0; p < UTREE_NUMBINS; ++p) {
+            uint64_t v;
+            if (in->binw == 4) { uint32_t t; memcpy(&t, b + 4ull * p, 4); v = t; } else memcpy(&v, b + 8ull * p, 8);
+            in->bins[p] = v;
+            if (p && v < in->bins[p - 1]) mono = 0;
+        }
+        if (!mono || in->bins[0] != 0 || in->bins[NPREFIX] != in->n)
+            return fail_text(UTREE_E_UNSUPPORTED, "%s: a .ctr whose bin table is not non-decreasing from 0 to its node count: its words cannot be reconstructed%s", path, "");
+    }
+    /* label lines as the loader reads them (itree.c:191-220): a text's index is that of its first line */
+    {
+        strtab own; memset(&own, 0, sizeof own);
+        uint32_t cap = 0;
+        uint64_t p = in->tail_off;
+        int rc = UTREE_OK;
+        while (p < in->size && !rc) {
+            const uint8_t *nl = (const uint8_t *)memchr(in->map + p, '\n', in->size - p);
+            const uint8_t *tab = (const uint8_t *)memchr(in->map + p, '\t', (size_t)(nl - (in->map + p)));
+            int fresh;
+            const size_t ll = (size_t)(tab - (in->map + p));
+            uint32_t d = st_intern(&own, (const char *)in->map + p, ll, &fresh);
+            if (d == 0xFFFFFFFFu) { rc = UTREE_E_NOMEM; break; }
+            if (fresh) {
+                if (d >= cap) {
+                    cap = cap ? cap * 2 : 1024;
+                    uint32_t *a = (uint32_t *)realloc(in->u_of_ix, 4ull * cap);
+                    if (!a) { rc = UTREE_E_NOMEM; break; }
+                    in->u_of_ix = a;
+                }
+                const uint32_t u = universe_add(L, (const char *)in->map + p, ll);
+                if (u == 0xFFFFFFFFu) { rc = UTREE_E_NOMEM; break; }
+                if (L->U.n >= (1u << 24)) rc = fail_text(UTREE_E_UNSUPPORTED, "%s: labels and their ';'-prefixes reach 2^24%s", path, "");
+                in->u_of_ix[d] = u;
+                in->n_lines = d + 1;
+            }
+            p = (uint64_t)(nl - in->map) + 1;
+        }
+        st_free(&own);
+        if (rc) return rc;
+    }
+    return UTREE_OK;
+}
+
+int utree_merge_probe(const char *path, utree_merge_input *info) {
+    if (!path || !info) return UTREE_E_ARG;
+    merge_in in; memset(&in, 0, sizeof in);
+    in.fd = -1;
+    label_universe L; memset(&L, 0, sizeof L);
+    const int rc = open_input(&in, path, &L);
+    memset(info, 0, sizeof *info);
+    if (!rc) { info->W = in.W; info->I = in.I; info->is_ctr = (uint32_t)in.is_ctr; info->n_nodes = in.n; info->n_labels = in.n_lines; }
+    close_input(&in);
+    universe_free(&L);
+    return rc;
+}
+
+static void rec_word(const merge_in *in, uint64_t node, uint64_t *hi, uint64_t *lo) {      /* .ubt only */
+    const uint8_t *r = in->map + in->rec_off + node * in->rec;
+    *hi = 0; *lo = 0;
+    memcpy(lo, r, in->W == 4 ? 4 : 8);
+    if (in->W == 16) memcpy(hi, r + 8, 8);
+}
+
+/* nodes of the input whose word's top 24 bits are below P (P <= 2^24) */
+static uint64_t count_below(const merge_in *in, uint32_t P) {
+    if (P >= NPREFIX) return in->n;
+    if (in->is_ctr) return in->bins[P];
+    const uint64_t bound = (uint64_t)P << (in->W == 4 ? 8 : 40);                          /* of lo (W = 4, 8) or hi (W = 16) */
+    uint64_t a = 0, b = in->n;
+    while (a < b) {
+        const uint64_t m = a + ((b - a) >> 1);
+        uint64_t hi, lo;
+        rec_word(in, m, &hi, &lo);
+        if ((in->W == 16 ? hi : lo) < bound) a = m + 1; else b = m;
+    }
+    return a;
+}
+
+static uint64_t total_below(const merge_in *ins, int n_in, uint32_t P) {
+    uint64_t t = 0;
+    for (int i = 0; i < n_in; ++i) t += count_below(&ins[i], P);
+    return t;
+}
+
+typedef struct { uint64_t time; uint32_t u; } event;
+static int by_time(const void *a, const void *b) {
+    const event *x = (const event *)a, *y = (const event *)b;
+    return x->time < y->time ? -1 : x->time > y->time;
+}
+
+static int write_all(int fd, const void *p, size_t n) {
+    const char *c = (const char *)p;
+    while (n) { ssize_t w = write(fd, c, n); if (w <= 0) return -1; c += w; n -= (size_t)w; }
+    return 0;
+}
+
+int utree_merge_files(const char *const *in_paths, int n_in, const char *ubt_path, uint32_t I, int gg, int device, utree_merge_stats *stats) {
+    if (!in_paths || n_in < 1 || !ubt_path || (I != 0 && I != 2 && I != 4)) return UTREE_E_ARG;
+    for (int i = 0; i < n_in; ++i) if (!in_paths[i]) return UTREE_E_ARG;
+    utree_merge_stats st; memset(&st, 0, sizeof st);
+    st.n_inputs = (uint32_t)n_in;
+    const double t0 = now_s();
+    int rc = UTREE_OK, fd = -1, created = 0;
+    merge_in *ins = (merge_in *)calloc((size_t)n_in, sizeof(merge_in));
+    label_universe L; memset(&L, 0, sizeof L);
+    uint32_t *bounds = NULL, n_pass = 0, bounds_cap = 0, *ix_of_u = NULL, *u_of_ix = NULL, n_labels = 0;
+    uint32_t **maps = NULL, *n_lines = NULL;
+    uint64_t *first_time = NULL, *per_label = NULL;
+    utk_merge_slice *sl = NULL;
+    event *ev = NULL;
+    utk_merge_dev *D = NULL;
+    char *txt = NULL;
+    if (!ins) return UTREE_E_NOMEM;
+    for (int i = 0; i < n_in; ++i) ins[i].fd = -1;
+    /* ---- the inputs ---- */
+    uint32_t W = 0, I_out = I, rec_max = 0;
+    int any_ctr = 0;
+    for (int i = 0; i < n_in; ++i) {
+        rc = open_input(&ins[i], in_paths[i], &L);
+        if (rc) goto done;
+        if (i && ins[i].W != W) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: its word size differs from the first input's%s", in_paths[i], ""); goto done; }
+        W = ins[i].W;
+        if (!I && ins[i].I > I_out) I_out = ins[i].I;
+        if (ins[i].rec > rec_max) rec_max = ins[i].rec;
+        any_ctr |= ins[i].is_ctr;
+        ins[i].g0 = st.n_in_nodes;
+        st.n_in_nodes += ins[i].n;
+    }
+    st.W = W; st.I = I_out;
+    if (st.n_in_nodes >= (1ull << 40)) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: 2^40 nodes or more in all%s", ubt_path, ""); goto done; }
+    if (universe_close(&L)) { rc = UTREE_E_NOMEM; goto done; }
+    /* ---- passes: contiguous ranges of the words' top 24 bits, so a run of equal words is never split and a `.ctr`'s slice is a range of bins ---- */
+    uint64_t limit = 0, cap_nodes = 0, cap_raw = 0;
+    rc = utk_merge_limit(device, W, rec_max, &limit);
+    if (rc) goto done;
+    {
+        uint64_t want = limit;
+        const char *e = getenv("UTREE_TEST_MERGE_PASS_NODES");                            /* test hook: small inputs in many passes */
+        if (e && atoll(e) > 0 && (uint64_t)atoll(e) < want) want = (uint64_t)atoll(e);
+        uint32_t P0 = 0;
+        uint64_t below0 = 0;
+        while (below0 < st.n_in_nodes) {
+            uint32_t a = P0 + 1, b = NPREFIX;                                             /* the largest P1 in [a, b] with at most `want` nodes in [P0, P1); a itself if none */
+            if (total_below(ins, n_in, b) - below0 <= want) a = b;
+            else while (a < b) {
+                const uint32_t m = a + ((b - a + 1) >> 1);
+                if (total_below(ins, n_in, m) - below0 <= want) a = m; else b = m - 1;
+            }
+            if (total_below(ins, n_in, a) == below0) ++a;                                 /* nothing below the prefix that alone exceeds `want`: no empty pass, take that prefix */
+            const uint64_t below1 = total_below(ins, n_in, a);
+            if (below1 - below0 > limit) { rc = fail_text(UTREE_E_NOMEM, "%s: the nodes that share one 24-bit prefix do not fit the device's free memory%s", ubt_path, ""); goto done; }
+            if (n_pass + 2 > bounds_cap) {
+                bounds_cap = bounds_cap ? bounds_cap * 2 : 64;
+                uint32_t *nb = (uint32_t *)realloc(bounds, 4ull * bounds_cap);
+                if (!nb) { rc = UTREE_E_NOMEM; goto done; }
+                bounds = nb;
+            }
+            if (!n_pass) bounds[0] = 0;
+            bounds[++n_pass] = a;
+            if (below1 - below0 > cap_nodes) cap_nodes = below1 - below0;
+            uint64_t raw = 0;
+            for (int i = 0; i < n_in; ++i) raw += ((count_below(&ins[i], a) - count_below(&ins[i], P0)) * ins[i].rec + 255) & ~255ull;
+            if (raw > cap_raw) cap_raw = raw;
+            P0 = a; below0 = below1;
+        }
+    }
+    st.n_passes = n_pass;
+    /* ---- device ---- */
+    maps = (uint32_t **)calloc((size_t)n_in, sizeof *maps); n_lines = (uint32_t *)calloc((size_t)n_in, 4);
+    sl = (utk_merge_slice *)calloc((size_t)n_in, sizeof *sl);
+    first_time = (uint64_t *)malloc(8ull * (L.U.n + 1)); ix_of_u = (uint32_t *)malloc(4ull * (L.U.n + 1));
+    ev = (event *)malloc(sizeof(event) * (L.U.n + 1ull));
+    if (!maps || !n_lines || !sl || !first_time || !ix_of_u || !ev) { rc = UTREE_E_NOMEM; goto done; }
+    for (int i = 0; i < n_in; ++i) { maps[i] = ins[i].u_of_ix; n_lines[i] = ins[i].n_lines; }
+    {
+        utk_merge_cfg cfg = {L.U.blob, L.U.blob_n, L.U.off, L.U.n, L.trunc_off, L.trunc_ids, L.n_trunc, (uint32_t)n_in,
+                             (const uint32_t *const *)maps, n_lines, W, I_out, gg, device, any_ctr, cap_nodes, cap_raw};
+        rc = utk_merge_open(&cfg, &D);
+        if (rc) goto done;
+    }
+    /* One pass: its nodes stay on the device while the labels are numbered.  Several: the label numbers depend on every pass's events, so a
+     * first sweep replays all passes for the events alone and a second one replays them again and writes. */
+    for (int sweep = 0; sweep < (n_pass > 1 ? 2 : 1); ++sweep) {
+        for (uint32_t p = 0; p < n_pass; ++p) {
+            uint64_t raw_off = 0;
+            for (int i = 0; i < n_in; ++i) {
+                const merge_in *in = &ins[i];
+                utk_merge_slice *s = &sl[i];
+                memset(s, 0, sizeof *s);
+                const uint64_t first = count_below(in, bounds[p]), end = count_below(in, bounds[p + 1]);
+                s->input = (uint32_t)i; s->is_ctr = (uint32_t)in->is_ctr; s->I = in->I;
+                s->n = end - first; s->raw_off = raw_off; s->g0 = in->g0 + first; s->first = first;
+                s->fd = in->fd; s->file_off = in->rec_off + first * in->rec;
+                if (!s->n) continue;
+                raw_off += (s->n * in->rec + 255) & ~255ull;
+                if (in->is_ctr) {
+                    s->p_lo = bounds[p]; s->n_bins = bounds[p + 1] - bounds[p]; s->h_bins = in->bins + bounds[p];
+                    if (first) {                                                           /* the node in front lies in the last non-empty bin below */
+                        uint32_t q = bounds[p];
+                        while (q && in->bins[q] >= first) --q;                             /* bins[q] < first <= bins[q + 1] */
+                        const uint8_t *r = in->map + in->rec_off + (first - 1) * in->rec;
+                        uint64_t suf_lo = 0, suf_hi = 0;
+                        memcpy(&suf_lo, r, in->W == 16 ? 8 : in->W - 3);
+                        if (in->W == 16) memcpy(&suf_hi, r + 8, 5);
+                        s->has_prev = 1;
+                        if (in->W == 4) s->prev_lo = ((uint64_t)q << 8) | suf_lo;
+                        else if (in->W == 8) s->prev_lo = ((uint64_t)q << 40) | suf_lo;
+                        else { s->prev_lo = suf_lo; s->prev_hi = ((uint64_t)q << 40) | suf_hi; }
+                    }
+                } else if (first) { s->has_prev = 1; rec_word(in, first - 1, &s->prev_hi, &s->prev_lo); }
+            }
+            utk_merge_pass_out po;
+            uint32_t io_slice = 0;
+            rc = utk_merge_pass(D, sl, (uint32_t)n_in, sweep == 0, &po, &io_slice);
+            if (rc == UTREE_E_IO) fail_text(rc, "%s: cannot read its nodes%s", ins[io_slice].path, "");
+            if (rc) goto done;
+            if (po.err & 2u) { rc = fail_text(UTREE_E_FORMAT, "%s: a node's label index names no label line of its input%s", ubt_path, ""); goto done; }
+            if (po.err & 1u) { rc = fail_text(UTREE_E_FORMAT, "%s: the words of a .ubt input are not strictly ascending%s", ubt_path, ""); goto done; }
+            if (po.err & 4u) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: a .ctr input whose words, rebuilt from its bins, are not strictly ascending (xtree-compress's first-bin quirk does that when the first prefix holds one node): its words cannot be reconstructed%s", ubt_path, ""); goto done; }
+            if (sweep == 0) { st.n_nodes += po.n_nodes; st.n_shared += po.n_shared; st.n_relabelled += po.n_relabelled; st.n_dropped += po.n_dropped; }
+            if (n_pass > 1 && sweep == 0) continue;
+            if (fd < 0) {
+                /* ---- label indices in the imagined build's order of creation (addSampleU, itree.c:593; addSampleUd, 299) ---- */
+                uint64_t nev = 0;
+                rc = utk_merge_events(D, first_time);
+                if (rc) goto done;
+                for (uint32_t u = 0; u < L.U.n; ++u) if (first_time[u] != ~0ull) { ev[nev].time = first_time[u]; ev[nev].u = u; ++nev; }
+                qsort(ev, nev, sizeof(event), by_time);
+                memset(ix_of_u, 0xFF, 4ull * (L.U.n + 1));
+                for (uint64_t i = 0; i < nev; ++i) ix_of_u[ev[i].u] = n_labels++;
+                st.n_labels = n_labels;
+                if (I_out == 2 && n_labels > 65534) {
+                    rc = fail_text(UTREE_E_UNSUPPORTED, "%s: more than 65534 labels do not fit a 2-byte index (65534 and 65535 are EMPTY_IX and BAD_IX): ask for the 4-byte index (I = 4, UTREE_IXTYPE=32)%s", ubt_path, "");
+                    goto done;
+                }
+                rc = utk_merge_set_ix(D, ix_of_u, n_labels);
+                if (rc) goto done;
+                fd = open(ubt_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+                if (fd < 0) { rc = fail_text(UTREE_E_IO, "%s: cannot create%s", ubt_path, ""); goto done; }
+                created = 1;
+                uint64_t md[4] = {W, 0, I_out, st.n_nodes};
+                if (write_all(fd, md, 32)) { rc = fail_text(UTREE_E_IO, "%s: cannot write%s", ubt_path, ""); goto done; }
+            }
+            rc = utk_merge_emit(D, fd);
+            if (rc) { if (rc == UTREE_E_IO) fail_text(rc, "%s: cannot write%s", ubt_path, ""); goto done; }
+        }
+    }
+    if (fd < 0) {                                                                          /* inputs without a node: the header alone */
+        fd = open(ubt_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) { rc = fail_text(UTREE_E_IO, "%s: cannot create%s", ubt_path, ""); goto done; }
+        created = 1;
+        uint64_t md[4] = {W, 0, I_out, 0};
+        if (write_all(fd, md, 32)) { rc = fail_text(UTREE_E_IO, "%s: cannot write%s", ubt_path, ""); goto done; }
+    }
+    /* ---- label lines in index order: text \t nodes carrying it ---- */
+    {
+        per_label = (uint64_t *)calloc(n_labels ? n_labels : 1, 8);
+        u_of_ix = (uint32_t *)malloc(4ull * (n_labels ? n_labels : 1));
+        txt = (char *)malloc((size_t)L.U.blob_n + 32ull * n_labels + 64);
+        if (!per_label || !u_of_ix || !txt) { rc = UTREE_E_NOMEM; goto done; }
+        if (n_labels) { rc = utk_merge_counts(D, per_label); if (rc) goto done; }
+        for (uint32_t u = 0; u < L.U.n; ++u) if (ix_of_u[u] != 0xFFFFFFFFu) u_of_ix[ix_of_u[u]] = u;
+        size_t o = 0;
+        for (uint32_t i = 0; i < n_labels; ++i) {
+            const uint32_t u = u_of_ix[i];
+            memcpy(txt + o, L.U.blob + L.U.off[u], L.U.len[u]); o += L.U.len[u];
+            o += (size_t)sprintf(txt + o, "\t%llu\n", (unsigned long long)per_label[i]);
+        }
+        if (write_all(fd, txt, o)) { rc = fail_text(UTREE_E_IO, "%s: cannot write%s", ubt_path, ""); goto done; }
+    }
+    if (close(fd)) { fd = -1; rc = fail_text(UTREE_E_IO, "%s: cannot write%s", ubt_path, ""); goto done; }
+    fd = -1;
+done:
+    if (fd >= 0) close(fd);
+    if (rc && created) unlink(ubt_path);                                                   /* a failed call leaves no output file behind */
+    if (D) utk_merge_close(D);
+    if (ins) { for (int i = 0; i < n_in; ++i) close_input(&ins[i]); free(ins); }
+    universe_free(&L);
+    free(bounds); free(ix_of_u); free(u_of_ix); free(maps); free(n_lines); free(first_time); free(per_label); free(sl); free(ev); free(txt);
+    st.seconds = now_s() - t0;
+    if (stats) *stats = st;
+    return rc;
+}

@@ -15,6 +15,8 @@ COMPRESS_CLI_PATH = os.path.join(_HERE, "xtree-compress")
 RANK_CLI_PATH = os.path.join(_HERE, "xtree-search")
 BUILD_GG_CLI_PATH = os.path.join(_HERE, "utree-buildGG")
 BUILD_CLI_PATH = os.path.join(_HERE, "utree-build")
+MERGE_GG_CLI_PATH = os.path.join(_HERE, "utree-mergeGG")
+MERGE_CLI_PATH = os.path.join(_HERE, "utree-merge")
 _LIB = None
 
 OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE, E_PAIRS, E_HITMAP = range(16)
@@ -63,6 +65,19 @@ class BuildStats(C.Structure):
                 ("error_line", C.c_uint64), ("error_kind", C.c_int), ("W", C.c_uint32), ("I", C.c_uint32),
                 ("seconds", C.c_double), ("n_distinct", C.c_uint64), ("map_bytes", C.c_uint64), ("map_lines", C.c_uint64),
                 ("map_error", C.c_int)]
+
+
+class MergeStats(C.Structure):
+    """utree_merge_stats: nodes read and written, the shared words and what became of them, labels written, passes."""
+    _fields_ = [("n_in_nodes", C.c_uint64), ("n_nodes", C.c_uint64), ("n_shared", C.c_uint64), ("n_relabelled", C.c_uint64),
+                ("n_dropped", C.c_uint64), ("n_labels", C.c_uint64), ("W", C.c_uint32), ("I", C.c_uint32), ("n_inputs", C.c_uint32),
+                ("n_passes", C.c_uint32), ("seconds", C.c_double)]
+
+
+class MergeInput(C.Structure):
+    """utree_merge_input: how utree_merge_files reads one input file."""
+    _fields_ = [("W", C.c_uint32), ("I", C.c_uint32), ("is_ctr", C.c_uint32), ("pad", C.c_uint32), ("n_nodes", C.c_uint64),
+                ("n_labels", C.c_uint64)]
 
 
 class RankParams(C.Structure):
@@ -202,7 +217,9 @@ SYMBOLS = {
                                               C.c_int, C.c_int, C.POINTER(SearchStats)]),
     "utree_build_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(BuildStats)]),
-    "utree_search_prepare": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]),
+    "utree_merge_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(MergeStats)]),
+    "utree_merge_probe": (C.c_int, [C.c_char_p, C.POINTER(MergeInput)]),
+    "utree_search_prepare":(C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "utree_search_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                     C.POINTER(SearchStats)]),
     "utree_search_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(SearchRequest), C.POINTER(SearchStats)]),

@@ -1009,6 +1009,37 @@ def compress(ubt: str, ctr: str, device: int = 0):
     return code, st
 
 
+def merge(inputs, ubt: str, gg: bool = True, I: int = 0, device: int = 0):
+    """`utree-merge[GG] out.ubt in1 [in2 ...]`: the `.ubt` / `.ctr` databases `inputs` folded into one `.ubt` as the builder's insert loop
+    would (include/utree_amd.h: utree_merge_files).  Returns the MergeStats; raises UtreeError (with .detail: what utree_last_hip_error
+    said) when the call fails, and no output file is left then."""
+    paths = [p.encode() for p in inputs]
+    arr = (C.c_char_p * max(len(paths), 1))(*paths)
+    st = _lib.MergeStats()
+    L = _lib.load()
+    code = L.utree_merge_files(arr, len(paths), ubt.encode(), I, int(gg), device, C.byref(st))
+    if code != _lib.OK:
+        detail = (L.utree_last_hip_error() or b"").decode(errors="replace")
+        e = _lib.UtreeError(code, "merge: " + detail)
+        e.detail = detail
+        e.stats = st
+        raise e
+    return st
+
+
+def merge_probe(path: str):
+    """How utree_merge_files reads one input (host only): the MergeInput (W, I, is_ctr, n_nodes, n_labels); raises UtreeError."""
+    info = _lib.MergeInput()
+    L = _lib.load()
+    code = L.utree_merge_probe(path.encode(), C.byref(info))
+    if code != _lib.OK:
+        detail = (L.utree_last_hip_error() or b"").decode(errors="replace")
+        e = _lib.UtreeError(code, "merge_probe: " + detail)
+        e.detail = detail
+        raise e
+    return info
+
+
 def classify_fasta_bytes(db: CtrDB, tree: DeviceTree, data: bytes, rc: bool = False) -> bytes:
     """Convenience for tests: frame -> upload -> classify -> format, through the C-ABI pieces."""
     import torch
