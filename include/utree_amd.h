@@ -913,6 +913,78 @@ typedef struct {
 
 int utree_merge_probe(const char *path, utree_merge_input *info);
 
+/* ------------------------------------------------------------------------------------------------
+ * EDITING while merging: cut labels to a rank, drop clades, keep only some clades, rename clades, subtract another database's
+ * k-mers.  utree_merge_files_edit(in_paths, n_in, ubt_path, I, gg, device, edit, stats, edit_stats) writes the `.ubt` of the
+ * merge's imagined build above, fed the nodes of the regular inputs in argument order and file order, EXCEPT
+ *   (a) nodes whose label the edit drops,
+ *   (b) nodes whose word occurs in any MINUS input (edit->minus_paths) -- for every input, regardless of argument order; a MINUS
+ *       input contributes no record and no label, and the label edit does not apply to it,
+ * and (c) with every remaining record mapped to the EDITED text of its label.  Everything else is utree_merge_files unchanged:
+ * the fold (itree.c:242-307), the creation-order numbering (itree.c:593, 299), "a label line no node carries is not carried
+ * over", the 2-byte limit of 65534 labels (applied to the labels AFTER the edit), the refusals of inputs (they hold for MINUS
+ * inputs too: same W, `.ubt` or `.ctr`, words strictly ascending; a MINUS input's label indices are not looked at), and "a
+ * failed call leaves no output file".  utree_merge_files(...) is utree_merge_files_edit(..., NULL, stats, NULL).
+ *
+ * The label edit of one label text t, in this order:
+ *   1. clade match: a rule taxon p matches t iff t == p or t begins with p followed by ';' ("k__A;p__B" does not match
+ *      "k__A;p__Bx");
+ *   2. selection, on the original text: t is dropped when a keep file is given and no keep line matches it, or when some drop
+ *      line matches it (drop beats keep);
+ *   3. rename: among the rename lines `old \t new` whose old matches t, the one with the longest old is applied, once, with no
+ *      chaining: t' = new + t[len(old):];
+ *   4. ranks: with ranks = n, a t' that holds at least n ';' is cut before its n-th ';' (its first n tokens stay), else it is
+ *      unchanged;
+ *   5. empty result: an edited text that is empty is UTREE_E_FORMAT (the builder refuses blank labels); utree_last_hip_error
+ *      names the label.
+ * Rule files: lines end at '\n' (the last may lack it), one trailing '\r' is removed, empty lines are ignored, there is no
+ * comment syntax, spaces and bytes above 0x7F are ordinary.  Drop and keep files: the whole line is the taxon, a TAB in it is
+ * UTREE_E_FORMAT.  Rename file: exactly one TAB with both sides non-empty, else UTREE_E_FORMAT; two lines with the same old are
+ * UTREE_E_FORMAT.  The error text names the file and the 1-based line.  A file that cannot be opened is UTREE_E_IO.  A rule
+ * that matches no label line of any regular input is no error: it is counted (n_rules_unmatched), and the preview lists it.
+ * UTREE_E_ARG (edit->size, ranks > 255, n_minus < 0, n_minus > 0 with a NULL array or entry, and utree_merge_files' own) comes
+ * before any file is touched.
+ *
+ * With an edit utree_merge_stats reads: n_in_nodes the nodes read from the regular inputs; n_shared (two or more records fed),
+ * n_relabelled, n_dropped (BAD) and n_nodes those of the records actually fed.  n_in_nodes == records fed + n_nodes_dropped +
+ * n_nodes_subtracted; a node that is both label-dropped and in a MINUS input counts as dropped.
+ *
+ * LIMITS.  (1) Dropping a clade removes the k-mers still labelled inside it: k-mers that an earlier fold lifted to an ancestor
+ * and k-mers an earlier build dropped as BAD do not change back -- only a rebuild is exact.  (2) A rename does not re-fold
+ * earlier folds: texts that become equal merge into one label line, nothing else moves.  (3) MINUS is by identical word, as
+ * stored: the database holds k-mers in the references' orientation and the search covers the other strand by appending the
+ * reverse complement, so a contaminant on the opposite strand is removed only if the MINUS database was built from both
+ * strands.  (4) A MINUS database built above compression level 0 holds only a sample of its k-mers (itree.c:603-616: the
+ * sampling looks at the bases in front of the k-mer).  Build a MINUS database at level 0 from the host FASTA plus its reverse
+ * complement.
+ *
+ * utree_merge_edit_preview (host only, never touches a device; minus_paths is ignored) writes to tsv_path, per regular input,
+ * `# input \t path \t .ubt|.ctr \t nodes \t labels` followed, per distinct label text of that input in line order, by
+ * `text \t nodes its first line states \t keep|rename|cut|rename+cut|drop \t edited text (empty for drop)`, and at the end one
+ * `# unmatched \t rule file \t line \t rule taxon` per unmatched rule (drop file, keep file, rename file; line order).  Its
+ * n_nodes_dropped is the sum of the stated counts of the dropped texts; n_minus_nodes and n_nodes_subtracted are 0.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t size;                 /* sizeof(utree_merge_edit), else UTREE_E_ARG */
+    uint32_t ranks;                /* 0: none; 1..255: cut each label before its ranks-th ';'; > 255: UTREE_E_ARG */
+    const char *drop_path, *keep_path, *rename_path;      /* NULL: none */
+    const char *const *minus_paths; int n_minus;          /* n_minus < 0, or > 0 with a NULL array or a NULL entry: UTREE_E_ARG */
+} utree_merge_edit;
+
+typedef struct {
+    uint64_t n_label_lines;      /* distinct label texts looked at, summed over the regular inputs */
+    uint64_t n_labels_dropped, n_labels_renamed, n_labels_cut;   /* of those; a text both renamed and cut counts in both */
+    uint64_t n_rules_unmatched;
+    uint64_t n_nodes_dropped;    /* regular-input nodes not fed because their label was dropped */
+    uint64_t n_minus_nodes;      /* nodes read from the MINUS inputs */
+    uint64_t n_nodes_subtracted; /* regular-input nodes the label edit kept, not fed because their word is in a MINUS input */
+} utree_merge_edit_stats;
+
+int utree_merge_files_edit(const char *const *in_paths, int n_in, const char *ubt_path, uint32_t I, int gg, int device,
+                           const utree_merge_edit *edit, utree_merge_stats *stats, utree_merge_edit_stats *edit_stats);
+int utree_merge_edit_preview(const char *const *in_paths, int n_in, const utree_merge_edit *edit, const char *tsv_path,
+                             utree_merge_edit_stats *st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,9 @@
 /* merge.c -- host side of utree_merge_files (`utree-merge`, `utree-mergeGG`): the inputs' layouts (`.ubt` or `.ctr`, told apart by
  * structure), their label lines, the label universe the device folds over, the plan of passes over contiguous ranges of words, the
  * numbering of labels in the order the imagined build creates them, and the `.ubt` written (UT_writeTreeBinary, itree.c:1317-1343).
- * The node work is in merge_kernels.hip; include/utree_amd.h states what a merge is.
+ * The node work is in merge_kernels.hip; include/utree_amd.h states what a merge is.  utree_merge_files_edit is the same call with an edit:
+ * each label line goes through label_edit.c on its way into the universe, MINUS inputs are further slices of every pass, and
+ * utree_merge_edit_preview shows what the label edit would do without a device.
  */
 #define _FILE_OFFSET_BITS 64
 #define _GNU_SOURCE
@@ -15,6 +17,7 @@
 #include "utree_internal.h"
 #include "dev_image.h"
 #include "merge_gpu.h"
+#include "label_edit.h"
 #include "strtab.h"
 
 #define NPREFIX (1u << 24)
@@ -65,8 +68,10 @@ static void close_input(merge_in *in) {
     free(in->bins); free(in->u_of_ix);
 }
 
-/* header, layout, bin table, label lines -> universe */
-static int open_input(merge_in *in, const char *path, label_universe *L) {
+/* header, layout, bin table, label lines -> universe.  R (or NULL): each distinct label text goes through the label edit; its edited text
+ * enters the universe in its place, a dropped one maps to UTK_MERGE_DROP; es (or NULL) counts what the edit did, tsv (or NULL) gets the
+ * preview's line per text.  minus: a MINUS input gives words only, its label lines are not read. */
+static int open_input(merge_in *in, const char *path, label_universe *L, le_rules *R, utree_merge_edit_stats *es, int minus, FILE *tsv) {
     in->path = path;
     in->fd = open(path, O_RDONLY);
     if (in->fd < 0) return fail_text(UTREE_E_IO, "%s: cannot open%s", path, "");
@@ -107,7 +112,7 @@ static int open_input(merge_in *in, const char *path, label_universe *L) {
             return fail_text(UTREE_E_UNSUPPORTED, "%s: a .ctr whose bin table is not non-decreasing from 0 to its node count: its words cannot be reconstructed%s", path, "");
     }
     /* label lines as the loader reads them (itree.c:191-220): a text's index is that of its first line */
-    {
+    if (!minus) {
         strtab own; memset(&own, 0, sizeof own);
         uint32_t cap = 0;
         uint64_t p = in->tail_off;
@@ -126,9 +131,32 @@ static int open_input(merge_in *in, const char *path, label_universe *L) {
                     if (!a) { rc = UTREE_E_NOMEM; break; }
                     in->u_of_ix = a;
                 }
-                const uint32_t u = universe_add(L, (const char *)in->map + p, ll);
-                if (u == 0xFFFFFFFFu) { rc = UTREE_E_NOMEM; break; }
-                if (L->U.n >= (1u << 24)) rc = fail_text(UTREE_E_UNSUPPORTED, "%s: labels and their ';'-prefixes reach 2^24%s", path, "");
+                const char *text = (const char *)in->map + p;
+                size_t tn = ll;
+                const int act = R ? le_apply(R, text, ll, &text, &tn) : LE_KEEP;
+                if (act < 0) { rc = UTREE_E_NOMEM; break; }
+                if (es) { ++es->n_label_lines; es->n_labels_dropped += act == LE_DROP; es->n_labels_renamed += act != LE_DROP && (act & LE_RENAME); es->n_labels_cut += act != LE_DROP && (act & LE_CUT); }
+                uint32_t u = UTK_MERGE_DROP;
+                if (act != LE_DROP) {
+                    if (!tn) {                                                 /* the builder refuses blank labels */
+                        char name[300];
+                        snprintf(name, sizeof name, "%.*s", (int)(ll < 280 ? ll : 280), (const char *)in->map + p);
+                        rc = fail_text(UTREE_E_FORMAT, "%s: the edit leaves label `%s` empty", path, name);
+                        break;
+                    }
+                    u = universe_add(L, text, tn);
+                    if (u == 0xFFFFFFFFu) { rc = UTREE_E_NOMEM; break; }
+                    if (L->U.n >= (1u << 24)) rc = fail_text(UTREE_E_UNSUPPORTED, "%s: labels and their ';'-prefixes reach 2^24%s", path, "");
+                }
+                if (tsv) {
+                    static const char *const names[4] = {"keep", "rename", "cut", "rename+cut"};
+                    fwrite(in->map + p, 1, ll, tsv); fputc('\t', tsv);
+                    fwrite(tab + 1, 1, (size_t)(nl - tab - 1), tsv);
+                    fprintf(tsv, "\t%s\t", act == LE_DROP ? "drop" : names[act & 3]);
+                    if (act != LE_DROP) fwrite(text, 1, tn, tsv);
+                    fputc('\n', tsv);
+                    if (act == LE_DROP && es) es->n_nodes_dropped += strtoull((const char *)tab + 1, NULL, 10);
+                }
                 in->u_of_ix[d] = u;
                 in->n_lines = d + 1;
             }
@@ -145,7 +173,7 @@ int utree_merge_probe(const char *path, utree_merge_input *info) {
     merge_in in; memset(&in, 0, sizeof in);
     in.fd = -1;
     label_universe L; memset(&L, 0, sizeof L);
-    const int rc = open_input(&in, path, &L);
+    const int rc = open_input(&in, path, &L, NULL, NULL, 0, NULL);
     memset(info, 0, sizeof *info);
     if (!rc) { info->W = in.W; info->I = in.I; info->is_ctr = (uint32_t)in.is_ctr; info->n_nodes = in.n; info->n_labels = in.n_lines; }
     close_input(&in);
@@ -193,14 +221,85 @@ static int write_all(int fd, const void *p, size_t n) {
     return 0;
 }
 
+static int edit_args_bad(const utree_merge_edit *e) {
+    if (e->size != sizeof(utree_merge_edit) || e->ranks > 255 || e->n_minus < 0 || (e->n_minus > 0 && !e->minus_paths)) return 1;
+    for (int i = 0; i < e->n_minus; ++i) if (!e->minus_paths[i]) return 1;
+    return 0;
+}
+
+static int load_rules(const utree_merge_edit *e, le_rules **R) {
+    char msg[512];
+    msg[0] = 0;
+    const int rc = le_load(R, e->ranks, e->drop_path, e->keep_path, e->rename_path, msg, sizeof msg);
+    if (rc && msg[0]) utree_set_error_text(msg);
+    return rc;
+}
+
+static void preview_unmatched(void *ctx, const char *file, uint64_t line, const char *text, size_t text_n) {
+    FILE *out = (FILE *)ctx;
+    fprintf(out, "# unmatched\t%s\t%llu\t", file, (unsigned long long)line);
+    fwrite(text, 1, text_n, out);
+    fputc('\n', out);
+}
+
+int utree_merge_edit_preview(const char *const *in_paths, int n_in, const utree_merge_edit *edit, const char *tsv_path, utree_merge_edit_stats *stats) {
+    if (!in_paths || n_in < 1 || !edit || !tsv_path || edit_args_bad(edit)) return UTREE_E_ARG;
+    for (int i = 0; i < n_in; ++i) if (!in_paths[i]) return UTREE_E_ARG;
+    utree_merge_edit_stats es; memset(&es, 0, sizeof es);
+    le_rules *R = NULL;
+    label_universe L; memset(&L, 0, sizeof L);
+    FILE *out = NULL;
+    int rc = load_rules(edit, &R);
+    if (!rc && !(out = fopen(tsv_path, "wb"))) rc = fail_text(UTREE_E_IO, "%s: cannot create%s", tsv_path, "");
+    for (int i = 0; i < n_in && !rc; ++i) {
+        merge_in in; memset(&in, 0, sizeof in);
+        in.fd = -1;
+        char *lines = NULL; size_t lines_n = 0;
+        FILE *mem = open_memstream(&lines, &lines_n);                                      /* the input's line comes first and states how many follow */
+        if (!mem) rc = UTREE_E_NOMEM;
+        else {
+            rc = open_input(&in, in_paths[i], &L, R, &es, 0, mem);
+            if (fclose(mem) && !rc) rc = UTREE_E_NOMEM;
+        }
+        if (!rc) {
+            fprintf(out, "# input\t%s\t%s\t%llu\t%u\n", in_paths[i], in.is_ctr ? ".ctr" : ".ubt", (unsigned long long)in.n, in.n_lines);
+            fwrite(lines, 1, lines_n, out);
+        }
+        free(lines);
+        close_input(&in);
+    }
+    if (!rc) {
+        es.n_rules_unmatched = le_unmatched(R);
+        le_each_unmatched(R, preview_unmatched, out);
+    }
+    if (out) {
+        const int bad = ferror(out);
+        if ((fclose(out) || bad) && !rc) rc = fail_text(UTREE_E_IO, "%s: cannot write%s", tsv_path, "");
+        if (rc) unlink(tsv_path);                                                          /* a failed call leaves no file behind */
+    }
+    le_free(R);
+    universe_free(&L);
+    if (stats) *stats = es;
+    return rc;
+}
+
 int utree_merge_files(const char *const *in_paths, int n_in, const char *ubt_path, uint32_t I, int gg, int device, utree_merge_stats *stats) {
+    return utree_merge_files_edit(in_paths, n_in, ubt_path, I, gg, device, NULL, stats, NULL);
+}
+
+int utree_merge_files_edit(const char *const *in_paths, int n_in, const char *ubt_path, uint32_t I, int gg, int device,
+                           const utree_merge_edit *edit, utree_merge_stats *stats, utree_merge_edit_stats *edit_stats) {
     if (!in_paths || n_in < 1 || !ubt_path || (I != 0 && I != 2 && I != 4)) return UTREE_E_ARG;
     for (int i = 0; i < n_in; ++i) if (!in_paths[i]) return UTREE_E_ARG;
+    if (edit && edit_args_bad(edit)) return UTREE_E_ARG;
+    const int n_minus = edit ? edit->n_minus : 0, n_all = n_in + n_minus;                   /* ins[]: the MINUS inputs, then the regular ones */
     utree_merge_stats st; memset(&st, 0, sizeof st);
+    utree_merge_edit_stats es; memset(&es, 0, sizeof es);
     st.n_inputs = (uint32_t)n_in;
     const double t0 = now_s();
     int rc = UTREE_OK, fd = -1, created = 0;
-    merge_in *ins = (merge_in *)calloc((size_t)n_in, sizeof(merge_in));
+    merge_in *ins = (merge_in *)calloc((size_t)n_all, sizeof(merge_in));
+    le_rules *R = NULL;
     label_universe L; memset(&L, 0, sizeof L);
     uint32_t *bounds = NULL, n_pass = 0, bounds_cap = 0, *ix_of_u = NULL, *u_of_ix = NULL, n_labels = 0;
     uint32_t **maps = NULL, *n_lines = NULL;
@@ -210,23 +309,28 @@ int utree_merge_files(const char *const *in_paths, int n_in, const char *ubt_pat
     utk_merge_dev *D = NULL;
     char *txt = NULL;
     if (!ins) return UTREE_E_NOMEM;
-    for (int i = 0; i < n_in; ++i) ins[i].fd = -1;
-    /* ---- the inputs ---- */
+    for (int i = 0; i < n_all; ++i) ins[i].fd = -1;
+    if (edit) { rc = load_rules(edit, &R); if (rc) goto done; }
+    /* ---- the inputs: the regular ones first, so that a MINUS input of another word size is the one refused ---- */
     uint32_t W = 0, I_out = I, rec_max = 0;
     int any_ctr = 0;
-    for (int i = 0; i < n_in; ++i) {
-        rc = open_input(&ins[i], in_paths[i], &L);
+    for (int o = 0; o < n_all; ++o) {
+        const int minus = o >= n_in, i = minus ? o - n_in : n_minus + o;
+        const char *path = minus ? edit->minus_paths[o - n_in] : in_paths[o];
+        rc = open_input(&ins[i], path, &L, R, edit ? &es : NULL, minus, NULL);
         if (rc) goto done;
-        if (i && ins[i].W != W) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: its word size differs from the first input's%s", in_paths[i], ""); goto done; }
+        if (o && ins[i].W != W) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: its word size differs from the first input's%s", path, ""); goto done; }
         W = ins[i].W;
-        if (!I && ins[i].I > I_out) I_out = ins[i].I;
         if (ins[i].rec > rec_max) rec_max = ins[i].rec;
         any_ctr |= ins[i].is_ctr;
+        if (minus) { es.n_minus_nodes += ins[i].n; continue; }
+        if (!I && ins[i].I > I_out) I_out = ins[i].I;
         ins[i].g0 = st.n_in_nodes;
         st.n_in_nodes += ins[i].n;
     }
     st.W = W; st.I = I_out;
-    if (st.n_in_nodes >= (1ull << 40)) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: 2^40 nodes or more in all%s", ubt_path, ""); goto done; }
+    const uint64_t n_read = st.n_in_nodes + es.n_minus_nodes;
+    if (n_read >= (1ull << 40)) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: 2^40 nodes or more in all%s", ubt_path, ""); goto done; }
     if (universe_close(&L)) { rc = UTREE_E_NOMEM; goto done; }
     /* ---- passes: contiguous ranges of the words' top 24 bits, so a run of equal words is never split and a `.ctr`'s slice is a range of bins ---- */
     uint64_t limit = 0, cap_nodes = 0, cap_raw = 0;
@@ -238,15 +342,15 @@ int utree_merge_files(const char *const *in_paths, int n_in, const char *ubt_pat
         if (e && atoll(e) > 0 && (uint64_t)atoll(e) < want) want = (uint64_t)atoll(e);
         uint32_t P0 = 0;
         uint64_t below0 = 0;
-        while (below0 < st.n_in_nodes) {
+        while (below0 < n_read) {
             uint32_t a = P0 + 1, b = NPREFIX;                                             /* the largest P1 in [a, b] with at most `want` nodes in [P0, P1); a itself if none */
-            if (total_below(ins, n_in, b) - below0 <= want) a = b;
+            if (total_below(ins, n_all, b) - below0 <= want) a = b;
             else while (a < b) {
                 const uint32_t m = a + ((b - a + 1) >> 1);
-                if (total_below(ins, n_in, m) - below0 <= want) a = m; else b = m - 1;
+                if (total_below(ins, n_all, m) - below0 <= want) a = m; else b = m - 1;
             }
-            if (total_below(ins, n_in, a) == below0) ++a;                                 /* nothing below the prefix that alone exceeds `want`: no empty pass, take that prefix */
-            const uint64_t below1 = total_below(ins, n_in, a);
+            if (total_below(ins, n_all, a) == below0) ++a;                                 /* nothing below the prefix that alone exceeds `want`: no empty pass, take that prefix */
+            const uint64_t below1 = total_below(ins, n_all, a);
             if (below1 - below0 > limit) { rc = fail_text(UTREE_E_NOMEM, "%s: the nodes that share one 24-bit prefix do not fit the device's free memory%s", ubt_path, ""); goto done; }
             if (n_pass + 2 > bounds_cap) {
                 bounds_cap = bounds_cap ? bounds_cap * 2 : 64;
@@ -258,22 +362,22 @@ int utree_merge_files(const char *const *in_paths, int n_in, const char *ubt_pat
             bounds[++n_pass] = a;
             if (below1 - below0 > cap_nodes) cap_nodes = below1 - below0;
             uint64_t raw = 0;
-            for (int i = 0; i < n_in; ++i) raw += ((count_below(&ins[i], a) - count_below(&ins[i], P0)) * ins[i].rec + 255) & ~255ull;
+            for (int i = 0; i < n_all; ++i) raw += ((count_below(&ins[i], a) - count_below(&ins[i], P0)) * ins[i].rec + 255) & ~255ull;
             if (raw > cap_raw) cap_raw = raw;
             P0 = a; below0 = below1;
         }
     }
     st.n_passes = n_pass;
     /* ---- device ---- */
-    maps = (uint32_t **)calloc((size_t)n_in, sizeof *maps); n_lines = (uint32_t *)calloc((size_t)n_in, 4);
-    sl = (utk_merge_slice *)calloc((size_t)n_in, sizeof *sl);
+    maps = (uint32_t **)calloc((size_t)n_all, sizeof *maps); n_lines = (uint32_t *)calloc((size_t)n_all, 4);
+    sl = (utk_merge_slice *)calloc((size_t)n_all, sizeof *sl);
     first_time = (uint64_t *)malloc(8ull * (L.U.n + 1)); ix_of_u = (uint32_t *)malloc(4ull * (L.U.n + 1));
     ev = (event *)malloc(sizeof(event) * (L.U.n + 1ull));
     if (!maps || !n_lines || !sl || !first_time || !ix_of_u || !ev) { rc = UTREE_E_NOMEM; goto done; }
-    for (int i = 0; i < n_in; ++i) { maps[i] = ins[i].u_of_ix; n_lines[i] = ins[i].n_lines; }
+    for (int i = 0; i < n_all; ++i) { maps[i] = ins[i].u_of_ix; n_lines[i] = ins[i].n_lines; }
     {
-        utk_merge_cfg cfg = {L.U.blob, L.U.blob_n, L.U.off, L.U.n, L.trunc_off, L.trunc_ids, L.n_trunc, (uint32_t)n_in,
-                             (const uint32_t *const *)maps, n_lines, W, I_out, gg, device, any_ctr, cap_nodes, cap_raw};
+        utk_merge_cfg cfg = {L.U.blob, L.U.blob_n, L.U.off, L.U.n, L.trunc_off, L.trunc_ids, L.n_trunc, (uint32_t)n_all,
+                             (const uint32_t *const *)maps, n_lines, W, I_out, gg, device, any_ctr, n_minus > 0, cap_nodes, cap_raw};
         rc = utk_merge_open(&cfg, &D);
         if (rc) goto done;
     }
@@ -282,12 +386,12 @@ int utree_merge_files(const char *const *in_paths, int n_in, const char *ubt_pat
     for (int sweep = 0; sweep < (n_pass > 1 ? 2 : 1); ++sweep) {
         for (uint32_t p = 0; p < n_pass; ++p) {
             uint64_t raw_off = 0;
-            for (int i = 0; i < n_in; ++i) {
+            for (int i = 0; i < n_all; ++i) {                                              /* MINUS slices in front: the stable sort keeps a MINUS record at the head of its run */
                 const merge_in *in = &ins[i];
                 utk_merge_slice *s = &sl[i];
                 memset(s, 0, sizeof *s);
                 const uint64_t first = count_below(in, bounds[p]), end = count_below(in, bounds[p + 1]);
-                s->input = (uint32_t)i; s->is_ctr = (uint32_t)in->is_ctr; s->I = in->I;
+                s->input = (uint32_t)i; s->is_ctr = (uint32_t)in->is_ctr; s->I = in->I; s->minus = i < n_minus;
                 s->n = end - first; s->raw_off = raw_off; s->g0 = in->g0 + first; s->first = first;
                 s->fd = in->fd; s->file_off = in->rec_off + first * in->rec;
                 if (!s->n) continue;
@@ -310,13 +414,13 @@ int utree_merge_files(const char *const *in_paths, int n_in, const char *ubt_pat
             }
             utk_merge_pass_out po;
             uint32_t io_slice = 0;
-            rc = utk_merge_pass(D, sl, (uint32_t)n_in, sweep == 0, &po, &io_slice);
+            rc = utk_merge_pass(D, sl, (uint32_t)n_all, sweep == 0, &po, &io_slice);
             if (rc == UTREE_E_IO) fail_text(rc, "%s: cannot read its nodes%s", ins[io_slice].path, "");
             if (rc) goto done;
             if (po.err & 2u) { rc = fail_text(UTREE_E_FORMAT, "%s: a node's label index names no label line of its input%s", ubt_path, ""); goto done; }
             if (po.err & 1u) { rc = fail_text(UTREE_E_FORMAT, "%s: the words of a .ubt input are not strictly ascending%s", ubt_path, ""); goto done; }
             if (po.err & 4u) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: a .ctr input whose words, rebuilt from its bins, are not strictly ascending (xtree-compress's first-bin quirk does that when the first prefix holds one node): its words cannot be reconstructed%s", ubt_path, ""); goto done; }
-            if (sweep == 0) { st.n_nodes += po.n_nodes; st.n_shared += po.n_shared; st.n_relabelled += po.n_relabelled; st.n_dropped += po.n_dropped; }
+            if (sweep == 0) { st.n_nodes += po.n_nodes; st.n_shared += po.n_shared; st.n_relabelled += po.n_relabelled; st.n_dropped += po.n_dropped; es.n_nodes_dropped += po.n_label_dropped; es.n_nodes_subtracted += po.n_subtracted; }
             if (n_pass > 1 && sweep == 0) continue;
             if (fd < 0) {
                 /* ---- label indices in the imagined build's order of creation (addSampleU, itree.c:593; addSampleUd, 299) ---- */
@@ -373,10 +477,13 @@ done:
     if (fd >= 0) close(fd);
     if (rc && created) unlink(ubt_path);                                                   /* a failed call leaves no output file behind */
     if (D) utk_merge_close(D);
-    if (ins) { for (int i = 0; i < n_in; ++i) close_input(&ins[i]); free(ins); }
+    if (ins) { for (int i = 0; i < n_all; ++i) close_input(&ins[i]); free(ins); }
+    if (R) es.n_rules_unmatched = le_unmatched(R);
+    le_free(R);
     universe_free(&L);
     free(bounds); free(ix_of_u); free(u_of_ix); free(maps); free(n_lines); free(first_time); free(per_label); free(sl); free(ev); free(txt);
     st.seconds = now_s() - t0;
     if (stats) *stats = st;
+    if (edit_stats) *edit_stats = es;
     return rc;
 }

@@ -8,6 +8,9 @@
 extern "C" {
 #endif
 
+/* what h_u_of_ix holds for a label line the edit drops (utree_merge_files_edit); universe ids stay below it (n_u < 2^24) */
+#define UTK_MERGE_DROP 0xFFFFFFu
+
 typedef struct {
     const char *h_ublob; uint64_t ublob_bytes;              /* universe: every input label and every ';'-prefix of one, NUL-terminated */
     const uint64_t *h_uoff; uint32_t n_u;
@@ -18,6 +21,8 @@ typedef struct {
     const uint32_t *n_lines;
     uint32_t W, I_out;
     int gg, device, any_ctr;
+    int has_minus;                                          /* some slice is a MINUS input's: which records are fed is known only after the sort, so
+                                                               the fold dates the labels of the records it feeds, not the decode */
     uint64_t cap_nodes;                                     /* nodes of the largest pass                                    */
     uint64_t cap_raw;                                       /* bytes of the largest pass's records as utk_merge_slice lays them out */
 } utk_merge_cfg;
@@ -25,6 +30,7 @@ typedef struct {
 /* one contiguous stretch of one input's nodes, all of one pass's word range */
 typedef struct {
     uint32_t input, is_ctr, I;
+    uint32_t minus;                  /* a MINUS input's slice: words only.  MINUS slices come before the regular ones in a pass */
     uint64_t n;                      /* records: rec bytes each at file_off of fd; they go to raw_off (a multiple of 256) of the pass's device buffer */
     int fd; uint64_t file_off;
     uint64_t raw_off;
@@ -37,6 +43,8 @@ typedef struct {
 
 typedef struct {
     uint64_t n_nodes, n_shared, n_relabelled, n_dropped;
+    uint64_t n_label_dropped;        /* regular records whose label line maps to UTK_MERGE_DROP                             */
+    uint64_t n_subtracted;           /* regular records with a label, not fed because a MINUS slice holds their word        */
     uint32_t err;                    /* bit 0: a `.ubt` slice not strictly ascending; 1: a node index without a label line; 2: `.ctr` words not ascending */
 } utk_merge_pass_out;
 

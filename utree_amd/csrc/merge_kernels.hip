@@ -12,6 +12,12 @@
 //   merge_fold_k                  one thread per distinct word replays its run (at most one node per input) with build_fold.hpp's step
 //   rocprim::select               words that are not BAD, ascending
 //   merge_pack_k                  W+I-byte records as the file holds them + nodes per label
+//
+// utree_merge_files_edit rides in the value word of that one sort.  A record whose label line the edit drops carries DROP in place of a
+// universe id; a MINUS input's record (words only: its slice's label indices are never looked at) is VAL_MINUS.  MINUS slices are laid
+// out in front of the regular ones, so the stable sort leaves a MINUS record at the head of its run: such a run feeds nothing, any other
+// run folds the records that are not DROP.  With a MINUS input the records fed are known only after the sort, so merge_fold_k dates the
+// labels then (has_minus); without one decode_k dates them as before.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -36,6 +42,10 @@ using utk_fold::universe;
 constexpr int BLOCK = 256;
 constexpr int REC_MAX = 20;                                // W = 16, I = 4
 constexpr uint32_t ERR_UBT_ORDER = 1u, ERR_IX = 2u, ERR_CTR_ORDER = 4u;
+constexpr uint32_t DROP = UTK_MERGE_DROP;                  // in the label field of a value: the record is not fed
+constexpr uint64_t VAL_MINUS = ~0ull;                      // no regular record has it: event clocks stay below 2^40 - 1
+constexpr uint32_t ROLE_DATES = 0, ROLE_REGULAR = 1, ROLE_MINUS = 2;   // a regular slice whose records date their labels here / in the fold; a MINUS slice
+constexpr int STAT_SHARED = 0, STAT_RELABELLED = 1, STAT_BAD = 2, STAT_LABEL_DROPPED = 3, STAT_SUBTRACTED = 4, N_STATS = 8;
 
 struct slice_dev {
     const uint32_t *raw;             // the slice's records, dword aligned, readable up to the dword that holds the last byte
@@ -45,7 +55,13 @@ struct slice_dev {
     uint32_t I;
     int has_prev; uint64_t prev_hi, prev_lo;
     const uint64_t *bins; uint32_t p_lo, n_bins; uint64_t first;       // .ctr
+    uint32_t role;
 };
+
+__device__ __forceinline__ void wave_count(bool pred, unsigned long long *ctr) {
+    const uint64_t m = __ballot(pred);
+    if (m && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(ctr, (unsigned long long)__popcll(m));
+}
 
 // the 256 records of this block as dwords into LDS: consecutive lanes load consecutive dwords
 __device__ __forceinline__ void stage_records(const uint32_t *__restrict__ raw, uint64_t n, uint32_t rec, uint32_t *s) {
@@ -87,7 +103,7 @@ __device__ __forceinline__ uint32_t bin_of(const uint64_t *__restrict__ bins, ui
 template <int W, bool CTR>
 __global__ __launch_bounds__(BLOCK) void decode_k(slice_dev S, uint64_t at, uint64_t *__restrict__ key_lo, uint64_t *__restrict__ key_hi,
                                                   uint64_t *__restrict__ val, unsigned long long *__restrict__ first_time,
-                                                  uint32_t *__restrict__ err) {
+                                                  uint32_t *__restrict__ err, unsigned long long *__restrict__ stats) {
     __shared__ uint32_t s_raw[(BLOCK / 4) * REC_MAX];
     __shared__ uint64_t s_lo[BLOCK], s_hi[W == 16 ? BLOCK : 1];
     const uint32_t rec = (CTR ? W - 3 : W) + S.I;
@@ -116,16 +132,19 @@ __global__ __launch_bounds__(BLOCK) void decode_k(slice_dev S, uint64_t at, uint
         else ubt_word<W>(tmp, phi, plo);
     } else { have = S.has_prev != 0; phi = S.prev_hi; plo = S.prev_lo; }
     if (have && !(phi < hi || (phi == hi && plo < lo))) atomicOr(err, CTR ? ERR_CTR_ORDER : ERR_UBT_ORDER);
+    key_lo[at + j] = lo;
+    if (W == 16) key_hi[at + j] = hi;
+    if (S.role == ROLE_MINUS) { val[at + j] = VAL_MINUS; return; }          // uniform over the launch: words only
     const uint32_t ix = (uint32_t)le_bytes(p + (CTR ? W - 3 : W), (int)S.I);
     uint32_t u = 0;
     if (ix < S.n_lines) u = S.u_of_ix[ix]; else atomicOr(err, ERR_IX);
     const uint64_t g = S.g0 + j;
-    key_lo[at + j] = lo;
-    if (W == 16) key_hi[at + j] = hi;
     val[at + j] = (g << 24) | u;
+    const bool dropped = ix < S.n_lines && u == DROP;                       // the edit dropped its label line: not fed, dates nothing
+    wave_count(dropped, stats + STAT_LABEL_DROPPED);
     // addSampleU (itree.c:593): the label is created when the first record that carries it is parsed.  Clocks ascend with the
     // thread index, so all but the first few carriers of a label see a smaller time already there and skip the atomic.
-    if (ix < S.n_lines && first_time[u] > 2 * g) atomicMin(&first_time[u], (unsigned long long)(2 * g));
+    if (S.role == ROLE_DATES && ix < S.n_lines && !dropped && first_time[u] > 2 * g) atomicMin(&first_time[u], (unsigned long long)(2 * g));
 }
 
 __global__ void iota_k(uint64_t *idx, uint64_t n) {
@@ -137,41 +156,49 @@ __global__ void gather64_k(const uint64_t *__restrict__ src, const uint64_t *__r
     if (i < n) dst[i] = src[idx[i]];
 }
 
-__device__ __forceinline__ void wave_count(bool pred, unsigned long long *ctr) {
-    const uint64_t m = __ballot(pred);
-    if (m && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(ctr, (unsigned long long)__popcll(m));
-}
-
-// stats[0] shared words, [1] of them relabelled, [2] of them BAD
+// stats[STAT_SHARED] words that two or more records fed carry, [STAT_RELABELLED] of them relabelled, [STAT_BAD] of them BAD,
+// [STAT_SUBTRACTED] records with a label that a MINUS record's run keeps from being fed
 template <int W, bool GG>
 __global__ __launch_bounds__(BLOCK) void merge_fold_k(const uint64_t *__restrict__ key_lo, const uint64_t *__restrict__ key_hi,
                                                       const uint64_t *__restrict__ val, uint64_t n, universe U,
                                                       unsigned long long *__restrict__ first_time, uint32_t *__restrict__ state_out,
-                                                      unsigned long long *__restrict__ stats) {
+                                                      unsigned long long *__restrict__ stats, int date) {
     const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     const uint64_t lo = j < n ? key_lo[j] : 0, hi = (W == 16 && j < n) ? key_hi[j] : 0;
     const bool head = j < n && !(j && key_lo[j - 1] == lo && (W != 16 || key_hi[j - 1] == hi));
-    uint32_t st = ST_SKIP;
+    uint32_t st = ST_SKIP;                                                  // a run that feeds no record writes nothing
     bool shared = false, relabelled = false;
-    if (head) {
-        st = (uint32_t)(val[j] & 0xFFFFFFu);
-        uint64_t t = j + 1;
-        for (; t < n && key_lo[t] == lo && (W != 16 || key_hi[t] == hi); ++t) {
-            if (st == ST_BAD) continue;                                     // BAD is absorbing (263, 281); the run is walked to its end for `shared`
+    if (head && val[j] == VAL_MINUS) {
+        // a MINUS input holds the word (its records lead the run): nothing is fed; the records that would have been are counted
+        uint32_t sub = 0;
+        for (uint64_t t = j + 1; t < n && key_lo[t] == lo && (W != 16 || key_hi[t] == hi); ++t) {
             const uint64_t v = val[t];
-            const bool cut = utk_fold::fold_next<GG>(U, st, (uint32_t)(v & 0xFFFFFFu));
+            sub += v != VAL_MINUS && (uint32_t)(v & 0xFFFFFFu) != DROP;
+        }
+        if (sub) atomicAdd(&stats[STAT_SUBTRACTED], (unsigned long long)sub);
+    } else if (head) {
+        uint32_t fed = 0;
+        uint64_t t = j;
+        for (; t < n && (t == j || (key_lo[t] == lo && (W != 16 || key_hi[t] == hi))); ++t) {
+            const uint64_t v = val[t];
+            const uint32_t u = (uint32_t)(v & 0xFFFFFFu);
+            if (u == DROP) continue;                                        // its label line was dropped: as if the input lacked the word
+            if (date && first_time[u] > (v >> 24) << 1) atomicMin(&first_time[u], (unsigned long long)((v >> 24) << 1));   // addSampleU (593), see decode_k
+            if (++fed == 1) { st = u; continue; }
+            if (st == ST_BAD) continue;                                     // BAD is absorbing (263, 281); the run is walked to its end for `shared`
+            const bool cut = utk_fold::fold_next<GG>(U, st, u);
             if (cut && st != ST_BAD) atomicMin(&first_time[st], (unsigned long long)(((v >> 24) << 1) | 1ull));   // event clock: 2 * node + 1
         }
-        shared = t > j + 1;
+        shared = fed > 1;
         if (shared && st != ST_BAD) {
             relabelled = true;
             for (uint64_t q = j; q < t; ++q) if ((uint32_t)(val[q] & 0xFFFFFFu) == st) relabelled = false;
         }
     }
     if (j < n) state_out[j] = st;
-    wave_count(shared, stats + 0);
-    wave_count(relabelled, stats + 1);
-    wave_count(shared && st == ST_BAD, stats + 2);
+    wave_count(shared, stats + STAT_SHARED);
+    wave_count(relabelled, stats + STAT_RELABELLED);
+    wave_count(shared && st == ST_BAD, stats + STAT_BAD);
 }
 
 struct is_node { __device__ bool operator()(uint32_t s) const { return s < ST_SKIP; } };
@@ -295,7 +322,7 @@ int utk_merge_open(const utk_merge_cfg *cfg, utk_merge_dev **out) {
     HK(dmalloc(&D->st, D->cap)); HK(dmalloc(&D->st2, D->cap));
     if (cfg->any_ctr) HK(dmalloc(&D->d_bins, (uint64_t)UTREE_NUMBINS + 1));
     HK(dmalloc(&D->d_ublob, cfg->ublob_bytes + 8)); HK(dmalloc(&D->d_uoff, cfg->n_u)); HK(dmalloc(&D->d_toff, (uint64_t)cfg->n_u + 1));
-    HK(dmalloc(&D->d_tids, cfg->n_trunc)); HK(dmalloc(&D->d_first, cfg->n_u)); HK(dmalloc(&D->d_stats, 4)); HK(dmalloc(&D->d_nsel, 1));
+    HK(dmalloc(&D->d_tids, cfg->n_trunc)); HK(dmalloc(&D->d_first, cfg->n_u)); HK(dmalloc(&D->d_stats, N_STATS)); HK(dmalloc(&D->d_nsel, 1));
     HK(dmalloc(&D->d_err, 1)); HK(dmalloc(&D->d_ix, cfg->n_u));
     for (int q = 0; q < 2; ++q) {
         HK(dmalloc(&D->d_out[q], D->out_chunk * (cfg->W + cfg->I_out)));
@@ -327,7 +354,7 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
     size_t tb = 0, tb2 = 0;
     uint64_t n = 0;
     int turn = 0, used[2] = {0, 0};
-    unsigned long long h_stats[4] = {0, 0, 0, 0}, nn = 0;
+    unsigned long long h_stats[N_STATS] = {0}, nn = 0;
     uint32_t h_err = 0;
     uint64_t *k_lo = D->b[0], *k_val = D->b[1], *s_lo, *s_hi = nullptr, *s_val;
     memset(out, 0, sizeof *out);
@@ -341,7 +368,7 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
     }
     if (n > D->cap) return UTREE_E_ARG;
     HK(hipMemset(D->d_err, 0, 4));
-    HK(hipMemset(D->d_stats, 0, 32));
+    HK(hipMemset(D->d_stats, 0, 8 * N_STATS));
     if (!n) return UTREE_OK;
     {
         uint64_t at = 0;
@@ -359,13 +386,14 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
             }
             if (sl[s].is_ctr) HK(hipMemcpy(D->d_bins, sl[s].h_bins, 8ull * (sl[s].n_bins + 1ull), hipMemcpyHostToDevice));
             const slice_dev S = {(const uint32_t *)(D->d_raw + sl[s].raw_off), sl[s].n, sl[s].g0, D->d_u_of_ix[sl[s].input], D->cfg.n_lines[sl[s].input],
-                                 sl[s].I, sl[s].has_prev, sl[s].prev_hi, sl[s].prev_lo, D->d_bins, sl[s].p_lo, sl[s].n_bins, sl[s].first};
+                                 sl[s].I, sl[s].has_prev, sl[s].prev_hi, sl[s].prev_lo, D->d_bins, sl[s].p_lo, sl[s].n_bins, sl[s].first,
+                                 sl[s].minus ? ROLE_MINUS : D->cfg.has_minus ? ROLE_REGULAR : ROLE_DATES};
             const unsigned gb = (unsigned)((sl[s].n + BLOCK - 1) / BLOCK);
             const bool ctr = sl[s].is_ctr != 0;
             dispatch_w(W, [&](auto w) {
                 constexpr int WV = decltype(w)::value;
-                if (ctr) decode_k<WV, true><<<dim3(gb), dim3(BLOCK)>>>(S, at, k_lo, D->b[4], k_val, D->d_first, D->d_err);
-                else decode_k<WV, false><<<dim3(gb), dim3(BLOCK)>>>(S, at, k_lo, D->b[4], k_val, D->d_first, D->d_err);
+                if (ctr) decode_k<WV, true><<<dim3(gb), dim3(BLOCK)>>>(S, at, k_lo, D->b[4], k_val, D->d_first, D->d_err, D->d_stats);
+                else decode_k<WV, false><<<dim3(gb), dim3(BLOCK)>>>(S, at, k_lo, D->b[4], k_val, D->d_first, D->d_err, D->d_stats);
             });
             HK(hipGetLastError());
             if (ctr) HK(hipDeviceSynchronize());                            /* the bin scratch is reused by the next `.ctr` slice */
@@ -403,8 +431,8 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
         // ---- replay each run of equal words ----
         dispatch_w(W, [&](auto w) {
             constexpr int WV = decltype(w)::value;
-            if (D->cfg.gg) merge_fold_k<WV, true><<<dim3(gb), dim3(BLOCK)>>>(s_lo, s_hi, s_val, n, U, D->d_first, D->st, D->d_stats);
-            else merge_fold_k<WV, false><<<dim3(gb), dim3(BLOCK)>>>(s_lo, s_hi, s_val, n, U, D->d_first, D->st, D->d_stats);
+            if (D->cfg.gg) merge_fold_k<WV, true><<<dim3(gb), dim3(BLOCK)>>>(s_lo, s_hi, s_val, n, U, D->d_first, D->st, D->d_stats, D->cfg.has_minus);
+            else merge_fold_k<WV, false><<<dim3(gb), dim3(BLOCK)>>>(s_lo, s_hi, s_val, n, U, D->d_first, D->st, D->d_stats, D->cfg.has_minus);
         });
         HK(hipGetLastError());
         // ---- keep what is not BAD, ascending: the sorted buffers are compacted into the ones the unsorted words came in ----
@@ -418,13 +446,16 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
             if (W == 16) HK(rocprim::select(tmp, tb, s_hi, flags, D->b[1], D->d_nsel, n));
             HK(rocprim::select(tmp, tb, D->st, flags, D->st2, D->d_nsel, n));
             HK(hipMemcpy(&nn, D->d_nsel, 8, hipMemcpyDeviceToHost));
-            HK(hipMemcpy(h_stats, D->d_stats, 32, hipMemcpyDeviceToHost));
+            HK(hipMemcpy(h_stats, D->d_stats, 8 * N_STATS, hipMemcpyDeviceToHost));
             HK(hipDeviceSynchronize());
             HK(hipFree(tmp)); tmp = nullptr;
         }
         D->seg_n = nn; D->seg_lo = D->b[0]; D->seg_hi = W == 16 ? D->b[1] : nullptr; D->seg_st = D->st2;
         out->n_nodes = nn;
-        if (count_stats) { out->n_shared = h_stats[0]; out->n_relabelled = h_stats[1]; out->n_dropped = h_stats[2]; }
+        if (count_stats) {
+            out->n_shared = h_stats[STAT_SHARED]; out->n_relabelled = h_stats[STAT_RELABELLED]; out->n_dropped = h_stats[STAT_BAD];
+            out->n_label_dropped = h_stats[STAT_LABEL_DROPPED]; out->n_subtracted = h_stats[STAT_SUBTRACTED];
+        }
     }
 fail:
     if (rc) (void)hipDeviceSynchronize();

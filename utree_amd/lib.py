@@ -80,6 +80,22 @@ class MergeInput(C.Structure):
                 ("n_labels", C.c_uint64)]
 
 
+class MergeEdit(C.Structure):
+    """utree_merge_edit: the edit of utree_merge_files_edit; the paths are bytes or None, `size` is filled in."""
+    _fields_ = [("size", C.c_uint32), ("ranks", C.c_uint32), ("drop_path", C.c_char_p), ("keep_path", C.c_char_p),
+                ("rename_path", C.c_char_p), ("minus_paths", C.POINTER(C.c_char_p)), ("n_minus", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__(size=C.sizeof(MergeEdit), **kw)
+
+
+class MergeEditStats(C.Structure):
+    """utree_merge_edit_stats: what the label edit did to the label lines, and the nodes it and the MINUS inputs kept from being fed."""
+    _fields_ = [("n_label_lines", C.c_uint64), ("n_labels_dropped", C.c_uint64), ("n_labels_renamed", C.c_uint64),
+                ("n_labels_cut", C.c_uint64), ("n_rules_unmatched", C.c_uint64), ("n_nodes_dropped", C.c_uint64),
+                ("n_minus_nodes", C.c_uint64), ("n_nodes_subtracted", C.c_uint64)]
+
+
 class RankParams(C.Structure):
     """SLACK, SPARSITY, TOLERANCE_THRESHOLD of the rank-specific search (itree.c:952-960)."""
     _fields_ = [("slack", C.c_uint32), ("sparsity", C.c_uint32), ("tolerance", C.c_uint32)]
@@ -219,6 +235,9 @@ SYMBOLS = {
                                    C.POINTER(BuildStats)]),
     "utree_merge_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(MergeStats)]),
     "utree_merge_probe": (C.c_int, [C.c_char_p, C.POINTER(MergeInput)]),
+    "utree_merge_files_edit": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(MergeEdit),
+                                         C.POINTER(MergeStats), C.POINTER(MergeEditStats)]),
+    "utree_merge_edit_preview": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(MergeEdit), C.c_char_p, C.POINTER(MergeEditStats)]),
     "utree_search_prepare":(C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "utree_search_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                     C.POINTER(SearchStats)]),

@@ -1027,6 +1027,52 @@ def merge(inputs, ubt: str, gg: bool = True, I: int = 0, device: int = 0):
     return st
 
 
+def _merge_edit_struct(ranks, drop, keep, rename, minus):
+    """(the MergeEdit, what must stay alive while it is in use)"""
+    mp = [p.encode() for p in minus]
+    arr = (C.c_char_p * max(len(mp), 1))(*mp)
+    enc = lambda p: p.encode() if p is not None else None
+    ed = _lib.MergeEdit(ranks=ranks, drop_path=enc(drop), keep_path=enc(keep), rename_path=enc(rename),
+                        minus_paths=C.cast(arr, C.POINTER(C.c_char_p)) if mp else None, n_minus=len(mp))
+    return ed, arr
+
+
+def merge_edit(inputs, ubt: str, gg: bool = True, I: int = 0, device: int = 0, ranks: int = 0, drop=None, keep=None, rename=None, minus=()):
+    """merge() with an edit (include/utree_amd.h: utree_merge_files_edit): labels cut to their first `ranks` ranks, the clades listed in the
+    file `drop` dropped, only those in `keep` kept, clades renamed by the `old TAB new` lines of `rename`, and every word that a database
+    of `minus` holds subtracted.  Returns (MergeStats, MergeEditStats); raises UtreeError as merge() does (.edit_stats is set too)."""
+    paths = [p.encode() for p in inputs]
+    arr = (C.c_char_p * max(len(paths), 1))(*paths)
+    ed, _alive = _merge_edit_struct(ranks, drop, keep, rename, minus)
+    st, es = _lib.MergeStats(), _lib.MergeEditStats()
+    L = _lib.load()
+    code = L.utree_merge_files_edit(arr, len(paths), ubt.encode(), I, int(gg), device, C.byref(ed), C.byref(st), C.byref(es))
+    if code != _lib.OK:
+        detail = (L.utree_last_hip_error() or b"").decode(errors="replace")
+        e = _lib.UtreeError(code, "merge_edit: " + detail)
+        e.detail = detail
+        e.stats, e.edit_stats = st, es
+        raise e
+    return st, es
+
+
+def merge_preview(inputs, tsv: str, ranks: int = 0, drop=None, keep=None, rename=None):
+    """What merge_edit's label edit would do to every label line of `inputs`, written to `tsv` (host only, utree_merge_edit_preview).
+    Returns the MergeEditStats; raises UtreeError, and no file is left then."""
+    paths = [p.encode() for p in inputs]
+    arr = (C.c_char_p * max(len(paths), 1))(*paths)
+    ed, _alive = _merge_edit_struct(ranks, drop, keep, rename, ())
+    es = _lib.MergeEditStats()
+    L = _lib.load()
+    code = L.utree_merge_edit_preview(arr, len(paths), C.byref(ed), tsv.encode(), C.byref(es))
+    if code != _lib.OK:
+        detail = (L.utree_last_hip_error() or b"").decode(errors="replace")
+        e = _lib.UtreeError(code, "merge_preview: " + detail)
+        e.detail = detail
+        raise e
+    return es
+
+
 def merge_probe(path: str):
     """How utree_merge_files reads one input (host only): the MergeInput (W, I, is_ctr, n_nodes, n_labels); raises UtreeError."""
     info = _lib.MergeInput()
