@@ -985,6 +985,89 @@ int utree_merge_files_edit(const char *const *in_paths, int n_in, const char *ub
 int utree_merge_edit_preview(const char *const *in_paths, int n_in, const utree_merge_edit *edit, const char *tsv_path,
                              utree_merge_edit_stats *st);
 
+/* ------------------------------------------------------------------------------------------------
+ * Database COMPARE (`utree-compare`): what a merge, an edit, a compression or a rebuild did to the k-mers, taxon by taxon.
+ *
+ * utree_compare_files(a_path, b_path, report_path, moves_path, device, stats) compares database A ("old") with database B
+ * ("new") and changes neither.  The inputs are `.ubt` or `.ctr` files in any mix, read exactly as utree_merge_files reads its
+ * inputs -- the same layouts told apart by structure, label lines that repeat a text read as the loader reads them, and the
+ * same refusals with the same codes (different W or W outside {4, 8, 16}: UTREE_E_UNSUPPORTED; words not strictly ascending or an
+ * index without a label line: UTREE_E_FORMAT; a bin table that is not non-decreasing or the first-bin quirk:
+ * UTREE_E_UNSUPPORTED).  I may differ between A and B.
+ *
+ * A word's LABEL is the TEXT of the label its node carries.  Index numbering, index width, file layout, the counts stated in
+ * the tail and label lines no node carries are not compared.  Every word of A or B falls into exactly one class:
+ *     same      in both, equal label text            only_a    in A only
+ *     changed   in both, different label text        only_b    in B only
+ * Per label text t there are seven figures: a (words of A labelled t), b (words of B labelled t), same, only_a, only_b, left
+ * (labelled t in A and something else in B) and arrived (labelled t in B and something else in A).  For every t
+ *     a = same + only_a + left,     b = same + only_b + arrived,     and over all t     sum(left) = sum(arrived) = changed.
+ * A MOVE is a pair (label in A, label in B) of a changed word, with the number of words that made it; per `from` text the moves
+ * sum to its left, per `to` text to its arrived, and all of them to changed.  Its kind is `lifted` when from begins with to
+ * followed by ';' (a fold moved the k-mer to an ancestor), `lowered` for the reverse, `moved` otherwise.
+ * IDENTICAL means changed == only_a == only_b == 0.
+ *
+ * report_path (all fields TAB-separated, lines end in '\n'):
+ *     # a <path> .ubt|.ctr <W> <I> <nodes> <labels>                  labels: distinct label texts its nodes carry
+ *     # b <path> .ubt|.ctr <W> <I> <nodes> <labels>
+ *     # words <union> both <n> same <n> changed <n> only_a <n> only_b <n>
+ *     # taxon a b same only_a only_b left arrived clade_a clade_b
+ *     <taxon> <a> <b> <same> <only_a> <only_b> <left> <arrived> <clade_a> <clade_b>
+ * with one row per label text with a + b > 0 and one per ';'-prefix of such a text, in unsigned bytewise order (the shorter
+ * first on a tie).  A row for a pure prefix has zero own figures; clade_a / clade_b sum a / b over every text that equals the
+ * row's taxon or begins with it followed by ';' (the profile's clade rule, the merge edit's clade match).
+ * moves_path (NULL: not written): the line `# from \t to \t kmers \t kind`, then one line per distinct move, ordered bytewise
+ * by from, then by to.
+ *
+ * What it is NOT.  (1) Words are compared as stored: a database built from the other strand shares nothing with this one.
+ * (2) Two databases built at different compression levels hold different samples of their k-mers and differ in most words.
+ * (3) A k-mer that B's build dropped as BAD has left no trace in B: it shows as only_a, indistinguishable from one that was
+ * subtracted.
+ *
+ * UTREE_E_ARG (a NULL a_path, b_path, report_path or stats) is returned before a file is opened or the device is touched.  A
+ * failed call leaves neither output file behind; utree_last_hip_error has the detail.  The nodes go through `device` in the
+ * merge's passes (n_passes): contiguous ranges of the words' top 24 bits, sized from its free memory.
+ *
+ * utree_compare_write (host only) is the writer of both files.  It takes the inputs' descriptions, n label texts with their five
+ * counted figures (a and b follow from the invariants; entries of equal text are added up; an entry without a word makes no
+ * row) and n_moves moves between entries (moves of equal text pairs are added up).  UTREE_E_ARG, and no file: a NULL
+ * argument other than moves_path and stats, a move that names no entry or whose texts are equal, or moves that do not sum to
+ * their entries' left and arrived.  stats (or NULL) gets everything but n_passes and seconds.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint64_t a, b;               /* nodes of A, nodes of B                                                   */
+    uint64_t same, only_a, only_b, left, arrived;   /* summed over all label texts; left == arrived == changed */
+    uint64_t words, both;        /* distinct words of A and B together; words in both = same + changed       */
+    uint64_t a_labels, b_labels; /* distinct label texts that nodes of A / of B carry                         */
+    uint64_t n_moves;            /* distinct (label in A, label in B) pairs among the changed words           */
+    uint32_t W, n_passes;
+    uint32_t identical;          /* 1: changed == only_a == only_b == 0                                       */
+    uint32_t pad;
+    double   seconds;
+} utree_compare_stats;           /* 120 bytes */
+
+int utree_compare_files(const char *a_path, const char *b_path, const char *report_path, const char *moves_path, int device,
+                        utree_compare_stats *stats);
+
+typedef struct {
+    const char *path;            /* as the report's `# a` / `# b` line names it */
+    uint32_t is_ctr, W, I, pad;
+} utree_compare_input;
+
+typedef struct {
+    const char *text; uint32_t len, pad;
+    uint64_t same, only_a, only_b, left, arrived;
+} utree_compare_entry;
+
+typedef struct {
+    uint32_t from, to;           /* indices into the entries */
+    uint64_t kmers;
+} utree_compare_move;
+
+int utree_compare_write(const utree_compare_input *a, const utree_compare_input *b, const utree_compare_entry *e, size_t n,
+                        const utree_compare_move *m, size_t n_moves, const char *report_path, const char *moves_path,
+                        utree_compare_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

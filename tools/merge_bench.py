@@ -49,6 +49,30 @@ def write_ubt(path, words, ix, labels, chunk=1 << 26):
         f.write(b"".join(l + b"\t%d\n" % c for l, c in zip(labels, counts)))
 
 
+def generate(d, nodes, shared, n_labels, dev):
+    """the two input files in directory d: (their paths, their node counts)"""
+    n, n_sh = nodes, int(nodes * shared)
+    own_a = sorted_unique_words(n, 1, dev)
+    own_b = sorted_unique_words(n - n_sh, 2, dev)
+    pick = torch.randperm(n, device=dev, generator=torch.Generator(device=dev).manual_seed(3))[:n_sh]
+    words_b = torch.unique(torch.cat([own_b, own_a[pick]]))       # a word both generators drew (about n^2 / 2^63 of them) counts as shared
+    del own_b, pick
+    labels = [[b"k__Bac;p__P%d;c__C%d;o__O%d;f__F%d;g__G%d;s__S%d_%s" % (j % 7, j % 31, j % 101, j % 499, j % 997, j, t) for j in range(n_labels)]
+              for t in (b"a", b"b")]
+    g = torch.Generator(device=dev).manual_seed(4)
+    paths = []
+    for k, w in enumerate((own_a, words_b)):
+        ix = torch.randint(0, n_labels, (len(w),), generator=g, device=dev, dtype=torch.int16)
+        p = os.path.join(d, "in%d.ubt" % k)
+        write_ubt(p, w, ix, labels[k])
+        paths.append(p)
+        del ix
+    n_in = [len(own_a), len(words_b)]
+    del own_a, words_b
+    torch.cuda.empty_cache()
+    return paths, n_in
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=600_000_000)
@@ -62,25 +86,7 @@ def main():
     os.makedirs(d, exist_ok=True)
     t0 = time.time()
     try:
-        n, n_sh = a.nodes, int(a.nodes * a.shared)
-        own_a = sorted_unique_words(n, 1, dev)
-        own_b = sorted_unique_words(n - n_sh, 2, dev)
-        pick = torch.randperm(n, device=dev, generator=torch.Generator(device=dev).manual_seed(3))[:n_sh]
-        words_b = torch.unique(torch.cat([own_b, own_a[pick]]))       # a word both generators drew (about n^2 / 2^63 of them) counts as shared
-        del own_b, pick
-        labels = [[b"k__Bac;p__P%d;c__C%d;o__O%d;f__F%d;g__G%d;s__S%d_%s" % (j % 7, j % 31, j % 101, j % 499, j % 997, j, t) for j in range(a.labels)]
-                  for t in (b"a", b"b")]
-        g = torch.Generator(device=dev).manual_seed(4)
-        paths = []
-        for k, w in enumerate((own_a, words_b)):
-            ix = torch.randint(0, a.labels, (len(w),), generator=g, device=dev, dtype=torch.int16)
-            p = os.path.join(d, "in%d.ubt" % k)
-            write_ubt(p, w, ix, labels[k])
-            paths.append(p)
-            del ix
-        n_in = [len(own_a), len(words_b)]
-        del own_a, words_b
-        torch.cuda.empty_cache()
+        paths, n_in = generate(d, a.nodes, a.shared, a.labels, dev)
         t_gen = time.time() - t0
         out, ctr = os.path.join(d, "merged.ubt"), os.path.join(d, "merged.ctr")
         st = search.merge(paths, out)

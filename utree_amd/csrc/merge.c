@@ -3,7 +3,8 @@
  * numbering of labels in the order the imagined build creates them, and the `.ubt` written (UT_writeTreeBinary, itree.c:1317-1343).
  * The node work is in merge_kernels.hip; include/utree_amd.h states what a merge is.  utree_merge_files_edit is the same call with an edit:
  * each label line goes through label_edit.c on its way into the universe, MINUS inputs are further slices of every pass, and
- * utree_merge_edit_preview shows what the label edit would do without a device.
+ * utree_merge_edit_preview shows what the label edit would do without a device.  The input reader, the pass plan and the slice layout are
+ * shared with compare.c (merge_input.h).
  */
 #define _FILE_OFFSET_BITS 64
 #define _GNU_SOURCE
@@ -16,25 +17,12 @@
 #include <unistd.h>
 #include "utree_internal.h"
 #include "dev_image.h"
-#include "merge_gpu.h"
-#include "label_edit.h"
-#include "strtab.h"
+#include "merge_input.h"
 
 #define NPREFIX (1u << 24)
+#define fail_text utree_merge_fail_text          /* shared with compare.c (merge_input.h) */
 
-typedef struct {
-    const char *path;
-    int fd;
-    const uint8_t *map; uint64_t size;
-    int is_ctr;
-    uint32_t W, I, rec, binw;
-    uint64_t n, rec_off, tail_off;
-    uint64_t *bins;                  /* .ctr: NPREFIX + 1 bin starts */
-    uint32_t *u_of_ix; uint32_t n_lines;       /* distinct label texts in order of first appearance (the loader's numbering) -> universe id */
-    uint64_t g0;                     /* nodes of the inputs in front */
-} merge_in;
-
-static int fail_text(int rc, const char *fmt, const char *path, const char *more) {
+int utree_merge_fail_text(int rc, const char *fmt, const char *path, const char *more) {
     char msg[512];
     snprintf(msg, sizeof msg, fmt, path, more);
     utree_set_error_text(msg);
@@ -62,16 +50,13 @@ static int tail_ok(const uint8_t *m, uint64_t size, uint64_t off, uint64_t n) {
     return sum == n;
 }
 
-static void close_input(merge_in *in) {
+void utree_merge_input_close(merge_in *in) {
     if (in->map && in->map != MAP_FAILED) munmap((void *)in->map, in->size ? in->size : 1);
     if (in->fd >= 0) close(in->fd);
     free(in->bins); free(in->u_of_ix);
 }
 
-/* header, layout, bin table, label lines -> universe.  R (or NULL): each distinct label text goes through the label edit; its edited text
- * enters the universe in its place, a dropped one maps to UTK_MERGE_DROP; es (or NULL) counts what the edit did, tsv (or NULL) gets the
- * preview's line per text.  minus: a MINUS input gives words only, its label lines are not read. */
-static int open_input(merge_in *in, const char *path, label_universe *L, le_rules *R, utree_merge_edit_stats *es, int minus, FILE *tsv) {
+int utree_merge_input_open(merge_in *in, const char *path, label_universe *L, le_rules *R, utree_merge_edit_stats *es, int minus, FILE *tsv) {
     in->path = path;
     in->fd = open(path, O_RDONLY);
     if (in->fd < 0) return fail_text(UTREE_E_IO, "%s: cannot open%s", path, "");
@@ -173,10 +158,10 @@ int utree_merge_probe(const char *path, utree_merge_input *info) {
     merge_in in; memset(&in, 0, sizeof in);
     in.fd = -1;
     label_universe L; memset(&L, 0, sizeof L);
-    const int rc = open_input(&in, path, &L, NULL, NULL, 0, NULL);
+    const int rc = utree_merge_input_open(&in, path, &L, NULL, NULL, 0, NULL);
     memset(info, 0, sizeof *info);
     if (!rc) { info->W = in.W; info->I = in.I; info->is_ctr = (uint32_t)in.is_ctr; info->n_nodes = in.n; info->n_labels = in.n_lines; }
-    close_input(&in);
+    utree_merge_input_close(&in);
     universe_free(&L);
     return rc;
 }
@@ -207,6 +192,72 @@ static uint64_t total_below(const merge_in *ins, int n_in, uint32_t P) {
     uint64_t t = 0;
     for (int i = 0; i < n_in; ++i) t += count_below(&ins[i], P);
     return t;
+}
+
+int utree_merge_plan(const merge_in *ins, int n_all, uint64_t n_read, uint64_t limit, const char *name, uint32_t **bounds_out, uint32_t *n_pass_out,
+                     uint64_t *cap_nodes_out, uint64_t *cap_raw_out) {
+    uint32_t *bounds = NULL, n_pass = 0, bounds_cap = 0;
+    uint64_t cap_nodes = 0, cap_raw = 0, want = limit;
+    const char *e = getenv("UTREE_TEST_MERGE_PASS_NODES");                                /* test hook: small inputs in many passes */
+    if (e && atoll(e) > 0 && (uint64_t)atoll(e) < want) want = (uint64_t)atoll(e);
+    uint32_t P0 = 0;
+    uint64_t below0 = 0;
+    while (below0 < n_read) {
+        uint32_t a = P0 + 1, b = NPREFIX;                                                 /* the largest P1 in [a, b] with at most `want` nodes in [P0, P1); a itself if none */
+        if (total_below(ins, n_all, b) - below0 <= want) a = b;
+        else while (a < b) {
+            const uint32_t m = a + ((b - a + 1) >> 1);
+            if (total_below(ins, n_all, m) - below0 <= want) a = m; else b = m - 1;
+        }
+        if (total_below(ins, n_all, a) == below0) ++a;                                     /* nothing below the prefix that alone exceeds `want`: no empty pass, take that prefix */
+        const uint64_t below1 = total_below(ins, n_all, a);
+        if (below1 - below0 > limit) { free(bounds); return fail_text(UTREE_E_NOMEM, "%s: the nodes that share one 24-bit prefix do not fit the device's free memory%s", name, ""); }
+        if (n_pass + 2 > bounds_cap) {
+            bounds_cap = bounds_cap ? bounds_cap * 2 : 64;
+            uint32_t *nb = (uint32_t *)realloc(bounds, 4ull * bounds_cap);
+            if (!nb) { free(bounds); return UTREE_E_NOMEM; }
+            bounds = nb;
+        }
+        if (!n_pass) bounds[0] = 0;
+        bounds[++n_pass] = a;
+        if (below1 - below0 > cap_nodes) cap_nodes = below1 - below0;
+        uint64_t raw = 0;
+        for (int i = 0; i < n_all; ++i) raw += ((count_below(&ins[i], a) - count_below(&ins[i], P0)) * ins[i].rec + 255) & ~255ull;
+        if (raw > cap_raw) cap_raw = raw;
+        P0 = a; below0 = below1;
+    }
+    *bounds_out = bounds; *n_pass_out = n_pass; *cap_nodes_out = cap_nodes; *cap_raw_out = cap_raw;
+    return UTREE_OK;
+}
+
+void utree_merge_slices(const merge_in *ins, int n_all, int n_minus, const uint32_t *bounds, uint32_t p, utk_merge_slice *sl) {
+    uint64_t raw_off = 0;
+    for (int i = 0; i < n_all; ++i) {
+        const merge_in *in = &ins[i];
+        utk_merge_slice *s = &sl[i];
+        memset(s, 0, sizeof *s);
+        const uint64_t first = count_below(in, bounds[p]), end = count_below(in, bounds[p + 1]);
+        s->input = (uint32_t)i; s->is_ctr = (uint32_t)in->is_ctr; s->I = in->I; s->minus = i < n_minus;
+        s->n = end - first; s->raw_off = raw_off; s->g0 = in->g0 + first; s->first = first;
+        s->fd = in->fd; s->file_off = in->rec_off + first * in->rec;
+        if (!s->n) continue;
+        raw_off += (s->n * in->rec + 255) & ~255ull;
+        if (in->is_ctr) {
+            s->p_lo = bounds[p]; s->n_bins = bounds[p + 1] - bounds[p]; s->h_bins = in->bins + bounds[p];
+            if (first) {                                                                   /* the node in front lies in the last non-empty bin below */
+                uint32_t q = bounds[p];
+                while (q && in->bins[q] >= first) --q;                                     /* bins[q] < first <= bins[q + 1] */
+                const uint8_t *r = in->map + in->rec_off + (first - 1) * in->rec;
+                uint64_t suf_lo = 0, suf_hi = 0;
+                memcpy(&suf_lo, r, in->W == 16 ? 8 : in->W - 3);
+                if (in->W == 16) memcpy(&suf_hi, r + 8, 5);
+                s->has_prev = 1;
+                if (in->W == 4) s->prev_lo = ((uint64_t)q << 8) | suf_lo;
+                else if (in->W == 8) s->prev_lo = ((uint64_t)q << 40) | suf_lo;
+                else { s->prev_lo = suf_lo; s->prev_hi = ((uint64_t)q << 40) | suf_hi; }
+            }
+        } else if (first) { s->has_prev = 1; rec_word(in, first - 1, &s->prev_hi, &s->prev_lo); }
+    }
 }
 
 typedef struct { uint64_t time; uint32_t u; } event;
@@ -258,7 +309,7 @@ int utree_merge_edit_preview(const char *const *in_paths, int n_in, const utree_
         FILE *mem = open_memstream(&lines, &lines_n);                                      /* the input's line comes first and states how many follow */
         if (!mem) rc = UTREE_E_NOMEM;
         else {
-            rc = open_input(&in, in_paths[i], &L, R, &es, 0, mem);
+            rc = utree_merge_input_open(&in, in_paths[i], &L, R, &es, 0, mem);
             if (fclose(mem) && !rc) rc = UTREE_E_NOMEM;
         }
         if (!rc) {
@@ -266,7 +317,7 @@ int utree_merge_edit_preview(const char *const *in_paths, int n_in, const utree_
             fwrite(lines, 1, lines_n, out);
         }
         free(lines);
-        close_input(&in);
+        utree_merge_input_close(&in);
     }
     if (!rc) {
         es.n_rules_unmatched = le_unmatched(R);
@@ -301,7 +352,7 @@ int utree_merge_files_edit(const char *const *in_paths, int n_in, const char *ub
     merge_in *ins = (merge_in *)calloc((size_t)n_all, sizeof(merge_in));
     le_rules *R = NULL;
     label_universe L; memset(&L, 0, sizeof L);
-    uint32_t *bounds = NULL, n_pass = 0, bounds_cap = 0, *ix_of_u = NULL, *u_of_ix = NULL, n_labels = 0;
+    uint32_t *bounds = NULL, n_pass = 0, *ix_of_u = NULL, *u_of_ix = NULL, n_labels = 0;
     uint32_t **maps = NULL, *n_lines = NULL;
     uint64_t *first_time = NULL, *per_label = NULL;
     utk_merge_slice *sl = NULL;
@@ -317,7 +368,7 @@ int utree_merge_files_edit(const char *const *in_paths, int n_in, const char *ub
     for (int o = 0; o < n_all; ++o) {
         const int minus = o >= n_in, i = minus ? o - n_in : n_minus + o;
         const char *path = minus ? edit->minus_paths[o - n_in] : in_paths[o];
-        rc = open_input(&ins[i], path, &L, R, edit ? &es : NULL, minus, NULL);
+        rc = utree_merge_input_open(&ins[i], path, &L, R, edit ? &es : NULL, minus, NULL);
         if (rc) goto done;
         if (o && ins[i].W != W) { rc = fail_text(UTREE_E_UNSUPPORTED, "%s: its word size differs from the first input's%s", path, ""); goto done; }
         W = ins[i].W;
@@ -336,37 +387,8 @@ int utree_merge_files_edit(const char *const *in_paths, int n_in, const char *ub
     uint64_t limit = 0, cap_nodes = 0, cap_raw = 0;
     rc = utk_merge_limit(device, W, rec_max, &limit);
     if (rc) goto done;
-    {
-        uint64_t want = limit;
-        const char *e = getenv("UTREE_TEST_MERGE_PASS_NODES");                            /* test hook: small inputs in many passes */
-        if (e && atoll(e) > 0 && (uint64_t)atoll(e) < want) want = (uint64_t)atoll(e);
-        uint32_t P0 = 0;
-        uint64_t below0 = 0;
-        while (below0 < n_read) {
-            uint32_t a = P0 + 1, b = NPREFIX;                                             /* the largest P1 in [a, b] with at most `want` nodes in [P0, P1); a itself if none */
-            if (total_below(ins, n_all, b) - below0 <= want) a = b;
-            else while (a < b) {
-                const uint32_t m = a + ((b - a + 1) >> 1);
-                if (total_below(ins, n_all, m) - below0 <= want) a = m; else b = m - 1;
-            }
-            if (total_below(ins, n_all, a) == below0) ++a;                                 /* nothing below the prefix that alone exceeds `want`: no empty pass, take that prefix */
-            const uint64_t below1 = total_below(ins, n_all, a);
-            if (below1 - below0 > limit) { rc = fail_text(UTREE_E_NOMEM, "%s: the nodes that share one 24-bit prefix do not fit the device's free memory%s", ubt_path, ""); goto done; }
-            if (n_pass + 2 > bounds_cap) {
-                bounds_cap = bounds_cap ? bounds_cap * 2 : 64;
-                uint32_t *nb = (uint32_t *)realloc(bounds, 4ull * bounds_cap);
-                if (!nb) { rc = UTREE_E_NOMEM; goto done; }
-                bounds = nb;
-            }
-            if (!n_pass) bounds[0] = 0;
-            bounds[++n_pass] = a;
-            if (below1 - below0 > cap_nodes) cap_nodes = below1 - below0;
-            uint64_t raw = 0;
-            for (int i = 0; i < n_all; ++i) raw += ((count_below(&ins[i], a) - count_below(&ins[i], P0)) * ins[i].rec + 255) & ~255ull;
-            if (raw > cap_raw) cap_raw = raw;
-            P0 = a; below0 = below1;
-        }
-    }
+    rc = utree_merge_plan(ins, n_all, n_read, limit, ubt_path, &bounds, &n_pass, &cap_nodes, &cap_raw);
+    if (rc) goto done;
     st.n_passes = n_pass;
     /* ---- device ---- */
     maps = (uint32_t **)calloc((size_t)n_all, sizeof *maps); n_lines = (uint32_t *)calloc((size_t)n_all, 4);
@@ -377,7 +399,7 @@ int utree_merge_files_edit(const char *const *in_paths, int n_in, const char *ub
     for (int i = 0; i < n_all; ++i) { maps[i] = ins[i].u_of_ix; n_lines[i] = ins[i].n_lines; }
     {
         utk_merge_cfg cfg = {L.U.blob, L.U.blob_n, L.U.off, L.U.n, L.trunc_off, L.trunc_ids, L.n_trunc, (uint32_t)n_all,
-                             (const uint32_t *const *)maps, n_lines, W, I_out, gg, device, any_ctr, n_minus > 0, cap_nodes, cap_raw};
+                             (const uint32_t *const *)maps, n_lines, W, I_out, gg, device, any_ctr, n_minus > 0, cap_nodes, cap_raw, 0};
         rc = utk_merge_open(&cfg, &D);
         if (rc) goto done;
     }
@@ -385,33 +407,7 @@ int utree_merge_files_edit(const char *const *in_paths, int n_in, const char *ub
      * first sweep replays all passes for the events alone and a second one replays them again and writes. */
     for (int sweep = 0; sweep < (n_pass > 1 ? 2 : 1); ++sweep) {
         for (uint32_t p = 0; p < n_pass; ++p) {
-            uint64_t raw_off = 0;
-            for (int i = 0; i < n_all; ++i) {                                              /* MINUS slices in front: the stable sort keeps a MINUS record at the head of its run */
-                const merge_in *in = &ins[i];
-                utk_merge_slice *s = &sl[i];
-                memset(s, 0, sizeof *s);
-                const uint64_t first = count_below(in, bounds[p]), end = count_below(in, bounds[p + 1]);
-                s->input = (uint32_t)i; s->is_ctr = (uint32_t)in->is_ctr; s->I = in->I; s->minus = i < n_minus;
-                s->n = end - first; s->raw_off = raw_off; s->g0 = in->g0 + first; s->first = first;
-                s->fd = in->fd; s->file_off = in->rec_off + first * in->rec;
-                if (!s->n) continue;
-                raw_off += (s->n * in->rec + 255) & ~255ull;
-                if (in->is_ctr) {
-                    s->p_lo = bounds[p]; s->n_bins = bounds[p + 1] - bounds[p]; s->h_bins = in->bins + bounds[p];
-                    if (first) {                                                           /* the node in front lies in the last non-empty bin below */
-                        uint32_t q = bounds[p];
-                        while (q && in->bins[q] >= first) --q;                             /* bins[q] < first <= bins[q + 1] */
-                        const uint8_t *r = in->map + in->rec_off + (first - 1) * in->rec;
-                        uint64_t suf_lo = 0, suf_hi = 0;
-                        memcpy(&suf_lo, r, in->W == 16 ? 8 : in->W - 3);
-                        if (in->W == 16) memcpy(&suf_hi, r + 8, 5);
-                        s->has_prev = 1;
-                        if (in->W == 4) s->prev_lo = ((uint64_t)q << 8) | suf_lo;
-                        else if (in->W == 8) s->prev_lo = ((uint64_t)q << 40) | suf_lo;
-                        else { s->prev_lo = suf_lo; s->prev_hi = ((uint64_t)q << 40) | suf_hi; }
-                    }
-                } else if (first) { s->has_prev = 1; rec_word(in, first - 1, &s->prev_hi, &s->prev_lo); }
-            }
+            utree_merge_slices(ins, n_all, n_minus, bounds, p, sl);        /* MINUS slices in front: the stable sort keeps a MINUS record at the head of its run */
             utk_merge_pass_out po;
             uint32_t io_slice = 0;
             rc = utk_merge_pass(D, sl, (uint32_t)n_all, sweep == 0, &po, &io_slice);
@@ -477,7 +473,7 @@ done:
     if (fd >= 0) close(fd);
     if (rc && created) unlink(ubt_path);                                                   /* a failed call leaves no output file behind */
     if (D) utk_merge_close(D);
-    if (ins) { for (int i = 0; i < n_all; ++i) close_input(&ins[i]); free(ins); }
+    if (ins) { for (int i = 0; i < n_all; ++i) utree_merge_input_close(&ins[i]); free(ins); }
     if (R) es.n_rules_unmatched = le_unmatched(R);
     le_free(R);
     universe_free(&L);

@@ -25,6 +25,8 @@ typedef struct {
                                                                the fold dates the labels of the records it feeds, not the decode */
     uint64_t cap_nodes;                                     /* nodes of the largest pass                                    */
     uint64_t cap_raw;                                       /* bytes of the largest pass's records as utk_merge_slice lays them out */
+    int compare;                                            /* the handle is utree_compare_files': two inputs, utk_compare_pass instead of
+                                                               utk_merge_pass, nothing is dated, numbered or emitted */
 } utk_merge_cfg;
 
 /* one contiguous stretch of one input's nodes, all of one pass's word range */
@@ -59,6 +61,19 @@ int utk_merge_set_ix(utk_merge_dev *D, const uint32_t *h_ix_of_u, uint32_t n_lab
 int utk_merge_emit(utk_merge_dev *D, int fd);                                          /* the last pass's records to fd: packing and download of a chunk overlap the write of the one before */
 int utk_merge_counts(utk_merge_dev *D, uint64_t *h_per_label);
 void utk_merge_close(utk_merge_dev *D);
+
+/* ---- utree_compare_files (compare.c): the same handle, slices, staging, decode and sort; input 0 is A, input 1 is B ---- */
+#define UTK_COMPARE_FIGURES 5        /* per universe label: same, only_a, only_b, left, arrived */
+typedef struct {
+    uint64_t n_changed;              /* words of the pass in both inputs under different labels                             */
+    uint64_t n_moves;                /* distinct (label in A, label in B) pairs among them, for utk_compare_moves            */
+    uint32_t err;                    /* as utk_merge_pass_out's                                                             */
+} utk_compare_pass_out;
+int utk_compare_limit(int device, uint32_t W, uint32_t rec_max, uint32_t n_u, uint64_t *nodes);   /* utk_merge_limit less the counters */
+/* b_g0: the event clock of B's first node (= A's nodes): what tells a lone record's input.  The counters add up over the passes. */
+int utk_compare_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, uint64_t b_g0, utk_compare_pass_out *out, uint32_t *io_slice);
+int utk_compare_moves(utk_merge_dev *D, uint64_t *h_keys, uint32_t *h_counts);          /* the last pass's n_moves pairs, key = label in A << 24 | label in B, ascending */
+int utk_compare_figures(utk_merge_dev *D, uint64_t *h_fig);                            /* [UTK_COMPARE_FIGURES][n_u] */
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,11 @@
 // out in front of the regular ones, so the stable sort leaves a MINUS record at the head of its run: such a run feeds nothing, any other
 // run folds the records that are not DROP.  With a MINUS input the records fed are known only after the sort, so merge_fold_k dates the
 // labels then (has_minus); without one decode_k dates them as before.
+//
+// utree_compare_files (`utree-compare`) shares the front half -- staging, decode_k, the sort: decode_sort -- with A and B as the two inputs:
+//   compare_runs_k                a run is one record or two, A's first: its head adds to the per-label counters same / only_a / only_b /
+//                                 left / arrived (a wavefront of one counter adds once) and a changed word appends label A << 24 | label B
+//   rocprim                       radix sort of those keys, run-length encoding -> the pass's distinct moves and their counts
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -26,6 +31,7 @@
 #include <unistd.h>
 #include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_run_length_encode.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 #include "utree_internal.h"
@@ -234,6 +240,59 @@ __global__ __launch_bounds__(BLOCK) void merge_pack_k(const uint64_t *__restrict
     else if (live) atomicAdd(&per_label[ix], 1ull);
 }
 
+// ---- utree_compare_files: A's slice lies in front of B's, so after the stable sort a run is one record (a word only A or only B holds) or
+// two, A's first.  fig[c * n_u + u]: words of class c under universe label u.
+constexpr uint32_t CMP_SAME = 0, CMP_ONLY_A = 1, CMP_ONLY_B = 2, CMP_LEFT = 3, CMP_ARRIVED = 4;
+constexpr int STAT_MOVES = 5;                              // changed words of the pass = move keys appended
+static_assert(UTK_COMPARE_FIGURES == 5, "fig[] holds one row of n_u counters per class");
+
+// ++fig[slot] for every lane that is `on`: neighbours in word order mostly share a label and a class, so a wavefront of one slot adds once
+__device__ __forceinline__ void wave_add(bool on, uint32_t slot, unsigned long long *__restrict__ fig) {
+    const uint64_t m = __ballot(on);
+    if (!m) return;
+    const uint32_t lead = (uint32_t)__builtin_ctzll(m);
+    const uint32_t slot0 = (uint32_t)__shfl((int)slot, (int)lead);
+    const uint64_t same = __ballot(on && slot == slot0);
+    if (same == m) { if ((threadIdx.x & 63u) == lead) atomicAdd(&fig[slot0], (unsigned long long)__popcll(m)); }
+    else if (on) atomicAdd(&fig[slot], 1ull);
+}
+
+// The head of each run classifies it.  A record is B's when its event clock has reached b_g0, the clock of B's first node.  A changed word
+// also appends its move key (label in A << 24 | label in B) to move_keys[0 .. stats[STAT_MOVES]), a wavefront reserving its places with one
+// atomic; the order of the keys does not matter, they are sorted next.  At most n / 2 words are changed, so move_keys[n] cannot overflow.
+template <int W>
+__global__ __launch_bounds__(BLOCK) void compare_runs_k(const uint64_t *__restrict__ key_lo, const uint64_t *__restrict__ key_hi,
+                                                        const uint64_t *__restrict__ val, uint64_t n, uint64_t b_g0, uint32_t n_u,
+                                                        unsigned long long *__restrict__ fig, uint64_t *__restrict__ move_keys,
+                                                        unsigned long long *__restrict__ stats) {
+    const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t lo = j < n ? key_lo[j] : 0, hi = (W == 16 && j < n) ? key_hi[j] : 0;
+    const bool head = j < n && !(j && key_lo[j - 1] == lo && (W != 16 || key_hi[j - 1] == hi));
+    bool changed = false;
+    uint32_t slot = 0, slot2 = 0;
+    uint64_t key = 0;
+    if (head) {
+        const uint64_t v = val[j];
+        const uint32_t u = (uint32_t)(v & 0xFFFFFFu);
+        if (j + 1 < n && key_lo[j + 1] == lo && (W != 16 || key_hi[j + 1] == hi)) {
+            const uint32_t ub = (uint32_t)(val[j + 1] & 0xFFFFFFu);
+            changed = ub != u;
+            slot = (changed ? CMP_LEFT : CMP_SAME) * n_u + u;
+            slot2 = CMP_ARRIVED * n_u + ub;
+            key = ((uint64_t)u << 24) | ub;
+        } else slot = ((v >> 24) >= b_g0 ? CMP_ONLY_B : CMP_ONLY_A) * n_u + u;
+    }
+    wave_add(head, slot, fig);
+    wave_add(changed, slot2, fig);
+    const uint64_t m = __ballot(changed);
+    if (!m) return;
+    const uint32_t lane = threadIdx.x & 63u, lead = (uint32_t)__builtin_ctzll(m);
+    unsigned long long base = 0;
+    if (lane == lead) base = atomicAdd(&stats[STAT_MOVES], (unsigned long long)__popcll(m));
+    const uint32_t b_lo = (uint32_t)__shfl((int)(uint32_t)base, (int)lead), b_hi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)lead);
+    if (changed) move_keys[(((uint64_t)b_hi << 32) | b_lo) + (uint64_t)__popcll(m & ((1ull << lane) - 1ull))] = key;
+}
+
 template <typename Fn> bool dispatch_w(int W, Fn &&fn) {
     if (W == 4) fn(std::integral_constant<int, 4>{});
     else if (W == 8) fn(std::integral_constant<int, 8>{});
@@ -265,100 +324,24 @@ struct utk_merge_dev {
     uint8_t *d_out[2], *h_out[2]; uint64_t out_chunk;
     uint32_t n_labels;
     uint64_t seg_n; const uint64_t *seg_lo, *seg_hi; const uint32_t *seg_st;
+    unsigned long long *d_fig;                      // compare: [N_CMP][n_u] words per class and label, summed over the passes
+    uint64_t moves_n;                               // compare: (key, count) pairs of the last pass, keys in b[0], counts in st
 };
 
-extern "C" {
-
-int utk_merge_limit(int device, uint32_t W, uint32_t rec_max, uint64_t *nodes) {
-    int rc = UTREE_OK;
-    size_t free_b = 0, total_b = 0;
-    HK(hipSetDevice(device));
-    HK(hipMemGetInfo(&free_b, &total_b));
-    {
-        const uint64_t reserve = (uint64_t)2 << 30;                         /* universe, bin table, output chunk, rocprim's scratch */
-        uint64_t lim = (free_b > reserve ? free_b - reserve : 0) / bytes_per_node(W, rec_max);
-        if (lim > (1ull << 31) - 1) lim = (1ull << 31) - 1;                 /* rocprim sorts fewer than 2^31 items */
-        *nodes = lim;
-    }
-fail:
-    return rc;
-}
-
-void utk_merge_close(utk_merge_dev *D) {
-    if (!D) return;
-    (void)hipSetDevice(D->cfg.device);
-    (void)hipDeviceSynchronize();
-    for (int q = 0; q < 2; ++q) {
-        if (D->h_stage[q]) (void)hipHostFree(D->h_stage[q]);
-        if (D->h_out[q]) (void)hipHostFree(D->h_out[q]);
-        if (D->d_out[q]) (void)hipFree(D->d_out[q]);
-        if (D->ev[q]) (void)hipEventDestroy(D->ev[q]);
-    }
-    void *dev[] = {D->d_raw, D->b[0], D->b[1], D->b[2], D->b[3], D->b[4], D->b[5], D->b[6], D->st, D->st2, D->d_bins, D->d_ublob, D->d_uoff,
-                   D->d_toff, D->d_tids, D->d_first, D->d_stats, D->d_nsel, D->d_cnt, D->d_err, D->d_ix};
-    for (void *p : dev) if (p) (void)hipFree(p);
-    if (D->d_u_of_ix) { for (uint32_t i = 0; i < D->cfg.n_in; ++i) if (D->d_u_of_ix[i]) (void)hipFree(D->d_u_of_ix[i]); free(D->d_u_of_ix); }
-    free(D);
-}
-
-int utk_merge_open(const utk_merge_cfg *cfg, utk_merge_dev **out) {
-    int rc = UTREE_OK;
-    if (!dispatch_w((int)cfg->W, [](auto) {}) || (cfg->I_out != 2 && cfg->I_out != 4)) return UTREE_E_ARG;
-    utk_merge_dev *D = (utk_merge_dev *)calloc(1, sizeof *D);
-    if (!D) return UTREE_E_NOMEM;
-    D->cfg = *cfg;
-    D->cap = cfg->cap_nodes ? cfg->cap_nodes : 1;
-    D->out_chunk = D->cap < (16ull << 20) ? D->cap : (16ull << 20);
-    D->stage_bytes = cfg->cap_raw + 512 < (256ull << 20) ? cfg->cap_raw + 512 : (256ull << 20);
-    D->d_u_of_ix = (uint32_t **)calloc(cfg->n_in, sizeof(uint32_t *));
-    if (!D->d_u_of_ix) { rc = UTREE_E_NOMEM; goto fail; }
-    HK(hipSetDevice(cfg->device));
-    for (int q = 0; q < 2; ++q) {
-        HK(hipHostMalloc((void **)&D->h_stage[q], D->stage_bytes, hipHostMallocDefault));
-        HK(hipEventCreateWithFlags(&D->ev[q], hipEventDisableTiming));
-    }
-    HK(dmalloc(&D->d_raw, cfg->cap_raw + 512));
-    for (int q = 0; q < (cfg->W == 16 ? 7 : 4); ++q) HK(dmalloc(&D->b[q], D->cap));
-    HK(dmalloc(&D->st, D->cap)); HK(dmalloc(&D->st2, D->cap));
-    if (cfg->any_ctr) HK(dmalloc(&D->d_bins, (uint64_t)UTREE_NUMBINS + 1));
-    HK(dmalloc(&D->d_ublob, cfg->ublob_bytes + 8)); HK(dmalloc(&D->d_uoff, cfg->n_u)); HK(dmalloc(&D->d_toff, (uint64_t)cfg->n_u + 1));
-    HK(dmalloc(&D->d_tids, cfg->n_trunc)); HK(dmalloc(&D->d_first, cfg->n_u)); HK(dmalloc(&D->d_stats, N_STATS)); HK(dmalloc(&D->d_nsel, 1));
-    HK(dmalloc(&D->d_err, 1)); HK(dmalloc(&D->d_ix, cfg->n_u));
-    for (int q = 0; q < 2; ++q) {
-        HK(dmalloc(&D->d_out[q], D->out_chunk * (cfg->W + cfg->I_out)));
-        HK(hipHostMalloc((void **)&D->h_out[q], D->out_chunk * (cfg->W + cfg->I_out) + 8, hipHostMallocDefault));
-    }
-    if (cfg->ublob_bytes) HK(hipMemcpy(D->d_ublob, cfg->h_ublob, cfg->ublob_bytes, hipMemcpyHostToDevice));
-    if (cfg->n_u) {
-        HK(hipMemcpy(D->d_uoff, cfg->h_uoff, 8ull * cfg->n_u, hipMemcpyHostToDevice));
-        HK(hipMemset(D->d_first, 0xFF, 8ull * cfg->n_u));
-    }
-    HK(hipMemcpy(D->d_toff, cfg->h_trunc_off, 4ull * (cfg->n_u + 1ull), hipMemcpyHostToDevice));
-    if (cfg->n_trunc) HK(hipMemcpy(D->d_tids, cfg->h_trunc_ids, 4ull * cfg->n_trunc, hipMemcpyHostToDevice));
-    for (uint32_t i = 0; i < cfg->n_in; ++i) {
-        HK(dmalloc(&D->d_u_of_ix[i], cfg->n_lines[i]));
-        if (cfg->n_lines[i]) HK(hipMemcpy(D->d_u_of_ix[i], cfg->h_u_of_ix[i], 4ull * cfg->n_lines[i], hipMemcpyHostToDevice));
-    }
-    *out = D;
-    return UTREE_OK;
-fail:
-    utk_merge_close(D);
-    return rc;
-}
-
-int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, int count_stats, utk_merge_pass_out *out, uint32_t *io_slice) {
+// The front half of a pass, shared by the merge and the compare: every slice from its file through the two pinned staging buffers onto the
+// device, decoded in slice order, then the stable sort by word.  *n: the pass's records; *err: what decode_k found (then nothing is sorted);
+// *s_lo, *s_hi (W = 16), *s_val: the sorted words and values.  Afterwards b[0] and b[1] hold nothing that is still needed.
+static int decode_sort(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, uint64_t *n_out, uint32_t *err, uint64_t **s_lo_out,
+                       uint64_t **s_hi_out, uint64_t **s_val_out, uint32_t *io_slice) {
     int rc = UTREE_OK;
     const int W = (int)D->cfg.W;
-    const universe U = {D->d_ublob, D->d_uoff, D->d_toff, D->d_tids};
     void *tmp = nullptr;
-    size_t tb = 0, tb2 = 0;
+    size_t tb = 0;
     uint64_t n = 0;
     int turn = 0, used[2] = {0, 0};
-    unsigned long long h_stats[N_STATS] = {0}, nn = 0;
     uint32_t h_err = 0;
     uint64_t *k_lo = D->b[0], *k_val = D->b[1], *s_lo, *s_hi = nullptr, *s_val;
-    memset(out, 0, sizeof *out);
-    D->seg_n = 0;
+    *n_out = 0; *err = 0;
     HK(hipSetDevice(D->cfg.device));
     for (uint32_t s = 0; s < n_sl; ++s) {
         const uint64_t rec = (sl[s].is_ctr ? D->cfg.W - 3 : D->cfg.W) + sl[s].I;
@@ -387,7 +370,7 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
             if (sl[s].is_ctr) HK(hipMemcpy(D->d_bins, sl[s].h_bins, 8ull * (sl[s].n_bins + 1ull), hipMemcpyHostToDevice));
             const slice_dev S = {(const uint32_t *)(D->d_raw + sl[s].raw_off), sl[s].n, sl[s].g0, D->d_u_of_ix[sl[s].input], D->cfg.n_lines[sl[s].input],
                                  sl[s].I, sl[s].has_prev, sl[s].prev_hi, sl[s].prev_lo, D->d_bins, sl[s].p_lo, sl[s].n_bins, sl[s].first,
-                                 sl[s].minus ? ROLE_MINUS : D->cfg.has_minus ? ROLE_REGULAR : ROLE_DATES};
+                                 sl[s].minus ? ROLE_MINUS : (D->cfg.has_minus || D->cfg.compare) ? ROLE_REGULAR : ROLE_DATES};
             const unsigned gb = (unsigned)((sl[s].n + BLOCK - 1) / BLOCK);
             const bool ctr = sl[s].is_ctr != 0;
             dispatch_w(W, [&](auto w) {
@@ -401,8 +384,9 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
         }
     }
     HK(hipMemcpy(&h_err, D->d_err, 4, hipMemcpyDeviceToHost));
-    out->err = h_err;
-    if (h_err) return UTREE_OK;                                             /* the caller names the error; indices were not looked up */
+    *err = h_err;
+    *n_out = n;
+    if (h_err) return UTREE_OK;
     {
         const unsigned gb = (unsigned)((n + BLOCK - 1) / BLOCK);
         // ---- stable sort by word (W = 4: only the low 32 bits carry the 16-mer) ----
@@ -428,6 +412,132 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
         HK(hipGetLastError());
         HK(hipDeviceSynchronize());
         HK(hipFree(tmp)); tmp = nullptr;
+        *s_lo_out = s_lo; *s_hi_out = s_hi; *s_val_out = s_val;
+    }
+fail:
+    if (rc) (void)hipDeviceSynchronize();
+    if (tmp) (void)hipFree(tmp);
+    return rc;
+}
+
+extern "C" {
+
+int utk_merge_limit(int device, uint32_t W, uint32_t rec_max, uint64_t *nodes) {
+    int rc = UTREE_OK;
+    size_t free_b = 0, total_b = 0;
+    HK(hipSetDevice(device));
+    HK(hipMemGetInfo(&free_b, &total_b));
+    {
+        const uint64_t reserve = (uint64_t)2 << 30;                         /* universe, bin table, output chunk, rocprim's scratch */
+        uint64_t lim = (free_b > reserve ? free_b - reserve : 0) / bytes_per_node(W, rec_max);
+        if (lim > (1ull << 31) - 1) lim = (1ull << 31) - 1;                 /* rocprim sorts fewer than 2^31 items */
+        *nodes = lim;
+    }
+fail:
+    return rc;
+}
+
+/* The compare's pass holds what the merge's holds, less the second state array and the output chunks.  After the sort by word its move keys
+ * (at most half the pass's nodes, 8 bytes each) are sorted and run-length-encoded in place of the two buffers the unsorted records came in,
+ * and rocprim's scratch for that (a second copy of the keys) takes the room the first sort's scratch has given back: bytes_per_node covers
+ * it.  What comes on top is the five counters per universe label. */
+int utk_compare_limit(int device, uint32_t W, uint32_t rec_max, uint32_t n_u, uint64_t *nodes) {
+    int rc = UTREE_OK;
+    size_t free_b = 0, total_b = 0;
+    HK(hipSetDevice(device));
+    HK(hipMemGetInfo(&free_b, &total_b));
+    {
+        const uint64_t reserve = ((uint64_t)2 << 30) + 8ull * UTK_COMPARE_FIGURES * n_u;
+        uint64_t lim = (free_b > reserve ? free_b - reserve : 0) / bytes_per_node(W, rec_max);
+        if (lim > (1ull << 31) - 1) lim = (1ull << 31) - 1;                 /* rocprim sorts fewer than 2^31 items */
+        *nodes = lim;
+    }
+fail:
+    return rc;
+}
+
+void utk_merge_close(utk_merge_dev *D) {
+    if (!D) return;
+    (void)hipSetDevice(D->cfg.device);
+    (void)hipDeviceSynchronize();
+    for (int q = 0; q < 2; ++q) {
+        if (D->h_stage[q]) (void)hipHostFree(D->h_stage[q]);
+        if (D->h_out[q]) (void)hipHostFree(D->h_out[q]);
+        if (D->d_out[q]) (void)hipFree(D->d_out[q]);
+        if (D->ev[q]) (void)hipEventDestroy(D->ev[q]);
+    }
+    void *dev[] = {D->d_raw, D->b[0], D->b[1], D->b[2], D->b[3], D->b[4], D->b[5], D->b[6], D->st, D->st2, D->d_bins, D->d_ublob, D->d_uoff,
+                   D->d_toff, D->d_tids, D->d_first, D->d_stats, D->d_nsel, D->d_cnt, D->d_err, D->d_ix, D->d_fig};
+    for (void *p : dev) if (p) (void)hipFree(p);
+    if (D->d_u_of_ix) { for (uint32_t i = 0; i < D->cfg.n_in; ++i) if (D->d_u_of_ix[i]) (void)hipFree(D->d_u_of_ix[i]); free(D->d_u_of_ix); }
+    free(D);
+}
+
+int utk_merge_open(const utk_merge_cfg *cfg, utk_merge_dev **out) {
+    int rc = UTREE_OK;
+    if (!dispatch_w((int)cfg->W, [](auto) {}) || (cfg->I_out != 2 && cfg->I_out != 4)) return UTREE_E_ARG;
+    utk_merge_dev *D = (utk_merge_dev *)calloc(1, sizeof *D);
+    if (!D) return UTREE_E_NOMEM;
+    D->cfg = *cfg;
+    D->cap = cfg->cap_nodes ? cfg->cap_nodes : 1;
+    D->out_chunk = D->cap < (16ull << 20) ? D->cap : (16ull << 20);
+    D->stage_bytes = cfg->cap_raw + 512 < (256ull << 20) ? cfg->cap_raw + 512 : (256ull << 20);
+    D->d_u_of_ix = (uint32_t **)calloc(cfg->n_in, sizeof(uint32_t *));
+    if (!D->d_u_of_ix) { rc = UTREE_E_NOMEM; goto fail; }
+    HK(hipSetDevice(cfg->device));
+    for (int q = 0; q < 2; ++q) {
+        HK(hipHostMalloc((void **)&D->h_stage[q], D->stage_bytes, hipHostMallocDefault));
+        HK(hipEventCreateWithFlags(&D->ev[q], hipEventDisableTiming));
+    }
+    HK(dmalloc(&D->d_raw, cfg->cap_raw + 512));
+    for (int q = 0; q < (cfg->W == 16 ? 7 : 4); ++q) HK(dmalloc(&D->b[q], D->cap));
+    HK(dmalloc(&D->st, D->cap));
+    if (!cfg->compare) HK(dmalloc(&D->st2, D->cap));
+    if (cfg->any_ctr) HK(dmalloc(&D->d_bins, (uint64_t)UTREE_NUMBINS + 1));
+    HK(dmalloc(&D->d_ublob, cfg->ublob_bytes + 8)); HK(dmalloc(&D->d_uoff, cfg->n_u)); HK(dmalloc(&D->d_toff, (uint64_t)cfg->n_u + 1));
+    HK(dmalloc(&D->d_tids, cfg->n_trunc)); HK(dmalloc(&D->d_first, cfg->n_u)); HK(dmalloc(&D->d_stats, N_STATS)); HK(dmalloc(&D->d_nsel, 1));
+    HK(dmalloc(&D->d_err, 1)); HK(dmalloc(&D->d_ix, cfg->n_u));
+    if (cfg->compare) {
+        HK(dmalloc(&D->d_fig, (uint64_t)UTK_COMPARE_FIGURES * cfg->n_u));
+        HK(hipMemset(D->d_fig, 0, 8ull * UTK_COMPARE_FIGURES * (cfg->n_u ? cfg->n_u : 1)));
+    }
+    for (int q = 0; q < (cfg->compare ? 0 : 2); ++q) {                      /* a compare writes no nodes */
+        HK(dmalloc(&D->d_out[q], D->out_chunk * (cfg->W + cfg->I_out)));
+        HK(hipHostMalloc((void **)&D->h_out[q], D->out_chunk * (cfg->W + cfg->I_out) + 8, hipHostMallocDefault));
+    }
+    if (cfg->ublob_bytes) HK(hipMemcpy(D->d_ublob, cfg->h_ublob, cfg->ublob_bytes, hipMemcpyHostToDevice));
+    if (cfg->n_u) {
+        HK(hipMemcpy(D->d_uoff, cfg->h_uoff, 8ull * cfg->n_u, hipMemcpyHostToDevice));
+        HK(hipMemset(D->d_first, 0xFF, 8ull * cfg->n_u));
+    }
+    HK(hipMemcpy(D->d_toff, cfg->h_trunc_off, 4ull * (cfg->n_u + 1ull), hipMemcpyHostToDevice));
+    if (cfg->n_trunc) HK(hipMemcpy(D->d_tids, cfg->h_trunc_ids, 4ull * cfg->n_trunc, hipMemcpyHostToDevice));
+    for (uint32_t i = 0; i < cfg->n_in; ++i) {
+        HK(dmalloc(&D->d_u_of_ix[i], cfg->n_lines[i]));
+        if (cfg->n_lines[i]) HK(hipMemcpy(D->d_u_of_ix[i], cfg->h_u_of_ix[i], 4ull * cfg->n_lines[i], hipMemcpyHostToDevice));
+    }
+    *out = D;
+    return UTREE_OK;
+fail:
+    utk_merge_close(D);
+    return rc;
+}
+
+int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, int count_stats, utk_merge_pass_out *out, uint32_t *io_slice) {
+    int rc = UTREE_OK;
+    const int W = (int)D->cfg.W;
+    const universe U = {D->d_ublob, D->d_uoff, D->d_toff, D->d_tids};
+    void *tmp = nullptr;
+    size_t tb = 0, tb2 = 0;
+    uint64_t n = 0;
+    unsigned long long h_stats[N_STATS] = {0}, nn = 0;
+    uint64_t *s_lo = nullptr, *s_hi = nullptr, *s_val = nullptr;
+    memset(out, 0, sizeof *out);
+    D->seg_n = 0;
+    rc = decode_sort(D, sl, n_sl, &n, &out->err, &s_lo, &s_hi, &s_val, io_slice);
+    if (rc || !n || out->err) return rc;                                    /* the caller names the error; indices were not looked up */
+    {
+        const unsigned gb = (unsigned)((n + BLOCK - 1) / BLOCK);
         // ---- replay each run of equal words ----
         dispatch_w(W, [&](auto w) {
             constexpr int WV = decltype(w)::value;
@@ -460,6 +570,71 @@ int utk_merge_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, i
 fail:
     if (rc) (void)hipDeviceSynchronize();
     if (tmp) (void)hipFree(tmp);
+    return rc;
+}
+
+int utk_compare_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, uint64_t b_g0, utk_compare_pass_out *out, uint32_t *io_slice) {
+    int rc = UTREE_OK;
+    const int W = (int)D->cfg.W;
+    void *tmp = nullptr;
+    size_t tb = 0, tb2 = 0;
+    uint64_t n = 0;
+    unsigned long long h_stats[N_STATS] = {0}, runs = 0;
+    uint64_t *s_lo = nullptr, *s_hi = nullptr, *s_val = nullptr;
+    memset(out, 0, sizeof *out);
+    D->moves_n = 0;
+    if (!D->cfg.compare) return UTREE_E_ARG;
+    rc = decode_sort(D, sl, n_sl, &n, &out->err, &s_lo, &s_hi, &s_val, io_slice);
+    if (rc || !n || out->err) return rc;
+    {
+        const unsigned gb = (unsigned)((n + BLOCK - 1) / BLOCK);
+        uint64_t *keys = D->b[0], *sorted = D->b[1];                        /* the unsorted words and values: free since the sort */
+        dispatch_w(W, [&](auto w) {
+            constexpr int WV = decltype(w)::value;
+            compare_runs_k<WV><<<dim3(gb), dim3(BLOCK)>>>(s_lo, s_hi, s_val, n, b_g0, D->cfg.n_u, D->d_fig, keys, D->d_stats);
+        });
+        HK(hipGetLastError());
+        HK(hipMemcpy(h_stats, D->d_stats, 8 * N_STATS, hipMemcpyDeviceToHost));
+        const uint64_t m = h_stats[STAT_MOVES];
+        if (m > n / 2) { rc = UTREE_E_HIP; utree_dev_set_hip_error(0, "compare: more changed words than runs of two"); goto fail; }
+        if (m) {
+            // ---- the distinct (label in A, label in B) pairs of the pass and how many words made each move ----
+            HK(rocprim::radix_sort_keys(nullptr, tb, keys, sorted, m, 0, 48));
+            HK(rocprim::run_length_encode(nullptr, tb2, sorted, (unsigned int)m, keys, D->st, D->d_nsel));
+            if (tb2 > tb) tb = tb2;
+            HK(hipMalloc(&tmp, tb ? tb : 8));
+            HK(rocprim::radix_sort_keys(tmp, tb, keys, sorted, m, 0, 48));
+            HK(rocprim::run_length_encode(tmp, tb, sorted, (unsigned int)m, keys, D->st, D->d_nsel));
+            HK(hipMemcpy(&runs, D->d_nsel, 8, hipMemcpyDeviceToHost));
+            HK(hipDeviceSynchronize());
+            HK(hipFree(tmp)); tmp = nullptr;
+        }
+        D->moves_n = runs;
+        out->n_changed = m;
+        out->n_moves = runs;
+    }
+fail:
+    if (rc) (void)hipDeviceSynchronize();
+    if (tmp) (void)hipFree(tmp);
+    return rc;
+}
+
+int utk_compare_moves(utk_merge_dev *D, uint64_t *h_keys, uint32_t *h_counts) {
+    int rc = UTREE_OK;
+    HK(hipSetDevice(D->cfg.device));
+    if (D->moves_n) {
+        HK(hipMemcpy(h_keys, D->b[0], 8ull * D->moves_n, hipMemcpyDeviceToHost));
+        HK(hipMemcpy(h_counts, D->st, 4ull * D->moves_n, hipMemcpyDeviceToHost));
+    }
+fail:
+    return rc;
+}
+
+int utk_compare_figures(utk_merge_dev *D, uint64_t *h_fig) {
+    int rc = UTREE_OK;
+    HK(hipSetDevice(D->cfg.device));
+    if (D->cfg.n_u) HK(hipMemcpy(h_fig, D->d_fig, 8ull * UTK_COMPARE_FIGURES * D->cfg.n_u, hipMemcpyDeviceToHost));
+fail:
     return rc;
 }
 

@@ -40,10 +40,14 @@ static utree_taxon_row *find_row(utree_taxon_row *r, size_t n, const char *s, ui
 }
 
 int utree_taxon_table_write(utree_taxon_row *t, size_t n, int n_fig, int key, const char *header, const char *path) {
+    return utree_taxon_table_write_wide(t, n, n_fig, n_fig, key, header, path);
+}
+
+int utree_taxon_table_write_wide(utree_taxon_row *t, size_t n, int n_own, int n_clade, int key, const char *header, const char *path) {
     const size_t nt = merge_rows(t, n);                      /* one row per distinct text */
     size_t nr = 0;
     for (size_t i = 0; i < nt; ++i) {
-        if (!t[i].own[key]) continue;
+        if (key >= 0 && !t[i].own[key]) continue;
         ++nr;
         for (uint32_t j = 0; j < t[i].len; ++j) nr += t[i].s[j] == ';';
     }
@@ -51,7 +55,7 @@ int utree_taxon_table_write(utree_taxon_row *t, size_t n, int n_fig, int key, co
     if (!r) return UTREE_E_NOMEM;
     size_t k = 0;
     for (size_t i = 0; i < nt; ++i) {                        /* the rows: every text with the key figure and every ';'-prefix of one */
-        if (!t[i].own[key]) continue;
+        if (key >= 0 && !t[i].own[key]) continue;
         r[k++] = t[i];
         for (uint32_t j = 0; j < t[i].len; ++j)
             if (t[i].s[j] == ';') { r[k].s = t[i].s; r[k].len = j; ++k; }
@@ -63,17 +67,17 @@ int utree_taxon_table_write(utree_taxon_row *t, size_t n, int n_fig, int key, co
     }
     for (size_t i = 0; i < nt; ++i) {                        /* clade figures: over ALL inputs whose text is the row's or begins with it + ';' */
         utree_taxon_row *o = find_row(r, nr, t[i].s, t[i].len);
-        if (o) for (int q = 0; q < n_fig; ++q) o->clade[q] += t[i].own[q];
+        if (o) for (int q = 0; q < n_clade; ++q) o->clade[q] += t[i].own[q];
         for (uint32_t j = 0; j < t[i].len; ++j)
-            if (t[i].s[j] == ';' && (o = find_row(r, nr, t[i].s, j))) for (int q = 0; q < n_fig; ++q) o->clade[q] += t[i].own[q];
+            if (t[i].s[j] == ';' && (o = find_row(r, nr, t[i].s, j))) for (int q = 0; q < n_clade; ++q) o->clade[q] += t[i].own[q];
     }
     FILE *f = fopen(path, "wb");
     if (!f) { free(r); return UTREE_E_IO; }
     int bad = fputs(header, f) < 0;
     for (size_t i = 0; i < nr && !bad; ++i) {
         if (r[i].len && fwrite(r[i].s, 1, r[i].len, f) != r[i].len) bad = 1;
-        for (int q = 0; q < 2 * n_fig; ++q)
-            if (fprintf(f, "\t%llu", (unsigned long long)(q < n_fig ? r[i].own[q] : r[i].clade[q - n_fig])) < 0) bad = 1;
+        for (int q = 0; q < n_own + n_clade; ++q)
+            if (fprintf(f, "\t%llu", (unsigned long long)(q < n_own ? r[i].own[q] : r[i].clade[q - n_own])) < 0) bad = 1;
         if (fputc('\n', f) == EOF) bad = 1;
     }
     free(r);

@@ -7,7 +7,7 @@
 /* unsigned bytewise order, the shorter text first on a tie: the order of every report's rows and of a matrix's columns */
 int utree_text_cmp(const void *a, uint64_t la, const void *b, uint64_t lb);
 
-#define UTREE_TAXON_FIGURES 3
+#define UTREE_TAXON_FIGURES 7
 typedef struct { const char *s; uint32_t len; uint64_t own[UTREE_TAXON_FIGURES], clade[UTREE_TAXON_FIGURES]; } utree_taxon_row;
 
 /* Writes `header` (the file's two '#' lines) and one line "<taxon>\t<own figures>\t<clade figures>\n" per row to `path`.  `t` holds n input
@@ -15,6 +15,9 @@ typedef struct { const char *s; uint32_t len; uint64_t own[UTREE_TAXON_FIGURES],
  * one, in unsigned bytewise order (shorter first on a tie).  A row's own figures are those of the inputs of exactly that text, its clade
  * figures the sum over ALL inputs whose text is the row's or begins with it + ';'.  UTREE_OK, UTREE_E_NOMEM or UTREE_E_IO. */
 int utree_taxon_table_write(utree_taxon_row *t, size_t n, int n_fig, int key, const char *header, const char *path);
+/* The same with n_own own figures per line followed by the clade figures of the first n_clade of them (n_clade <= n_own), and with key < 0
+ * for "every input text is a row" (the database compare: seven own figures, clades of its first two). */
+int utree_taxon_table_write_wide(utree_taxon_row *t, size_t n, int n_own, int n_clade, int key, const char *header, const char *path);
 
 /* The per-sample matrix (the layouts are in include/utree_amd.h: utree_samples_write, utree_sredist_write): a column per sample, a row per taxon. */
 typedef struct { const uint8_t *s; uint64_t len; uint64_t reads, uncl; } utree_matrix_col;     /* a sample: its id, reads, unclassified reads  */

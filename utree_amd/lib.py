@@ -17,6 +17,7 @@ BUILD_GG_CLI_PATH = os.path.join(_HERE, "utree-buildGG")
 BUILD_CLI_PATH = os.path.join(_HERE, "utree-build")
 MERGE_GG_CLI_PATH = os.path.join(_HERE, "utree-mergeGG")
 MERGE_CLI_PATH = os.path.join(_HERE, "utree-merge")
+COMPARE_CLI_PATH = os.path.join(_HERE, "utree-compare")
 _LIB = None
 
 OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE, E_PAIRS, E_HITMAP = range(16)
@@ -94,6 +95,31 @@ class MergeEditStats(C.Structure):
     _fields_ = [("n_label_lines", C.c_uint64), ("n_labels_dropped", C.c_uint64), ("n_labels_renamed", C.c_uint64),
                 ("n_labels_cut", C.c_uint64), ("n_rules_unmatched", C.c_uint64), ("n_nodes_dropped", C.c_uint64),
                 ("n_minus_nodes", C.c_uint64), ("n_nodes_subtracted", C.c_uint64)]
+
+
+class CompareStats(C.Structure):
+    """utree_compare_stats: the seven figures summed over all label texts (a, b: the nodes of A and of B; left == arrived == changed), the
+    distinct words and those in both, the label texts each side's nodes carry, the distinct moves, W, passes, identical, seconds."""
+    _fields_ = [("a", C.c_uint64), ("b", C.c_uint64), ("same", C.c_uint64), ("only_a", C.c_uint64), ("only_b", C.c_uint64),
+                ("left", C.c_uint64), ("arrived", C.c_uint64), ("words", C.c_uint64), ("both", C.c_uint64), ("a_labels", C.c_uint64),
+                ("b_labels", C.c_uint64), ("n_moves", C.c_uint64), ("W", C.c_uint32), ("n_passes", C.c_uint32), ("identical", C.c_uint32),
+                ("pad", C.c_uint32), ("seconds", C.c_double)]
+
+
+class CompareInput(C.Structure):
+    """utree_compare_input: how a report's `# a` / `# b` line describes an input."""
+    _fields_ = [("path", C.c_char_p), ("is_ctr", C.c_uint32), ("W", C.c_uint32), ("I", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class CompareEntry(C.Structure):
+    """utree_compare_entry: a label text and its five counted figures."""
+    _fields_ = [("text", C.c_char_p), ("len", C.c_uint32), ("pad", C.c_uint32), ("same", C.c_uint64), ("only_a", C.c_uint64),
+                ("only_b", C.c_uint64), ("left", C.c_uint64), ("arrived", C.c_uint64)]
+
+
+class CompareMove(C.Structure):
+    """utree_compare_move: `kmers` changed words whose label is entry `from_` in A and entry `to` in B."""
+    _fields_ = [("from_", C.c_uint32), ("to", C.c_uint32), ("kmers", C.c_uint64)]
 
 
 class RankParams(C.Structure):
@@ -238,6 +264,9 @@ SYMBOLS = {
     "utree_merge_files_edit": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(MergeEdit),
                                          C.POINTER(MergeStats), C.POINTER(MergeEditStats)]),
     "utree_merge_edit_preview": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.POINTER(MergeEdit), C.c_char_p, C.POINTER(MergeEditStats)]),
+    "utree_compare_files": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(CompareStats)]),
+    "utree_compare_write": (C.c_int, [C.POINTER(CompareInput), C.POINTER(CompareInput), C.POINTER(CompareEntry), C.c_size_t,
+                                      C.POINTER(CompareMove), C.c_size_t, C.c_char_p, C.c_char_p, C.POINTER(CompareStats)]),
     "utree_search_prepare":(C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "utree_search_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                     C.POINTER(SearchStats)]),

@@ -1086,6 +1086,23 @@ def merge_probe(path: str):
     return info
 
 
+def compare(a: str, b: str, report: str, moves=None, device: int = 0):
+    """`utree-compare old new report.tsv [moves.tsv]`: the `.ubt` / `.ctr` database `a` ("old") against `b` ("new"), word by word and label
+    text by label text (include/utree_amd.h: utree_compare_files).  `report` gets the per-taxon figures, `moves` (or None) the distinct
+    (label in a, label in b) pairs of the words whose label changed.  Returns the CompareStats; raises UtreeError (with .detail: what
+    utree_last_hip_error said) when the call fails, and neither file is left then."""
+    st = _lib.CompareStats()
+    L = _lib.load()
+    code = L.utree_compare_files(a.encode(), b.encode(), report.encode(), moves.encode() if moves is not None else None, device, C.byref(st))
+    if code != _lib.OK:
+        detail = (L.utree_last_hip_error() or b"").decode(errors="replace")
+        e = _lib.UtreeError(code, "compare: " + detail)
+        e.detail = detail
+        e.stats = st
+        raise e
+    return st
+
+
 def classify_fasta_bytes(db: CtrDB, tree: DeviceTree, data: bytes, rc: bool = False) -> bytes:
     """Convenience for tests: frame -> upload -> classify -> format, through the C-ABI pieces."""
     import torch
