@@ -1068,6 +1068,95 @@ int utree_compare_write(const utree_compare_input *a, const utree_compare_input 
                         const utree_compare_move *m, size_t n_moves, const char *report_path, const char *moves_path,
                         utree_compare_stats *stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * Database INSPECTION (`utree-inspect`): how safe the k-mers of ONE database are against a single substitution.
+ *
+ * The search matches k-mers exactly.  A sequencing error or a SNP turns a read's k-mer w into a word one substitution away; if the
+ * database holds that word under a label on the same lineage the vote loses nothing, if it holds it under another taxon the read
+ * casts a wrong vote.  utree_inspect_file(db_path, report_path, pairs_path, device, stats) counts, from the file alone, which
+ * nodes have such neighbours and between which label texts, and changes nothing.
+ *
+ * INPUT.  The database is the set of its nodes (word, label TEXT), read exactly as utree_merge_files and utree_compare_files
+ * read an input: `.ubt` or `.ctr` told apart by structure, W in {4, 8, 16} (k = 16, 32, 64), 2- or 4-byte indices, label lines
+ * that repeat a text read as the loader reads them, and the same refusals with the same codes.  Index numbering, index width and
+ * label lines no node carries do not matter.
+ *
+ * NEIGHBOURS.  A neighbour of word w is w ^ (d << 2p) for d in {1, 2, 3} and base position p in [0, k): 3k words (W = 4: only
+ * the low 32 bits carry the 16-mer, so 48, not 96).  A neighbour is HELD when some node of the database has that word.
+ * ANCESTORS.  Text x is an ancestor of y when y begins with x followed by ';' (the merge edit's clade match; taken literally for
+ * the empty text too).  Two texts are ON ONE LINEAGE when they are equal or one is an ancestor of the other.
+ * CLASSES.  Every node falls in exactly one class, the worst any held neighbour puts it in:
+ *     conflict   some held neighbour's text is off the node's lineage
+ *     lineage    otherwise, some held neighbour's text differs from the node's
+ *     same       otherwise, at least one neighbour is held
+ *     isolated   no neighbour is held
+ * (xtree's build log calls isolated + same the adamantine k-mers and conflict the weak ones.)
+ * A PAIR EVENT is an ordered (node, held neighbour node) of different label texts; each is found from both ends, so
+ * pairs(t, t') = pairs(t', t).  Its kind, seen from the node's text `from` towards the neighbour's text `to`: `ancestor` when to
+ * is an ancestor of from, `descendant` for the reverse, `conflict` otherwise.
+ *
+ * report_path (all fields TAB-separated, lines end in '\n'):
+ *     # db <path> .ubt|.ctr <W> <I> <nodes> <labels>                 labels: distinct label texts its nodes carry
+ *     # kmers <N> isolated <n> same <n> lineage <n> conflict <n> pair_events <n> distinct_pairs <n>
+ *     # taxon kmers isolated same lineage conflict clade_kmers clade_conflict
+ *     <taxon> <kmers> <isolated> <same> <lineage> <conflict> <clade_kmers> <clade_conflict>
+ * with one row per label text a node carries and one per ';'-prefix of such a text, in unsigned bytewise order (the shorter
+ * first on a tie); the clade columns sum kmers / conflict over every text that equals the row's taxon or begins with it followed
+ * by ';' (the profile's clade rule).  For every row kmers = isolated + same + lineage + conflict; each of the four class columns
+ * sums over all rows to its total on the `# kmers` line, and the kmers column sums to N.
+ * pairs_path (NULL: not written): the line `# from \t to \t pairs \t kind`, then one line per distinct ordered pair of different
+ * texts with at least one pair event, ordered bytewise by from, then by to.  The pairs column sums to pair_events and the file is
+ * symmetric: (a, b, n) stands with (b, a, n), and `ancestor` is mirrored by `descendant`.
+ *
+ * LIMITS.  (1) Only substitutions are considered, no insertions or deletions.  (2) A database built above compression level 0
+ * holds a sample of its k-mers: the figures describe exactly what the search of that file can hit, not the genomes.  (3) Words
+ * are compared as stored: a neighbour on the other strand counts only if the database holds it.
+ *
+ * UTREE_E_ARG (a NULL db_path, report_path or stats) is returned before a file is opened, and the file is read before a device
+ * is touched.  A failed call leaves neither output file behind; utree_last_hip_error has the detail.  The whole database is
+ * resident on `device` as sorted (word, label) arrays, 12 bytes per node (20 for W = 16), filled in the merge's passes
+ * (n_passes); fewer than 2^32 - 1 nodes (UTREE_E_UNSUPPORTED), and UTREE_E_NOMEM names the size when they do not fit.  With a
+ * pairs_path the distinct pairs are kept with their counts in a table of UTREE_INSPECT_PAIRS entries (default 2^22, at most
+ * 2^28); without one only their keys are kept, to count distinct_pairs, in a set of 2^24.  More distinct pairs than that:
+ * UTREE_E_NOMEM, and the text names the knob.
+ *
+ * utree_inspect_write (host only) is the writer of both files.  It takes the input's description, n label texts with their four
+ * class counts (kmers follows; entries of equal text are added up; an entry without a node makes no row) and, when pairs_path is
+ * given, n_pairs pairs between entries (pairs of equal text pairs are added up), from which pair_events and distinct_pairs are
+ * taken; without a pairs_path `p` is not looked at and the two totals are the arguments'.  UTREE_E_ARG, and no file: a NULL
+ * argument other than p, pairs_path and stats, a pair that names no entry or whose texts are equal, or pairs that are not
+ * symmetric.  stats (or NULL) gets everything but n_passes and the seconds.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint64_t kmers;              /* nodes of the database                                                     */
+    uint64_t isolated, same, lineage, conflict;     /* summed over all label texts: they add up to kmers      */
+    uint64_t pair_events;        /* ordered (node, held neighbour) pairs of different label texts             */
+    uint64_t distinct_pairs;     /* distinct ordered (text, text) pairs among them                            */
+    uint64_t labels;             /* distinct label texts that nodes carry                                     */
+    uint32_t W, I, is_ctr, n_passes;
+    uint32_t clean;              /* 1: conflict == 0                                                          */
+    uint32_t pad;
+    double   seconds;
+    double   seconds_neighbours; /* of those, the directory and the neighbour pass on the device              */
+} utree_inspect_stats;           /* 104 bytes */
+
+int utree_inspect_file(const char *db_path, const char *report_path, const char *pairs_path, int device,
+                       utree_inspect_stats *stats);
+
+typedef struct {
+    const char *text; uint32_t len, pad;
+    uint64_t isolated, same, lineage, conflict;
+} utree_inspect_entry;
+
+typedef struct {
+    uint32_t from, to;           /* indices into the entries: the node's text, its neighbour's text */
+    uint64_t pairs;
+} utree_inspect_pair;
+
+int utree_inspect_write(const utree_compare_input *db, const utree_inspect_entry *e, size_t n, const utree_inspect_pair *p,
+                        size_t n_pairs, uint64_t pair_events, uint64_t distinct_pairs, const char *report_path,
+                        const char *pairs_path, utree_inspect_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

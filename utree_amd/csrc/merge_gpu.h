@@ -26,7 +26,8 @@ typedef struct {
     uint64_t cap_nodes;                                     /* nodes of the largest pass                                    */
     uint64_t cap_raw;                                       /* bytes of the largest pass's records as utk_merge_slice lays them out */
     int compare;                                            /* the handle is utree_compare_files': two inputs, utk_compare_pass instead of
-                                                               utk_merge_pass, nothing is dated, numbered or emitted */
+                                                               utk_merge_pass, nothing is dated, numbered or emitted; or
+                                                               utree_inspect_file's: one input, utk_inspect_pass */
 } utk_merge_cfg;
 
 /* one contiguous stretch of one input's nodes, all of one pass's word range */
@@ -74,6 +75,13 @@ int utk_compare_limit(int device, uint32_t W, uint32_t rec_max, uint32_t n_u, ui
 int utk_compare_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, uint64_t b_g0, utk_compare_pass_out *out, uint32_t *io_slice);
 int utk_compare_moves(utk_merge_dev *D, uint64_t *h_keys, uint32_t *h_counts);          /* the last pass's n_moves pairs, key = label in A << 24 | label in B, ascending */
 int utk_compare_figures(utk_merge_dev *D, uint64_t *h_fig);                            /* [UTK_COMPARE_FIGURES][n_u] */
+
+/* ---- utree_inspect_file (inspect.c, inspect_kernels.hip): the same handle (opened with `compare` set and one input), slices, staging,
+ * decode and sort.  The pass's nodes, ascending, are appended at index `at` of the caller's device arrays, which hold `cap` nodes: the
+ * words' low halves, their high halves (W = 16, else NULL) and the universe label ids.  The passes ascend, so the arrays end up sorted.
+ * *n: the pass's nodes; *err as utk_merge_pass_out's (then nothing was appended). ---- */
+int utk_inspect_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, uint64_t at, uint64_t cap, uint64_t *d_lo, uint64_t *d_hi,
+                     uint32_t *d_lab, uint64_t *n, uint32_t *err, uint32_t *io_slice);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,9 @@
 //   compare_runs_k                a run is one record or two, A's first: its head adds to the per-label counters same / only_a / only_b /
 //                                 left / arrived (a wavefront of one counter adds once) and a changed word appends label A << 24 | label B
 //   rocprim                       radix sort of those keys, run-length encoding -> the pass's distinct moves and their counts
+//
+// utree_inspect_file (`utree-inspect`) shares the same front half with its database as the only input:
+//   inspect_append_k              the sorted pass, as (word, universe label), to the end of the resident arrays of inspect_kernels.hip
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -291,6 +294,17 @@ __global__ __launch_bounds__(BLOCK) void compare_runs_k(const uint64_t *__restri
     if (lane == lead) base = atomicAdd(&stats[STAT_MOVES], (unsigned long long)__popcll(m));
     const uint32_t b_lo = (uint32_t)__shfl((int)(uint32_t)base, (int)lead), b_hi = (uint32_t)__shfl((int)(uint32_t)(base >> 32), (int)lead);
     if (changed) move_keys[(((uint64_t)b_hi << 32) | b_lo) + (uint64_t)__popcll(m & ((1ull << lane) - 1ull))] = key;
+}
+
+// ---- utree_inspect_file: one input, so every run is one record; the sorted pass goes to the resident arrays as (word, universe label)
+__global__ __launch_bounds__(BLOCK) void inspect_append_k(const uint64_t *__restrict__ key_lo, const uint64_t *__restrict__ key_hi,
+                                                          const uint64_t *__restrict__ val, uint64_t n, uint64_t *__restrict__ out_lo,
+                                                          uint64_t *__restrict__ out_hi, uint32_t *__restrict__ out_lab) {
+    const uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    out_lo[j] = key_lo[j];
+    if (out_hi) out_hi[j] = key_hi[j];
+    out_lab[j] = (uint32_t)(val[j] & 0xFFFFFFu);
 }
 
 template <typename Fn> bool dispatch_w(int W, Fn &&fn) {
@@ -616,6 +630,25 @@ int utk_compare_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl,
 fail:
     if (rc) (void)hipDeviceSynchronize();
     if (tmp) (void)hipFree(tmp);
+    return rc;
+}
+
+int utk_inspect_pass(utk_merge_dev *D, const utk_merge_slice *sl, uint32_t n_sl, uint64_t at, uint64_t cap, uint64_t *d_lo, uint64_t *d_hi,
+                     uint32_t *d_lab, uint64_t *n_out, uint32_t *err, uint32_t *io_slice) {
+    int rc = UTREE_OK;
+    uint64_t n = 0;
+    uint64_t *s_lo = nullptr, *s_hi = nullptr, *s_val = nullptr;
+    *n_out = 0; *err = 0;
+    if (!D->cfg.compare || D->cfg.n_in != 1 || !d_lo || !d_lab || (D->cfg.W == 16) != (d_hi != nullptr)) return UTREE_E_ARG;
+    rc = decode_sort(D, sl, n_sl, &n, err, &s_lo, &s_hi, &s_val, io_slice);
+    if (rc || !n || *err) return rc;
+    if (at > cap || n > cap - at) return UTREE_E_ARG;                       /* never beyond the resident arrays */
+    inspect_append_k<<<dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK)>>>(s_lo, s_hi, s_val, n, d_lo + at, d_hi ? d_hi + at : nullptr, d_lab + at);
+    HK(hipGetLastError());
+    HK(hipDeviceSynchronize());
+    *n_out = n;
+fail:
+    if (rc) (void)hipDeviceSynchronize();
     return rc;
 }
 

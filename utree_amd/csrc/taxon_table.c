@@ -44,6 +44,11 @@ int utree_taxon_table_write(utree_taxon_row *t, size_t n, int n_fig, int key, co
 }
 
 int utree_taxon_table_write_wide(utree_taxon_row *t, size_t n, int n_own, int n_clade, int key, const char *header, const char *path) {
+    static const int first[UTREE_TAXON_FIGURES] = {0, 1, 2, 3, 4, 5, 6};
+    return utree_taxon_table_write_pick(t, n, n_own, first, n_clade, key, header, path);
+}
+
+int utree_taxon_table_write_pick(utree_taxon_row *t, size_t n, int n_own, const int *clade_of, int n_clade, int key, const char *header, const char *path) {
     const size_t nt = merge_rows(t, n);                      /* one row per distinct text */
     size_t nr = 0;
     for (size_t i = 0; i < nt; ++i) {
@@ -67,9 +72,9 @@ int utree_taxon_table_write_wide(utree_taxon_row *t, size_t n, int n_own, int n_
     }
     for (size_t i = 0; i < nt; ++i) {                        /* clade figures: over ALL inputs whose text is the row's or begins with it + ';' */
         utree_taxon_row *o = find_row(r, nr, t[i].s, t[i].len);
-        if (o) for (int q = 0; q < n_clade; ++q) o->clade[q] += t[i].own[q];
+        if (o) for (int q = 0; q < n_clade; ++q) o->clade[q] += t[i].own[clade_of[q]];
         for (uint32_t j = 0; j < t[i].len; ++j)
-            if (t[i].s[j] == ';' && (o = find_row(r, nr, t[i].s, j))) for (int q = 0; q < n_clade; ++q) o->clade[q] += t[i].own[q];
+            if (t[i].s[j] == ';' && (o = find_row(r, nr, t[i].s, j))) for (int q = 0; q < n_clade; ++q) o->clade[q] += t[i].own[clade_of[q]];
     }
     FILE *f = fopen(path, "wb");
     if (!f) { free(r); return UTREE_E_IO; }

@@ -18,6 +18,9 @@ int utree_taxon_table_write(utree_taxon_row *t, size_t n, int n_fig, int key, co
 /* The same with n_own own figures per line followed by the clade figures of the first n_clade of them (n_clade <= n_own), and with key < 0
  * for "every input text is a row" (the database compare: seven own figures, clades of its first two). */
 int utree_taxon_table_write_wide(utree_taxon_row *t, size_t n, int n_own, int n_clade, int key, const char *header, const char *path);
+/* The same with the clade figures picked: clade column q sums own figure clade_of[q] (the database inspection: five own figures, clades of
+ * its first and its last). */
+int utree_taxon_table_write_pick(utree_taxon_row *t, size_t n, int n_own, const int *clade_of, int n_clade, int key, const char *header, const char *path);
 
 /* The per-sample matrix (the layouts are in include/utree_amd.h: utree_samples_write, utree_sredist_write): a column per sample, a row per taxon. */
 typedef struct { const uint8_t *s; uint64_t len; uint64_t reads, uncl; } utree_matrix_col;     /* a sample: its id, reads, unclassified reads  */

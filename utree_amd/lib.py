@@ -18,6 +18,7 @@ BUILD_CLI_PATH = os.path.join(_HERE, "utree-build")
 MERGE_GG_CLI_PATH = os.path.join(_HERE, "utree-mergeGG")
 MERGE_CLI_PATH = os.path.join(_HERE, "utree-merge")
 COMPARE_CLI_PATH = os.path.join(_HERE, "utree-compare")
+INSPECT_CLI_PATH = os.path.join(_HERE, "utree-inspect")
 _LIB = None
 
 OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE, E_PAIRS, E_HITMAP = range(16)
@@ -120,6 +121,26 @@ class CompareEntry(C.Structure):
 class CompareMove(C.Structure):
     """utree_compare_move: `kmers` changed words whose label is entry `from_` in A and entry `to` in B."""
     _fields_ = [("from_", C.c_uint32), ("to", C.c_uint32), ("kmers", C.c_uint64)]
+
+
+class InspectStats(C.Structure):
+    """utree_inspect_stats: the nodes and their four classes summed over all label texts, the pair events and the distinct pairs, the label
+    texts nodes carry, how the input reads, passes, clean (no conflict node), seconds in all and in the neighbour pass."""
+    _fields_ = [("kmers", C.c_uint64), ("isolated", C.c_uint64), ("same", C.c_uint64), ("lineage", C.c_uint64), ("conflict", C.c_uint64),
+                ("pair_events", C.c_uint64), ("distinct_pairs", C.c_uint64), ("labels", C.c_uint64), ("W", C.c_uint32), ("I", C.c_uint32),
+                ("is_ctr", C.c_uint32), ("n_passes", C.c_uint32), ("clean", C.c_uint32), ("pad", C.c_uint32), ("seconds", C.c_double),
+                ("seconds_neighbours", C.c_double)]
+
+
+class InspectEntry(C.Structure):
+    """utree_inspect_entry: a label text and its four class counts."""
+    _fields_ = [("text", C.c_char_p), ("len", C.c_uint32), ("pad", C.c_uint32), ("isolated", C.c_uint64), ("same", C.c_uint64),
+                ("lineage", C.c_uint64), ("conflict", C.c_uint64)]
+
+
+class InspectPair(C.Structure):
+    """utree_inspect_pair: `pairs` pair events from nodes of entry `from_` to neighbours of entry `to`."""
+    _fields_ = [("from_", C.c_uint32), ("to", C.c_uint32), ("pairs", C.c_uint64)]
 
 
 class RankParams(C.Structure):
@@ -267,6 +288,9 @@ SYMBOLS = {
     "utree_compare_files": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(CompareStats)]),
     "utree_compare_write": (C.c_int, [C.POINTER(CompareInput), C.POINTER(CompareInput), C.POINTER(CompareEntry), C.c_size_t,
                                       C.POINTER(CompareMove), C.c_size_t, C.c_char_p, C.c_char_p, C.POINTER(CompareStats)]),
+    "utree_inspect_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(InspectStats)]),
+    "utree_inspect_write": (C.c_int, [C.POINTER(CompareInput), C.POINTER(InspectEntry), C.c_size_t, C.POINTER(InspectPair), C.c_size_t,
+                                      C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.POINTER(InspectStats)]),
     "utree_search_prepare":(C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]),
     "utree_search_file": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int,
                                     C.POINTER(SearchStats)]),

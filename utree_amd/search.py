@@ -1103,6 +1103,23 @@ def compare(a: str, b: str, report: str, moves=None, device: int = 0):
     return st
 
 
+def inspect(db: str, report: str, pairs=None, device: int = 0):
+    """`utree-inspect db report.tsv [pairs.tsv]`: which k-mers of the `.ubt` / `.ctr` database `db` have a neighbour one substitution away,
+    and under which label (include/utree_amd.h: utree_inspect_file).  `report` gets the per-taxon classes, `pairs` (or None) the distinct
+    ordered pairs of label texts one substitution apart.  Returns the InspectStats; raises UtreeError (with .detail: what
+    utree_last_hip_error said) when the call fails, and neither file is left then."""
+    st = _lib.InspectStats()
+    L = _lib.load()
+    code = L.utree_inspect_file(db.encode(), report.encode(), pairs.encode() if pairs is not None else None, device, C.byref(st))
+    if code != _lib.OK:
+        detail = (L.utree_last_hip_error() or b"").decode(errors="replace")
+        e = _lib.UtreeError(code, "inspect: " + detail)
+        e.detail = detail
+        e.stats = st
+        raise e
+    return st
+
+
 def classify_fasta_bytes(db: CtrDB, tree: DeviceTree, data: bytes, rc: bool = False) -> bytes:
     """Convenience for tests: frame -> upload -> classify -> format, through the C-ABI pieces."""
     import torch
