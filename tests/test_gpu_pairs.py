@@ -1,4 +1,4 @@
-"""GPU tests of paired-end reads (csrc/pairs_kernels.hip, search.c's second input, UTREE_MATES / UTREE_INTERLEAVED): the device join against a
+"""GPU tests of paired-end reads (csrc/pairs_kernels.hip, search_reader.c's and search.c's second input, UTREE_MATES / UTREE_INTERLEAVED): the device join against a
 numpy join, classify on the joined tensors against the CPU oracle on the numpy join, and the whole-file search against what the genuine
 reference prints for mate 1 + "N" + mate 2 (tests/golden/pairs_*_out*.txt.gz, pinned in tests/test_pairs_cpu.py).  All comparisons are
 exact: there is no tolerance in this feature.

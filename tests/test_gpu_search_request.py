@@ -1,6 +1,6 @@
 """GPU tests of utree_search_run (include/utree_amd.h): every older entry point is a fixed-argument form of it, so the same small search
 through either writes the same bytes; and the host pipeline's one shard path (csrc/search.c: stage, then run) at its edges -- an empty, a full
-and a half second shard, single reads and pairs, with the reports that ride the uploaded span.
+and a half second shard, single reads and pairs, with the reports that ride the uploaded span; and a slot formatted in three pieces across a shard edge.
 
 Run on the MI355X box:  python -m pytest tests -m gpu -x -q
 """
@@ -194,3 +194,26 @@ def test_every_report_over_several_slots_on_two_handles(toy, tmp_path, monkeypat
     assert st1.n_reads == st2.n_reads == toy["P"].n and len(toy["P"].reads_fasta()) > 8 * 30000
     same_files(one_files, two_files)
     assert two_files["out_path"].read_bytes() == toy["want_pairs"][1]
+
+
+# ---- 4. more than one formatting piece per slot -------------------------------------------------------------------------------------------
+def test_three_formatting_pieces_across_a_shard_edge(toy, tmp_path, monkeypatch):
+    """8193 reads in one slot, three host threads, two handles: the formatter cuts the slot into min(threads, reads / 4096 + 1) = 3 pieces at
+    reads 2731 and 5462, the handles' shards meet at read 4097 -- inside piece 1 --, and piece 2 is all of handle 1's.  The output, the map,
+    the sample table and each read's redistributed label (the spool's records carry the handle) equal those of one handle and one piece."""
+    n = 8193
+    monkeypatch.setenv("UTREE_HOST_TEXT", "1")
+    monkeypatch.delenv("UTREE_CHUNK_BYTES", raising=False)
+    reads = write_inputs(toy, tmp_path, "single", n)[0]
+    reports = ("hitmap_path", "samples_path", "redistribute_reads_path")
+    one, one_files = request(tmp_path / "one", reads, None, 0, 1, reports=reports, max_passes=PASSES)
+    two, two_files = request(tmp_path / "two", reads, None, 0, 1, reports=reports, max_passes=PASSES)
+    one.host_threads, two.host_threads = 1, 3
+    st1, st2 = run(toy, one, 1), run(toy, two, 2)
+    assert st1.n_reads == st2.n_reads == n and st1.pipeline == st2.pipeline == 0
+    same_files(one_files, two_files)
+    assert two_files["hitmap_path"].read_bytes().count(b"\n") == n
+    names = set(fasta_names(open(reads, "rb").read()))
+    assert len(names) == n
+    want = b"".join(l for l in toy["want_single"][1].splitlines(True) if l.split(b"\t", 1)[0] in names)
+    assert two_files["out_path"].read_bytes() == want

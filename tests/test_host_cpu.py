@@ -4,6 +4,7 @@ import ctypes as C
 import json
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -396,3 +397,22 @@ def test_k64_sub_slices_in_the_size_model(monkeypatch):
     assert image_gib(568_000_000) == without
     monkeypatch.setenv("UTREE_TABLE_MAX_GB", "20")         # ... and now the plain one is too: coarser slots
     assert image_gib(568_000_000) < without - 4
+
+
+def test_search_reader_under_the_sanitizers(tmp_path):
+    """the host pipeline's reader steps (csrc/search_reader.c) in a stand-alone program under AddressSanitizer + UndefinedBehaviorSanitizer:
+    what the slots commit against the framing of the whole file, and how a search ends, at chunk sizes from two records up"""
+    probe = str(tmp_path / "probe.c")
+    open(probe, "w").write("int main(void) { return 0; }\n")
+    cc = os.environ.get("CC", "cc")
+    try:
+        p = subprocess.run([cc, "-fsanitize=address,undefined", probe, "-o", str(tmp_path / "probe")], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    except OSError:
+        pytest.skip("no C compiler")
+    if p.returncode != 0:
+        pytest.skip("the toolchain has no sanitizer runtime")
+    exe = str(tmp_path / "search_reader_asan")
+    p = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "utree_amd", "csrc"), "search-reader-asan", "SEARCH_READER_ASAN=" + exe],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert p.returncode == 0 and b"search_reader_asan: ok" in p.stdout, p.stdout[-2000:].decode(errors="replace")
+    assert b"ERROR: AddressSanitizer" not in p.stdout and b"runtime error" not in p.stdout

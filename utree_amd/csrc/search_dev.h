@@ -34,4 +34,7 @@ int utree_search_file_device(const utree_ctr *ctr, utree_dev **devs, int n_dev, 
  * pipeline that runs the file again does not print those a second time (the reference prints each once, itree.c:878) */
 void utree_search_ctx_free(void *ctx);
 
+/* one request that utree_search_run (search_entry.c) has checked: the search and its reports (search.c) */
+int utree_search_checked(const utree_ctr *ctr, utree_dev **devs, int n_dev, const utree_search_request *req, utree_search_stats *stats);
+
 #endif
