@@ -54,6 +54,8 @@ def test_golden_outputs_bit_exact(torch_cuda, name, rc):
 @pytest.mark.parametrize("fine_bits", [0, 1, 3, 6])
 @pytest.mark.parametrize("name", ["toy", "k64", "ix32", "katq", "katq2"])
 def test_fine_index_width_does_not_change_results(torch_cuda, name, fine_bits):
+    """At fixture size every fine_bits yields the same table (2^16 slots in all 256 regions: the floor), so this holds the option's plumbing;
+    test_gpu_geometry.py is where the width changes the table."""
     db, tree = tree_for(name, fine_bits)
     assert tree.info.fine_bits == fine_bits
     got = classify_fasta_bytes(db, tree, util.fixture_bytes(name + "_reads.fa.gz"), rc=False)

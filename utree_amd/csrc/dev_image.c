@@ -106,6 +106,8 @@ static uint64_t compute_regions_sub(uint64_t n_nodes, uint32_t W, uint32_t I, ui
     const double m = 4.0 * W - 15.0 - 2.0 * UTREE_MIN_MARGIN(W);     /* the hash is the smallest of this many (a window's candidate 16-mers) */
     const uint32_t cap_entries = bucket_words / utree_rec_words(W, I);
     const char *te = getenv("UTREE_BUCKET_TARGET");                     /* nodes per bucket; experiments only */
+    /* (a fraction is taken as it stands: tests/test_gpu_geometry.py asks for thousandths of a node per bucket, which scales the table of a
+     * billion-node database down to one of a few hundred thousand nodes) */
     const double target = te && atof(te) > 0 ? atof(te) : (bucket_words == 16 ? 0.5625 : 0.375) * cap_entries;
     const char *se = getenv("UTREE_LUMP_SLACK");                        /* experiments only */
     const double slack = se ? atof(se) : 1.5;
