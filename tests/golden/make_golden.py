@@ -22,7 +22,8 @@ Fixture sets:
 `python tests/golden/make_golden.py reference_runs` writes reference_runs.json: hashes of the reference's results on the
 inputs tests/util.py and tests/rank_inputs.py generate (adversarial labels, byte and framing fuzz, hostile BUILD inputs, irregular
 PACKSIZE=16 tables, the rank-specific search's depth and vote-split files); `reference_runs rank_depth` adds only the last two,
-`reference_runs build_edges` adds only the BUILD edge inputs of tests/build_inputs.py (those records also keep the reference's stdout lines).
+`reference_runs build_edges` adds only the BUILD edge inputs of tests/build_inputs.py (those records also keep the reference's stdout lines),
+`reference_runs labels` adds only the searches of tests/label_inputs.py: databases of 65 534 .. 2^19 - 1 labels, reads that name chosen ranks.
 """
 import gzip
 import hashlib
@@ -835,12 +836,49 @@ def gen_build_edges_runs():
     json.dump(full, open(os.path.join(HERE, "reference_runs.json"), "w"), indent=1, sort_keys=True)
 
 
+def gen_labels_runs():
+    """Adds the `labels_*` keys to reference_runs.json and leaves the others as they are: what the genuine search of each record format
+    (oracle/_ref/xtree-searchGG[-k16|-k64][-ix32] and xtree-search[-ix32], one thread) wrote on the databases and reads of tests/label_inputs.py
+    -- SHA-256 of the database and of the reads, exit code, SHA-256 of the output.  The databases (up to 100 MB) are written to a temporary
+    directory and gone afterwards."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import pathlib
+    import label_inputs as li
+    import util
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        fa, want = os.path.join(td, "r.fa"), os.path.join(td, "ref.txt")
+        for name in li.SEARCH_RUNS:
+            built = li.build_named(name, pathlib.Path(td))
+            ctr_sha = util.sha256_of(built.ctr)
+            for rank, kinds in ((False, li.SEARCH_RUNS[name]), (True, li.RANK_RUNS.get(name, ()))):
+                exe = li.reference_binary(built.k, built.I, rank)
+                for kind in kinds:
+                    data = li.reads_data(built, kind)
+                    open(fa, "wb").write(data)
+                    for rc in (0, 1):
+                        if os.path.exists(want):
+                            os.remove(want)
+                        code, _, _ = run([os.path.join(REF, exe), built.ctr, fa, want, "1"] + (["RC"] if rc else []))
+                        out[li.run_key(name, kind, rc, rank)] = {"inputs": {"ctr": ctr_sha, "fa": util.sha256_of(data)}, "exit": code,
+                                                                 "outputs": {"out": util.sha256_of(want)}}
+                        print(li.run_key(name, kind, rc, rank), exe, code)
+            os.remove(built.ctr)
+    full = json.load(open(os.path.join(HERE, "reference_runs.json")))
+    full = {k: v for k, v in full.items() if not k.startswith("labels_")}
+    full.update(out)
+    json.dump(full, open(os.path.join(HERE, "reference_runs.json"), "w"), indent=1, sort_keys=True)
+
+
 def main():
     if not os.path.exists(os.path.join(REF, "xtree-searchGG")):
         sys.exit("build the reference first: make -C oracle ref")
     if len(sys.argv) > 1 and sys.argv[1] == "reference_runs":  # add reference_runs.json (the oracle-vs-reference tests' expected results)
         if len(sys.argv) > 2 and sys.argv[2] == "build_edges":
             gen_build_edges_runs()
+            return
+        if len(sys.argv) > 2 and sys.argv[2] == "labels":
+            gen_labels_runs()
             return
         gen_reference_runs(only_rank_depth=len(sys.argv) > 2 and sys.argv[2] == "rank_depth")
         return
