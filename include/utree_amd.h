@@ -250,7 +250,10 @@ size_t utree_format_records(const utree_ctr *ctr, const uint8_t *h_buf, const ui
 /* Opt-in input formats the reference does not read.  UTREE_INPUT_REFERENCE is the reference's
  * framing (utree_fasta_frame); the others frame complete records serially and, for multi-line FASTA, compact the sequence
  * lines in place.  Error codes: 1 truncated record, 2 record does not start with '@' / '>', 3 FASTQ separator line is not
- * '+', 5 sequence too long.  With a non-reference format the *_opts file functions also read gzip-compressed input. */
+ * '+', 5 sequence too long.  With a non-reference format the *_opts file functions also read gzip-compressed input.
+ * These formats are not read with fgets(…, LINELEN), so no line of theirs is split: a FASTQ record whose sequence and quality
+ * lines have LINELEN - 2 = 16 777 214 bytes each, plain or gzip, and a FASTA record of that many bases wrapped over lines are
+ * framed whole and give the output line of the same bases as one two-line FASTA record. */
 enum { UTREE_INPUT_REFERENCE = 0, UTREE_INPUT_FASTQ = 1, UTREE_INPUT_FASTA_MULTILINE = 2, UTREE_INPUT_AUTO = 3 };
 int utree_reads_frame(uint8_t *h_buf, size_t n, int final, int format, size_t max_reads, uint64_t *seq_off,
                       uint32_t *seq_len, uint64_t *name_off, uint32_t *name_len, size_t *n_reads, size_t *consumed,

@@ -69,6 +69,8 @@ def lib():
         L.orc_windows.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.orc_lookup.restype = C.c_uint32
         L.orc_lookup.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+        L.orc_lookup_batch.restype = None
+        L.orc_lookup_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.orc_vote.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Result)]
         L.orc_format.restype = C.c_size_t
         L.orc_format.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(Result), C.c_char_p, C.c_size_t]
@@ -151,6 +153,16 @@ class OracleDB:
 
     def lookup(self, hi: int, lo: int) -> int:
         return lib().orc_lookup(self._h, hi, lo)
+
+    def lookup_batch(self, hi: np.ndarray, lo: np.ndarray, positions: bool = False):
+        """lookup() for arrays of words: uint32 label indices (BAD_IX where none); with positions also the int64 index of the matching
+        record (-1 where none)."""
+        hi = np.ascontiguousarray(hi, dtype=np.uint64)
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        ix = np.empty(len(lo), dtype=np.uint32)
+        pos = np.empty(len(lo), dtype=np.int64) if positions else None
+        lib().orc_lookup_batch(self._h, hi.ctypes.data, lo.ctypes.data, len(lo), ix.ctypes.data, pos.ctypes.data if positions else None)
+        return (ix, pos) if positions else ix
 
     def vote(self, hits) -> Result:
         a = np.ascontiguousarray(hits, dtype=np.uint32)

@@ -228,12 +228,12 @@ static inline uint32_t rec_ix(const orc_db *db, const uint8_t *rec) {
     memcpy(&v, rec + db->sufbytes, db->I); /* itree.c:681 */
     return v;
 }
-static inline uint32_t lookup_word(const orc_db *db, u128 word) {
+static inline const uint8_t *lookup_rec(const orc_db *db, u128 word) {   /* the record the search ends on when it matches, else NULL */
     const unsigned sxbits = 2 * db->k - 24;                       /* itree.c:694 */
     uint32_t prefix = (uint32_t)(word >> sxbits);
     u128 sx = word & ((((u128)1) << sxbits) - 1);
     uint64_t s = db->binix[prefix], e = db->binix[prefix + 1];    /* itree.c:724 */
-    if (s >= e) return ORC_BAD_IX;                                 /* itree.c:726 */
+    if (s >= e) return NULL;                                       /* itree.c:726 */
     const uint8_t *p = db->recs + (size_t)db->SZ * s;
     uint64_t size = e - s - 1;
     while (size) {                                                 /* itree.c:701-705 */
@@ -242,13 +242,26 @@ static inline uint32_t lookup_word(const orc_db *db, u128 word) {
         if (rec_suffix(db, probe) <= sx) { p = probe; size -= w + 1; }
         else size = w;
     }
-    if (rec_suffix(db, p) != sx) return ORC_BAD_IX;                /* itree.c:706 */
+    return rec_suffix(db, p) == sx ? p : NULL;                     /* itree.c:706 */
+}
+static inline uint32_t lookup_word(const orc_db *db, u128 word) {
+    const uint8_t *p = lookup_rec(db, word);
+    if (!p) return ORC_BAD_IX;
     uint32_t ix = rec_ix(db, p);
     if (db->I == 2 && ix == 0xFFFFu) return ORC_BAD_IX;            /* stored BAD_IX (itree.c:105) */
     return ix;
 }
 uint32_t orc_lookup(const orc_db *db, uint64_t hi, uint64_t lo) {
     return lookup_word(db, ((u128)hi << 64) | lo);
+}
+/* orc_lookup for n words at once (the tests' hit-map and coverage models on reads of millions of windows): ix[i] as orc_lookup gives it,
+ * and, where pos is given, pos[i] = index of the record the search ended on, -1 where no record matched. */
+void orc_lookup_batch(const orc_db *db, const uint64_t *hi, const uint64_t *lo, size_t n, uint32_t *ix, int64_t *pos) {
+    for (size_t i = 0; i < n; ++i) {
+        const u128 word = ((u128)hi[i] << 64) | lo[i];
+        ix[i] = lookup_word(db, word);
+        if (pos) { const uint8_t *p = lookup_rec(db, word); pos[i] = p ? (int64_t)((size_t)(p - db->recs) / db->SZ) : -1; }
+    }
 }
 
 /* ---------------------------------------------------------------------------------------------

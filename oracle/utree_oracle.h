@@ -52,6 +52,8 @@ size_t orc_windows(const uint8_t *seq, size_t len, int k, uint32_t *end_pos, uin
                    size_t cap);
 /* itree.c:720-730 XT_getIX32 + 699-707 xtSuffixBS.  Returns raw stored ix or ORC_BAD_IX. */
 uint32_t orc_lookup(const orc_db *db, uint64_t hi, uint64_t lo);
+/* orc_lookup for n words; pos (may be NULL): index of the matching record, -1 where none matched. */
+void orc_lookup_batch(const orc_db *db, const uint64_t *hi, const uint64_t *lo, size_t n, uint32_t *ix, int64_t *pos);
 /* itree.c:1028-1096: tally + sort + vote on a hit list (label indices < nlabels). */
 void orc_vote(const orc_db *db, const uint32_t *hits, uint32_t nhits, orc_result *res);
 /* itree.c:1032,1040,1096: format one output line (returns bytes written, 0 when res->found==0). */

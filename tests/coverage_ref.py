@@ -48,6 +48,28 @@ def coverage_counts(ctr_path, seqs, rc):
     return db, cov, hits, [o.label(i) for i in range(nl)]
 
 
+def coverage_counts_batch(ctr_path, seqs, rc):
+    """coverage_counts() with one lookup call per read (OracleDB.lookup_batch gives label and record position): for reads of millions of
+    windows.  seqs: bytes or uint8 arrays."""
+    import hitmap_ref
+    o = orc.OracleDB.load(ctr_path)
+    d = ctrfile.read_ctr(ctr_path)
+    nl = o.n_labels
+    ix = d.ix()
+    db = np.bincount(ix[ix < nl].astype(np.int64), minlength=nl)
+    hits = np.zeros(nl, dtype=np.int64)
+    seen = np.zeros(len(ix), dtype=bool)
+    for s in seqs:
+        _, hi, lo = orc.windows(hitmap_ref.query_array(s, rc), o.k)
+        lab, pos = o.lookup_batch(hi, lo, positions=True)
+        hit = lab < nl
+        assert (pos[hit] >= 0).all() and np.array_equal(ix[pos[hit]], lab[hit])
+        hits += np.bincount(lab[hit].astype(np.int64), minlength=nl)
+        seen[pos[hit]] = True
+    cov = np.bincount(ix[seen].astype(np.int64), minlength=nl)
+    return db, cov, hits, [o.label(i) for i in range(nl)]
+
+
 def coverage_file(db, cov, hits, texts, n_reads):
     own, clade = {}, {}
     for t, a, b, c in zip(texts, db.tolist(), cov.tolist(), hits.tolist()):

@@ -23,7 +23,8 @@ Fixture sets:
 inputs tests/util.py and tests/rank_inputs.py generate (adversarial labels, byte and framing fuzz, hostile BUILD inputs, irregular
 PACKSIZE=16 tables, the rank-specific search's depth and vote-split files); `reference_runs rank_depth` adds only the last two,
 `reference_runs build_edges` adds only the BUILD edge inputs of tests/build_inputs.py (those records also keep the reference's stdout lines),
-`reference_runs labels` adds only the searches of tests/label_inputs.py: databases of 65 534 .. 2^19 - 1 labels, reads that name chosen ranks.
+`reference_runs labels` adds only the searches of tests/label_inputs.py: databases of 65 534 .. 2^19 - 1 labels, reads that name chosen ranks,
+`reference_runs long` adds only the searches of tests/long_inputs.py: records at and one byte past the 16 MiB line limit.
 """
 import gzip
 import hashlib
@@ -870,10 +871,50 @@ def gen_labels_runs():
     json.dump(full, open(os.path.join(HERE, "reference_runs.json"), "w"), indent=1, sort_keys=True)
 
 
+def gen_long_runs():
+    """Adds the `long_*` keys to reference_runs.json and leaves the others as they are: what the genuine search of each record format
+    (oracle/_ref/xtree-searchGG[-k16|-k64][-ix32] and xtree-search[-k64|-ix32], one thread) wrote on the databases and files of
+    tests/long_inputs.py -- records at, and one byte past, the 16 MiB line limit.  SHA-256 of the database and of the input, exit code, SHA-256
+    of the output; a run that ends in an error keeps the lines the reference printed as well.  Nothing of the inputs (up to 84 MB) is kept."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import pathlib
+    import long_inputs as li
+    import util
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        fa, want = os.path.join(td, "r.fa"), os.path.join(td, "ref.txt")
+        for name in li.SEARCH_RUNS:
+            built = li.build(name, pathlib.Path(td))
+            ctr_sha = util.sha256_of(built.ctr)
+            for rank, fnames in ((False, li.SEARCH_RUNS[name]), (True, li.RANK_RUNS.get(name, ()))):
+                exe = li.reference_binary(built.k, built.I, rank)
+                for fname in fnames:
+                    data = li.file_bytes(built, fname)
+                    open(fa, "wb").write(data)
+                    for rc in (0, 1):
+                        if os.path.exists(want):
+                            os.remove(want)
+                        code, so, se = run([os.path.join(REF, exe), built.ctr, fa, want, "1"] + (["RC"] if rc else []))
+                        rec = {"inputs": {"ctr": ctr_sha, "fa": util.sha256_of(data)}, "exit": code, "outputs": {"out": util.sha256_of(want)}}
+                        if code:                                        # (the error message itself goes to stderr, with the offending line behind it)
+                            rec["stdout"] = so.decode("latin-1").splitlines()
+                            rec["stderr"] = [line[:64] for line in se.decode("latin-1").splitlines()]
+                        out[li.run_key(name, fname, rc, rank)] = rec
+                        print(li.run_key(name, fname, rc, rank), exe, code, flush=True)
+            os.remove(built.ctr)
+    full = json.load(open(os.path.join(HERE, "reference_runs.json")))
+    full = {k: v for k, v in full.items() if not k.startswith("long_")}
+    full.update(out)
+    json.dump(full, open(os.path.join(HERE, "reference_runs.json"), "w"), indent=1, sort_keys=True)
+
+
 def main():
     if not os.path.exists(os.path.join(REF, "xtree-searchGG")):
         sys.exit("build the reference first: make -C oracle ref")
     if len(sys.argv) > 1 and sys.argv[1] == "reference_runs":  # add reference_runs.json (the oracle-vs-reference tests' expected results)
+        if len(sys.argv) > 2 and sys.argv[2] == "long":
+            gen_long_runs()
+            return
         if len(sys.argv) > 2 and sys.argv[2] == "build_edges":
             gen_build_edges_runs()
             return

@@ -30,6 +30,37 @@ def codes(o, seq, rc):
     return out
 
 
+def query_array(seq, rc):
+    """query() on a uint8 array (bytes are taken too): no Python object per base"""
+    s = np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else seq
+    if not rc:
+        return s
+    comp = np.arange(256, dtype=np.uint8)
+    comp[np.frombuffer(b"ACGTacgt", dtype=np.uint8)] = np.frombuffer(b"TGCAtgca", dtype=np.uint8)
+    return np.concatenate([s, np.frombuffer(b"N", dtype=np.uint8), comp[s[::-1]]])
+
+
+def codes_batch(o, seq, rc):
+    """codes() with one lookup call for all windows (OracleDB.lookup_batch): for reads of millions of windows"""
+    q, k = query_array(seq, rc), o.k
+    n = len(q) - k + 1 if len(q) >= k else 0
+    out = np.full(n, INVALID, dtype=np.uint32)
+    if n:
+        pos, hi, lo = orc.windows(q, k)
+        ix = o.lookup_batch(hi, lo)
+        out[pos.astype(np.int64) - (k - 1)] = np.where(ix < o.n_labels, ix, MISS).astype(np.uint32)
+    return out
+
+
+def runs_arrays(c):
+    """runs_of() as arrays (code uint32, count int64)"""
+    if not len(c):
+        return np.zeros(0, np.uint32), np.zeros(0, np.int64)
+    cut = np.flatnonzero(c[1:] != c[:-1]) + 1
+    starts = np.concatenate([[0], cut])
+    return c[starts], np.diff(np.concatenate([starts, [len(c)]]))
+
+
 def runs_of(c):
     """maximal stretches of equal code: [(code, count), ...]"""
     if not len(c):
