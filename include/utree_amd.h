@@ -1160,6 +1160,101 @@ int utree_inspect_write(const utree_compare_input *db, const utree_inspect_entry
                         size_t n_pairs, uint64_t pair_events, uint64_t distinct_pairs, const char *report_path,
                         const char *pairs_path, utree_inspect_stats *stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * Long queries tile by tile (`utree-tiles`; no counterpart in the reference, which gives a query ONE vote over all of its k-mers,
+ * itree.c:1044-1088: a 2-Mb contig that is 85 % one taxon and 15 % another reads like one that is uniformly the first).  A tile is a
+ * stretch of a query classified as a read of its own; a tile is a VIEW into the bytes of the query that are already in HBM, never a copy.
+ *   Parameters.  W = tile_bp, S = step_bp, in bases, 1 <= S <= W <= UTREE_TILE_MAX_BP (16 777 214: the longest line the framing takes);
+ *     anything else is UTREE_E_ARG.
+ *   Tiles.  A query is framed exactly as the search frames it; its length is L.  n = 1 if L <= W, else 1 + ceil((L - W) / S) tiles;
+ *     tile t is q[t*S .. min(t*S + W, L)).  Only the last tile can be shorter than W, and when there is more than one it is longer than
+ *     W - S.  (An input format that frames an empty sequence gives it one empty tile.)  L < 2^32 and S >= 1: fewer than 2^32 tiles a query.
+ *   Result.  A tile's utree_result is what utree_classify_batch gives for that byte range as a read of its own; with RC that is
+ *     tile + 'N' + revcomp(tile), what the reference does with a record holding those bases (itree.c:891-898).
+ *   tiles.tsv.  A tile with found > 0 has one line: the reference's output line (itree.c:1032, 1040, 1096) under the name
+ *     <name>:<start>-<end>, 1-based and inclusive (the region syntax of `samtools faidx`); query order, then tile order; found == 0 prints
+ *     nothing.  The file is byte for byte what `xtree-searchGG db split.fa out.txt 1 [RC]` of the reference writes for the FASTA that holds
+ *     one two-line record ><name>:<start>-<end> per tile.
+ *   segments.tsv (optional).  Within a query, maximal runs of consecutive tiles of equal class: both unclassified (found == 0), or both
+ *     classified with the same taxon TEXT (two labels may print one text; the empty taxon is a classified class of its own).  One line a run,
+ *         name \t start \t end \t n_tiles \t C|U \t taxon \t found
+ *     start = the first tile's, end = the last tile's, taxon empty for U, found = the sum of the tiles'.  Every query has at least one
+ *     line, and the n_tiles column sums to the tiles.
+ *   Not supported: pairs (a tile across the joining 'N' means nothing), the rank-specific search, more than one device.
+ *
+ * Device side, two calls, both asynchronous on `stream` and without state outside what the caller passes.  utree_classify_batch then takes
+ * (d_bases, d_toff, d_tlen) unchanged.  What makes that right: no kernel of the classify path writes d_bases or looks at a read's
+ * neighbour (there is no d_off[r + 1] anywhere), so overlapping views are reads like any other; its workspace is sized from the total_bases
+ * it is GIVEN (dev_image.c: carve), not from the buffer, so a sum of tile lengths above the buffer's size is an ordinary figure.  Pass the
+ * meta record's exact total_bases and max_len.  A larger total_bases only sizes more workspace; a larger max_len is also answered
+ * correctly but may pick the kernels of longer reads, so it costs time.
+ * ---------------------------------------------------------------------------------------------- */
+#define UTREE_TILE_MAX_BP 16777214u
+#define UTREE_TILES_MAX_BATCH (1u << 21)      /* tiles a call of utree_tiles_views takes: the search's reads per batch */
+/* total_tiles: of the batch (both calls write it).  total_bases / max_len: of the range's tiles (utree_tiles_views; 0 from utree_tiles_plan).
+ * error: 0; 1 (utree_tiles_views): the range ends behind total_tiles -- nothing was written.  utree_tiles_plan has nothing to report and
+ * writes 0: the word is there so that a caller checks one field after either call. */
+typedef struct { uint64_t total_tiles, total_bases; uint32_t max_len, error; } utree_tiles_meta;
+size_t utree_tiles_workspace_bytes(const utree_dev *dev, uint32_t n_reads);
+/* d_tile_first[r] = tiles of the queries in front of r (n_reads + 1 entries; the last is the batch's total): one count kernel and the scan
+ * the hit map uses. */
+int utree_tiles_plan(utree_dev *dev, const uint32_t *d_len, uint32_t n_reads, uint32_t tile_bp, uint32_t step_bp, uint64_t *d_tile_first,
+                     utree_tiles_meta *d_meta, void *d_workspace, size_t workspace_bytes, void *stream);
+/* Tiles [first_tile, first_tile + n_tiles) of the batch's numbering, n_tiles <= UTREE_TILES_MAX_BATCH; for the j-th of them d_toff[j] =
+ * d_off[q] + t*S (absolute, as utree_classify_batch takes it), d_tlen[j], d_tquery[j] = q, d_tindex[j] = t.  One thread a tile, its query
+ * found by binary search in d_tile_first: a query of one tile and one of 30 000 load the lanes alike.  A range may begin and end inside a
+ * query.  *d_meta is complete once the stream has drained. */
+int utree_tiles_views(utree_dev *dev, const uint64_t *d_off, const uint32_t *d_len, uint32_t n_reads, uint32_t tile_bp, uint32_t step_bp,
+                      const uint64_t *d_tile_first, uint64_t first_tile, uint32_t n_tiles, uint64_t *d_toff, uint32_t *d_tlen,
+                      uint32_t *d_tquery, uint32_t *d_tindex, utree_tiles_meta *d_meta, void *stream);
+
+/* Host only, thread-safe: the two files' lines for n tiles in order.  Tile j belongs to query q = tquery[j], whose name is
+ * h_buf[name_off[q] .. + name_len[q]) and whose length is seq_len[q]; tindex[j] is its number within q.  Both return the bytes written, or
+ * (size_t)-1 when cap is too small or a result names a label that is none of ctr's -- as utree_hitmap_format.
+ * utree_tiles_format: one line per tile with found > 0; everything behind the name is written by the code utree_format_records uses.
+ * *classified (may be NULL) += lines written. */
+size_t utree_tiles_format(const utree_ctr *ctr, const uint8_t *h_buf, const uint64_t *name_off, const uint32_t *name_len,
+                          const uint32_t *seq_len, uint32_t tile_bp, uint32_t step_bp, const uint32_t *tquery, const uint32_t *tindex,
+                          const utree_result *h_res, size_t n, char *h_out, size_t cap, uint64_t *classified);
+/* The run that is open behind the tiles seen so far.  Zero it in front of a query's first tile; a caller that formats a query's tiles in
+ * several calls (its tiles may straddle sub-batches) passes the same state to each, and flush != 0 with the last, which closes the open run.
+ * A call that returns (size_t)-1 leaves the state as it was. */
+typedef struct {
+    uint32_t open, query;        /* a run is open, of this query                           */
+    uint64_t start, end;         /* 1-based, inclusive                                      */
+    uint64_t n_tiles, found;
+    uint32_t classified, label;  /* C or U; the label whose first taxon_len bytes it prints */
+    uint64_t taxon_len;
+} utree_tiles_run;               /* 56 bytes */
+/* *segments (may be NULL) += lines written. */
+size_t utree_tiles_segments_format(const utree_ctr *ctr, const uint8_t *h_buf, const uint64_t *name_off, const uint32_t *name_len,
+                                   const uint32_t *seq_len, uint32_t tile_bp, uint32_t step_bp, const uint32_t *tquery,
+                                   const uint32_t *tindex, const utree_result *h_res, size_t n, int flush, utree_tiles_run *state,
+                                   char *h_out, size_t cap, uint64_t *segments);
+
+/* The whole run: reads_path framed as the search frames it (input_format: UTREE_INPUT_*; gzip with the opt-in formats), every query cut
+ * into tiles on the device, the tiles classified in sub-batches of at most UTREE_TILES_BATCH (environment; default and most
+ * UTREE_TILES_MAX_BATCH), tiles_path and -- when not NULL -- segments_path written.  `size` of both structs is sizeof the struct.
+ * Every argument check comes before ctr or dev is looked at: UTREE_E_ARG for a NULL ctr, dev, reads_path, tiles_path, params or stats, a
+ * wrong size, W or S out of range, do_rc other than 0 / 1, an input_format that is none.  A framing error ends the run as it ends the
+ * search: the tiles of the queries framed in front of it are written, stats->fasta_error says what, UTREE_E_FASTA.  A run that fails for
+ * another reason leaves neither file (UTREE_E_DEVICE also when a tile's result names a label ctr does not have: ctr and dev are of
+ * different databases). */
+typedef struct {
+    uint32_t size;
+    uint32_t tile_bp, step_bp;
+    int32_t  do_rc, input_format, host_threads;
+} utree_tiles_params;            /* 24 bytes */
+typedef struct {
+    uint32_t size, pad;
+    uint64_t n_queries, n_tiles, classified, segments;   /* segments 0 without a segments_path */
+    uint64_t bytes_in, n_batches;
+    utree_fasta_error fasta_error;
+    double   seconds_total, seconds_device;              /* of those, upload to results on the host */
+} utree_tiles_stats;             /* 88 bytes */
+int utree_tiles_file(const utree_ctr *ctr, utree_dev *dev, const char *reads_path, const char *tiles_path, const char *segments_path,
+                     const utree_tiles_params *params, utree_tiles_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,4 +18,12 @@ struct utree_ctr {
     uint32_t *rank2ix, *ix2rank;/* strcmp order <-> file order                                             */
 };
 
+/* The two halves of an output line of the GG search behind the query's name (fasta.c), shared by utree_format_records and the tile lines of
+ * tiles.c.  utk_record_taxon: the taxon a record prints -- the first bytes of *text, their number returned ((size_t)-1: the label is none of
+ * ctr's).  utk_record_tail: "\t taxon \t found \t uix \t sl;ol \n" (itree.c:1032, 1040, 1096) at o, at most ll + UTK_RECORD_TAIL_MAX bytes;
+ * returns the byte behind them. */
+#define UTK_RECORD_TAIL_MAX 48
+size_t utk_record_taxon(const utree_ctr *ctr, const utree_result *r, const char **text);
+char *utk_record_tail(const char *lab, size_t ll, const utree_result *r, char *o);
+
 #endif

@@ -253,6 +253,30 @@ static inline char *put_u32(char *o, uint32_t v) {
     return o;
 }
 
+size_t utk_record_taxon(const utree_ctr *ctr, const utree_result *r, const char **text) {
+    if (r->label >= ctr->info.n_labels) return (size_t)-1;
+    size_t ll = r->cut == -1 ? 0 : r->cut == -2 ? ctr->label_len[r->label] : (size_t)r->cut;
+    if (ll > ctr->label_len[r->label]) ll = ctr->label_len[r->label];
+    *text = ctr->labels[r->label];
+    return ll;
+}
+
+char *utk_record_tail(const char *lab, size_t ll, const utree_result *r, char *o) {
+    *o++ = '\t';
+    memcpy(o, lab, ll); o += ll;
+    *o++ = '\t';
+    o = put_u32(o, r->found);
+    *o++ = '\t';
+    if (r->uix == 1) { *o++ = '1'; *o++ = '\t'; *o++ = '*'; }        /* itree.c:1032, 1040 */
+    else {                                                           /* itree.c:1096 */
+        o = put_u32(o, r->uix); *o++ = '\t';
+        o = put_u32(o, r->sl); *o++ = ';';
+        o = put_u32(o, r->ol);
+    }
+    *o++ = '\n';
+    return o;
+}
+
 size_t utree_format_records(const utree_ctr *ctr, const uint8_t *h_buf, const uint64_t *name_off,
                             const uint32_t *name_len, const utree_result *res, size_t n, char *out, size_t cap,
                             uint64_t *good_finds) {
@@ -261,25 +285,13 @@ size_t utree_format_records(const utree_ctr *ctr, const uint8_t *h_buf, const ui
     for (size_t i = 0; i < n; ++i) {
         const utree_result *r = &res[i];
         if (!r->found) continue;                                     /* itree.c:1028: no hit, no line */
-        if (r->label >= ctr->info.n_labels) return (size_t)-1;
-        const char *lab = ctr->labels[r->label];
-        size_t ll = r->cut == -1 ? 0 : r->cut == -2 ? ctr->label_len[r->label] : (size_t)r->cut;
-        if (ll > ctr->label_len[r->label]) ll = ctr->label_len[r->label];
-        size_t need = (size_t)name_len[i] + ll + 48;
+        const char *lab;
+        const size_t ll = utk_record_taxon(ctr, r, &lab);
+        if (ll == (size_t)-1) return (size_t)-1;
+        size_t need = (size_t)name_len[i] + ll + UTK_RECORD_TAIL_MAX;
         if ((size_t)(o - out) + need > cap) return (size_t)-1;
         memcpy(o, h_buf + name_off[i], name_len[i]); o += name_len[i];
-        *o++ = '\t';
-        memcpy(o, lab, ll); o += ll;
-        *o++ = '\t';
-        o = put_u32(o, r->found);
-        *o++ = '\t';
-        if (r->uix == 1) { *o++ = '1'; *o++ = '\t'; *o++ = '*'; }    /* itree.c:1032, 1040 */
-        else {                                                       /* itree.c:1096 */
-            o = put_u32(o, r->uix); *o++ = '\t';
-            o = put_u32(o, r->sl); *o++ = ';';
-            o = put_u32(o, r->ol);
-        }
-        *o++ = '\n';
+        o = utk_record_tail(lab, ll, r, o);
         ++good;
     }
     if (good_finds) *good_finds += good;

@@ -19,10 +19,12 @@ MERGE_GG_CLI_PATH = os.path.join(_HERE, "utree-mergeGG")
 MERGE_CLI_PATH = os.path.join(_HERE, "utree-merge")
 COMPARE_CLI_PATH = os.path.join(_HERE, "utree-compare")
 INSPECT_CLI_PATH = os.path.join(_HERE, "utree-inspect")
+TILES_CLI_PATH = os.path.join(_HERE, "utree-tiles")
 _LIB = None
 
 OK, E_IO, E_FORMAT, E_UNSUPPORTED, E_NOMEM, E_HIP, E_ARG, E_NOLABELS, E_FASTA, E_RCCL, E_BUILD, E_DEVICE, E_PROFILE, E_COVERAGE, E_PAIRS, E_HITMAP = range(16)
 HIT_MISS, HIT_INVALID = 0xFFFFFFFF, 0xFFFFFFFE
+TILE_MAX_BP, TILES_MAX_BATCH = 16777214, 1 << 21
 REDIST_KEY_NONE = 0xFFFFFFFF
 BUILD_E_MAP_EMPTY, BUILD_E_MAP, BUILD_E_FASTA, BUILD_E_NO_KMERS, BUILD_E_NAME = range(1, 6)
 FINE_AUTO = -1
@@ -193,6 +195,36 @@ class HitRun(C.Structure):
 class HitmapMeta(C.Structure):
     """utree_hitmap_meta: error 0, 1 run_capacity too small, 2 total_bases too small, 3 a query of 2^32 windows or more."""
     _fields_ = [("total_runs", C.c_uint64), ("total_windows", C.c_uint64), ("error", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class TilesMeta(C.Structure):
+    """utree_tiles_meta: the batch's tiles; the bases and the longest tile of a range of them; error 1: the range ends behind the tiles."""
+    _fields_ = [("total_tiles", C.c_uint64), ("total_bases", C.c_uint64), ("max_len", C.c_uint32), ("error", C.c_uint32)]
+
+
+class TilesRun(C.Structure):
+    """utree_tiles_run: the run of tiles that utree_tiles_segments_format holds open between two calls."""
+    _fields_ = [("open", C.c_uint32), ("query", C.c_uint32), ("start", C.c_uint64), ("end", C.c_uint64), ("n_tiles", C.c_uint64),
+                ("found", C.c_uint64), ("classified", C.c_uint32), ("label", C.c_uint32), ("taxon_len", C.c_uint64)]
+
+
+class TilesParams(C.Structure):
+    """utree_tiles_params: tile length and step in bases, RC, UTREE_INPUT_*, the formatting team; `size` is filled in."""
+    _fields_ = [("size", C.c_uint32), ("tile_bp", C.c_uint32), ("step_bp", C.c_uint32), ("do_rc", C.c_int32), ("input_format", C.c_int32),
+                ("host_threads", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__(size=C.sizeof(TilesParams), **kw)
+
+
+class TilesStats(C.Structure):
+    """utree_tiles_stats: what utree_tiles_file counted and how long it took; `size` is filled in."""
+    _fields_ = [("size", C.c_uint32), ("pad", C.c_uint32), ("n_queries", C.c_uint64), ("n_tiles", C.c_uint64), ("classified", C.c_uint64),
+                ("segments", C.c_uint64), ("bytes_in", C.c_uint64), ("n_batches", C.c_uint64), ("fasta_error", FastaError),
+                ("seconds_total", C.c_double), ("seconds_device", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__(size=C.sizeof(TilesStats), **kw)
 
 
 class SamplesCell(C.Structure):
@@ -377,6 +409,17 @@ SYMBOLS = {
     "utree_search_file_sample_redistribute": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p,
                                                         C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_char_p,
                                                         C.c_char_p, C.c_int, C.c_char_p, C.POINTER(SearchStats)]),
+    "utree_tiles_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32]),
+    "utree_tiles_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "utree_tiles_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "utree_tiles_format": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "utree_tiles_segments_format": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(TilesRun), C.c_void_p, C.c_size_t,
+                                                 C.POINTER(C.c_uint64)]),
+    "utree_tiles_file": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(TilesParams), C.POINTER(TilesStats)]),
 }
 
 

@@ -11,6 +11,8 @@
     tree.coverage()                  per-taxon database k-mers, distinct ones hit, hits (no counterpart in the reference)
     tree.samples()                   per-sample taxon table of multiplexed reads, ids interned on the device (no counterpart in the reference)
     tree.sample_redistribution()     ambiguous reads of multiplexed reads redistributed within each sample (no counterpart in the reference)
+    tree.tiles_plan / tiles_views    the tiles of long queries as views into their bases, for classify() (no counterpart in the reference)
+    tiles_file(db, tree, in, ...)    the `utree-tiles` run: tiles.tsv and segments.tsv of a file of long queries
     tree.redistribution()            candidate sets of ambiguous reads, redistributed among their tied labels (as xtree does)
 
 torch is used only for device memory and streams (plumbing); every computation happens in the HIP kernels
@@ -344,6 +346,44 @@ class DeviceTree:
         stream.synchronize()
         m = _lib.HitmapMeta.from_buffer_copy(d_meta.cpu().numpy().tobytes())
         return run_off, runs, dict(total_runs=int(m.total_runs), total_windows=int(m.total_windows), error=int(m.error))
+
+    def tiles_plan(self, length, tile_bp: int, step_bp: int):
+        """utree_tiles_plan: the tiles of a batch of queries, W = tile_bp, S = step_bp.  length: int32 CUDA tensor of the queries' lengths.
+        Returns (tile_first, meta): the int64 [n + 1] CUDA tensor of the tiles in front of each query (the last entry is the batch's total)
+        and meta = the dict {total_tiles, total_bases, max_len, error} read back once the stream has drained."""
+        import torch
+        n = length.numel()
+        dev = length.device
+        need = _lib.load().utree_tiles_workspace_bytes(self._h, n)
+        if not need:
+            raise _lib.UtreeError(_lib.E_ARG, "utree_tiles_workspace_bytes")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        tile_first = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_meta = torch.zeros(3, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _lib.check(_lib.load().utree_tiles_plan(self._h, length.data_ptr(), n, tile_bp, step_bp, tile_first.data_ptr(), d_meta.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), stream.cuda_stream), "utree_tiles_plan")
+        stream.synchronize()
+        return tile_first, _tiles_meta(d_meta)
+
+    def tiles_views(self, off, length, tile_bp: int, step_bp: int, tile_first, first_tile: int, n_tiles: int):
+        """utree_tiles_views: tiles [first_tile, first_tile + n_tiles) of the plan `tile_first` as views into the queries' bases.  off /
+        length: the queries as classify() takes them.  Returns (toff, tlen, tquery, tindex, meta): int64 / int32 / int32 / int32 CUDA
+        tensors of n_tiles entries -- classify(bases, toff, tlen, total_bases=meta["total_bases"], max_len=meta["max_len"]) classifies the
+        tiles -- and meta as tiles_plan gives it (error 1: the range ends behind the plan's tiles, nothing was written)."""
+        import torch
+        dev = tile_first.device
+        toff = torch.empty(n_tiles, dtype=torch.int64, device=dev)
+        tlen = torch.empty(n_tiles, dtype=torch.int32, device=dev)
+        tquery = torch.empty(n_tiles, dtype=torch.int32, device=dev)
+        tindex = torch.empty(n_tiles, dtype=torch.int32, device=dev)
+        d_meta = torch.zeros(3, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _lib.check(_lib.load().utree_tiles_views(self._h, off.data_ptr(), length.data_ptr(), length.numel(), tile_bp, step_bp, tile_first.data_ptr(),
+                                                 first_tile, n_tiles, toff.data_ptr(), tlen.data_ptr(), tquery.data_ptr(), tindex.data_ptr(),
+                                                 d_meta.data_ptr(), stream.cuda_stream), "utree_tiles_views")
+        stream.synchronize()
+        return toff, tlen, tquery, tindex, _tiles_meta(d_meta)
 
     def poll(self):
         """utree_classify_poll: raises UtreeError(E_DEVICE) if a batch that has finished since the last call found its workspace
@@ -1118,6 +1158,79 @@ def inspect(db: str, report: str, pairs=None, device: int = 0):
         e.stats = st
         raise e
     return st
+
+
+def _tiles_meta(d_meta):
+    m = _lib.TilesMeta.from_buffer_copy(d_meta.cpu().numpy().tobytes())
+    return dict(total_tiles=int(m.total_tiles), total_bases=int(m.total_bases), max_len=int(m.max_len), error=int(m.error))
+
+
+def _tiles_text(what, cap, call):
+    bad = C.c_size_t(-1).value
+    while True:
+        out = np.empty(cap, dtype=np.uint8)
+        n = call(out)
+        if n != bad:
+            return out[:n].tobytes()
+        if cap > (1 << 34):
+            raise _lib.UtreeError(_lib.E_NOMEM, what)
+        cap *= 4
+
+
+def tiles_format(db: CtrDB, buf, name_off, name_len, seq_len, tile_bp: int, step_bp: int, tquery, tindex, results):
+    """utree_tiles_format: the lines of tiles.tsv for tiles (tquery, tindex) of the framed queries and their results.  Returns (text, lines)."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    name_off, name_len = np.ascontiguousarray(name_off, dtype=np.uint64), np.ascontiguousarray(name_len, dtype=np.uint32)
+    seq_len, tquery, tindex = (np.ascontiguousarray(a, dtype=np.uint32) for a in (seq_len, tquery, tindex))
+    results = np.ascontiguousarray(results)
+    assert (results.dtype.itemsize == 24 or results.dtype == np.int32) and results.nbytes == 24 * len(tquery) and len(tquery) == len(tindex)
+    lines = C.c_uint64(0)
+
+    def call(out):
+        lines.value = 0
+        return _lib.load().utree_tiles_format(db._h, buf.ctypes.data, name_off.ctypes.data, name_len.ctypes.data, seq_len.ctypes.data, tile_bp,
+                                              step_bp, tquery.ctypes.data, tindex.ctypes.data, results.ctypes.data, len(tquery), out.ctypes.data,
+                                              len(out), C.byref(lines))
+    text = _tiles_text("utree_tiles_format", int(name_len.sum()) + 4096, call)
+    return text, lines.value
+
+
+def tiles_segments_format(db: CtrDB, buf, name_off, name_len, seq_len, tile_bp: int, step_bp: int, tquery, tindex, results, flush: bool = True,
+                          state=None):
+    """utree_tiles_segments_format: the lines of segments.tsv; `state` (a lib.TilesRun, or None for a fresh one) carries the open run from
+    one call to the next, flush closes it.  Returns (text, lines)."""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    name_off, name_len = np.ascontiguousarray(name_off, dtype=np.uint64), np.ascontiguousarray(name_len, dtype=np.uint32)
+    seq_len, tquery, tindex = (np.ascontiguousarray(a, dtype=np.uint32) for a in (seq_len, tquery, tindex))
+    results = np.ascontiguousarray(results)
+    assert (results.dtype.itemsize == 24 or results.dtype == np.int32) and results.nbytes == 24 * len(tquery) and len(tquery) == len(tindex)
+    if state is None:
+        state = _lib.TilesRun()
+    lines = C.c_uint64(0)
+
+    def call(out):
+        lines.value = 0
+        return _lib.load().utree_tiles_segments_format(db._h, buf.ctypes.data, name_off.ctypes.data, name_len.ctypes.data, seq_len.ctypes.data,
+                                                       tile_bp, step_bp, tquery.ctypes.data, tindex.ctypes.data, results.ctypes.data, len(tquery),
+                                                       int(flush), C.byref(state), out.ctypes.data, len(out), C.byref(lines))
+    text = _tiles_text("utree_tiles_segments_format", int(name_len.sum()) + 4096, call)
+    return text, lines.value
+
+
+def tiles_file(db: CtrDB, tree: DeviceTree, reads: str, tiles: str, segments=None, tile_bp: int = 1000, step_bp=None, rc: bool = False,
+               input_format: int = _lib.INPUT_REFERENCE, threads: int = 0):
+    """`utree-tiles db contigs.fa tiles.tsv [segments.tsv] [RC]`: every query of `reads` classified tile by tile (include/utree_amd.h:
+    utree_tiles_file).  Returns (code, TilesStats): code is OK, or E_FASTA after a malformed record (the tiles of the queries in front of it
+    are written); any other failure raises UtreeError, and neither file is left then."""
+    if step_bp is None:
+        step_bp = max(tile_bp // 2, 1)
+    prm = _lib.TilesParams(tile_bp=tile_bp, step_bp=step_bp, do_rc=int(rc), input_format=input_format, host_threads=threads)
+    st = _lib.TilesStats()
+    code = _lib.load().utree_tiles_file(db._h, tree._h, reads.encode(), tiles.encode(), segments.encode() if segments is not None else None,
+                                        C.byref(prm), C.byref(st))
+    if code not in (_lib.OK, _lib.E_FASTA):
+        raise _lib.UtreeError(code, "utree_tiles_file")
+    return code, st
 
 
 def classify_fasta_bytes(db: CtrDB, tree: DeviceTree, data: bytes, rc: bool = False) -> bytes:
