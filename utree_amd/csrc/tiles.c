@@ -35,7 +35,9 @@ int utree_tiles_plan(utree_dev *dev, const uint32_t *d_len, uint32_t n_reads, ui
     utk_tiles_ws w;
     char *base = (char *)(((uintptr_t)d_workspace + 255) & ~(uintptr_t)255);
     const size_t need = carve(&w, base, n_reads);
-    if (!need || (size_t)(base - (char *)d_workspace) + need > workspace_bytes) return UTREE_E_ARG;
+    /* what utree_tiles_workspace_bytes said, wherever the pointer lies: a caller one byte short is told so on every run, not only on those
+     * whose allocation happens to need the whole alignment slack */
+    if (!need || workspace_bytes < need + 256) return UTREE_E_ARG;
     if (hipSetDevice(dev->device) != hipSuccess) { utree_dev_set_hip_error((int)hipGetLastError(), "utree_tiles_plan: hipSetDevice"); return UTREE_E_HIP; }
     const int e = utk_tiles_plan(d_len, n_reads, tile_bp, step_bp, d_tile_first, d_meta, &w, stream);
     if (e) { utree_dev_set_hip_error(e, "utree_tiles_plan"); return UTREE_E_HIP; }
