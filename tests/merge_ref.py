@@ -32,6 +32,20 @@ def cut_before(a: bytes, m: int) -> bytes:
     return a[:pos]
 
 
+def step(st, lab: bytes, gg=True):
+    """The insert loop's step on a word the tree holds already under st (a label text or BAD), met again under lab.
+    Returns (the word's new state, the text the step cut st to -- a label from now on -- or None)."""
+    if st is BAD or st == lab:
+        return st, None
+    if not gg:
+        return BAD, None
+    m = shared_semicolons(st, lab)
+    if m < 2:
+        return BAD, None
+    st = cut_before(st, m)
+    return st, st
+
+
 def fold(inputs, gg=True):
     """The insert loop over the nodes of the inputs, input by input, each in file order.
     Returns (tree: word -> label text or BAD, labels: text -> index in order of creation, stats)."""
@@ -43,19 +57,9 @@ def fold(inputs, gg=True):
             if w not in tree:
                 tree[w] = lab
                 continue
-            st = tree[w]
-            if st is BAD or st == lab:
-                continue
-            if not gg:
-                tree[w] = BAD
-                continue
-            m = shared_semicolons(st, lab)
-            if m < 2:
-                tree[w] = BAD
-                continue
-            st = cut_before(st, m)
-            labels.setdefault(st, len(labels))                   # a text already present keeps its index
-            tree[w] = st
+            tree[w], cut = step(tree[w], lab, gg)
+            if cut is not None:
+                labels.setdefault(cut, len(labels))              # a text already present keeps its index
     shared = [w for w, ls in seen_in.items() if len(ls) > 1]
     stats = {"n_in_nodes": sum(len(db.nodes) for db in inputs), "n_shared": len(shared),
              "n_dropped": sum(tree[w] is BAD for w in shared),

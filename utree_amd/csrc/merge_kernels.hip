@@ -496,6 +496,12 @@ int utk_merge_open(const utk_merge_cfg *cfg, utk_merge_dev **out) {
     D->cap = cfg->cap_nodes ? cfg->cap_nodes : 1;
     D->out_chunk = D->cap < (16ull << 20) ? D->cap : (16ull << 20);
     D->stage_bytes = cfg->cap_raw + 512 < (256ull << 20) ? cfg->cap_raw + 512 : (256ull << 20);
+    {   /* test hooks: small inputs in many staging chunks and many output chunks; they only lower a size, to 1 at the least */
+        const char *e = getenv("UTREE_TEST_MERGE_STAGE_BYTES");
+        if (e && atoll(e) > 0 && (uint64_t)atoll(e) < D->stage_bytes) D->stage_bytes = (uint64_t)atoll(e);
+        e = getenv("UTREE_TEST_MERGE_OUT_NODES");
+        if (e && atoll(e) > 0 && (uint64_t)atoll(e) < D->out_chunk) D->out_chunk = (uint64_t)atoll(e);
+    }
     D->d_u_of_ix = (uint32_t **)calloc(cfg->n_in, sizeof(uint32_t *));
     if (!D->d_u_of_ix) { rc = UTREE_E_NOMEM; goto fail; }
     HK(hipSetDevice(cfg->device));
